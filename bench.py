@@ -2,8 +2,14 @@
 """Benchmarks of the MI355X hot path (BASELINE.json).  Default = the headline: SimCLR ResNet-18 training throughput
 on synthetic wafer maps.
 
-    python bench.py --gpus N --steps K --warmup W [--workload simclr_r18]
+    python bench.py --gpus N --steps K --warmup W [--workload simclr_r18] [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure (the objects below,
+the host preparation time, the exposed all-reduce cost of N > 1) takes runs of its own and comes with --full only.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs): the loss and the
+model's parameters and buffers after it for the training workloads, the top-k similarities and indices for knn_allpairs.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workloads (`--workload`; each prints ONE JSON line with the same schema, rank 0):
   simclr_r18        BASELINE configs[1] (default).  One step = fused two-view augmentation of 256 wafers per GPU
@@ -21,7 +27,7 @@ Workloads (`--workload`; each prints ONE JSON line with the same schema, rank 0)
 All device work runs in the hand-written HIP kernels of libwafer_hip.so; inputs are resident in HBM before the timed
 region.  The timed region holds EXACTLY K steps between two fences (barrier + synchronize), max over ranks.
 
-Extra objects on the line:
+Extra objects on the line (--full):
   roofline     : dominant kernels of the workload (conv implicit-GEMM for simclr_r18; Linear GEMMs + attention for
                  the transformers; the streaming pairwise-dot kernel for knn): algorithmic FLOPs (bytes) / summed
                  HIP-event durations of those launches on the launch stream, measured live on ONE eager step run
@@ -51,6 +57,33 @@ HBM_PEAK_GBS = 8000.0           # HBM3E, same table
 # launch (every operand once): 230 MB.
 R18_GFLOP_PER_SAMPLE = 21.76    # ResNet-18 fwd 3.627 GFLOP x 3 (fwd+bwd) x 2 views
 KNN_N, KNN_D, KNN_K = 811457, 128, 8
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, tensors) -> None:
+    """--dump-outputs: each tensor of {name: tensor} as <path>/<name>.npy, float32 (float64 for float64 and integer data,
+    which float32 would round).  Within DUMP_BUDGET_BYTES every array is whole; above it the smallest arrays stay whole
+    and each larger one keeps an equal share of what is left, as a fixed, seeded sample of its flattened elements
+    (ascending index order): the same arguments give the same sample from run to run."""
+    import numpy as np
+    import torch
+
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        arrays[name] = t.cpu().numpy()
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(0)
+    left = DUMP_BUDGET_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)   # (stable: ties keep the caller's order)
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+        left -= a.nbytes
+        np.save(path / f"{name}.npy", a)
 
 
 # --------------------------------------------------------------------------------------------- CPU baselines
@@ -384,9 +417,14 @@ def main():
     ap.add_argument("--workload", default="simclr_r18",
                     choices=["simclr_r18", "dino_vit_tiny", "dino_vit_small", "mae_vit_small_16", "mae_vit_b_32", "knn_allpairs"])
     ap.add_argument("--batch", type=int, default=None, help="wafers per GPU per step (default: 256 SimCLR, 64 DINO / MAE)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the knn / augment objects of the default line")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, host preparation time, exposed all-reduce "
+                         "cost (N > 1), and for simclr_r18 the augment / vit / knn objects and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the knn / augment / vit objects")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full: skip the roofline")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step into hipGraphs")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: one graph + one exposed all-reduce (no stages)")
     ap.add_argument("--sharded", action="store_true",
@@ -511,6 +549,8 @@ def main():
                 return wdist.sharded_knn_topk(q, shard, KNN_K, lo)
 
             dt, gpu_ms, (sim, idx) = timed(sstep, args.warmup, args.steps)
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, {"similarity": sim, "index": idx})
             mine = sim[rank * bq:(rank + 1) * bq]
             if not (bool((mine[:, 0] > 0.99).all()) and bool((sim[:, :-1] >= sim[:, 1:]).all())):
                 raise SystemExit("knn_allpairs --sharded: self-retrieval / sortedness check failed")
@@ -564,6 +604,8 @@ def main():
             return F.knn_topk_batched(q, bank, KNN_K, batch=bq, lanes=n_lanes)   # (joins its lanes before returning)
 
         dt, gpu_ms, (sim, idx) = timed(step_join, args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"similarity": sim, "index": idx})
         ok = bool((sim[:, 0] > 0.99).all()) and bool((sim[:, :-1] >= sim[:, 1:]).all())
         if not ok:
             raise SystemExit("knn_allpairs: self-retrieval / sortedness check failed")
@@ -594,9 +636,10 @@ def main():
     from ssl_wafermap_amd.models import SimCLR
     from ssl_wafermap_amd.transforms import BaseViewTransform
 
-    def run_training(workload, B, warmup, steps, roof_steps, keep=False):
-        """One training workload: (warm-up, hipGraph capture, W + K replayed steps between fences, `roof_steps` eager
-        steps with HIP-event brackets around the MFMA launches) -> (result dict, dataset or None)."""
+    def run_training(workload, B, warmup, steps, roof_steps, keep=False, dump=None):
+        """One training workload: (warm-up, hipGraph capture, W + K replayed steps between fences, [`dump`: the outputs
+        of the last step], with --full: `roof_steps` eager steps with HIP-event brackets around the MFMA launches)
+        -> (result dict, dataset or None)."""
         simclr = workload == "simclr_r18"
         torch.manual_seed(0)
         if simclr:
@@ -654,11 +697,19 @@ def main():
 
         dt, gpu_ms, loss = timed(step, warmup, steps)
         final_loss = check_finite(loss)
-        rccl_ranks, ar_exposed = 1, 0.0
+        if dump and rank == 0:
+            # what a caller of the step gets back: the loss, and the model's state after the step (written before any
+            # step of --full below moves it on)
+            outs = {"loss": loss}
+            outs.update({f"param.{k}": v for k, v in model.named_parameters()})
+            outs.update({f"buffer.{k}": v for k, v in model.named_buffers() if v.numel()})
+            dump_outputs(dump, outs)
+        rccl_ranks, ar_exposed = 1, (0.0 if world == 1 else None)
         if world > 1:
             one = torch.ones(1, device=dev)
             dist.all_reduce(one)                       # every rank of the job took part in a collective
             rccl_ranks = int(one.item())
+        if world > 1 and args.full:
             # exposed cost of the gradient exchange = the same steps with and without it, measured AFTER the timed region
             # (without the exchange the replicas drift apart: nothing from here on is a training result)
             m = max(5, min(20, steps))
@@ -677,13 +728,14 @@ def main():
             dt_without, _, _ = timed(step_local, 0, m)
             ar_exposed = max(0.0, (dt_with - dt_without) / m * 1e3)
 
-        # ---- after the timed region: host-side preparation cost of a step, and eager steps with event brackets
-        t0 = time.perf_counter()
-        for i in range(20):
-            ds.transform.sample(ds.store, (np.arange(B) + i * B) % len(ds), rng)
-        host_prepare_ms = (time.perf_counter() - t0) / 20 * 1e3
-        roof = None
-        if not args.no_kernel_timer and roof_steps > 0:
+        # ---- --full, after the timed region: host-side preparation cost of a step, and eager steps with event brackets
+        host_prepare_ms, roof = None, None
+        if args.full:
+            t0 = time.perf_counter()
+            for i in range(20):
+                ds.transform.sample(ds.store, (np.arange(B) + i * B) % len(ds), rng)
+            host_prepare_ms = round((time.perf_counter() - t0) / 20 * 1e3, 3)
+        if args.full and not args.no_kernel_timer and roof_steps > 0:
             kl = ("conv_igemm + conv3x3_patch + conv_wgrad (implicit-GEMM, bf16 MFMA)" if simclr else
                   "Linear GEMMs (conv_igemm 1x1 fwd / dgrad, conv_wgrad) + attn_fwd / attn_bwd, bf16 MFMA")
             tkey = "simclr_r18" if simclr else workload
@@ -779,9 +831,10 @@ def main():
                        "model_mfma_frac": round(value / world * gflop / 1e3 / MFMA_BF16_PEAK_TFLOPS, 4)},
             "final_loss": round(final_loss, 4),
             "rccl_ranks": rccl_ranks,                    # result of an all-reduce of ones over the job's process group
-            "all_reduce_ms_exposed": round(ar_exposed, 3),  # step time with minus without the gradient exchange (after the timed region)
+            # step time with minus without the gradient exchange (after the timed region; --full)
+            "all_reduce_ms_exposed": None if ar_exposed is None else round(ar_exposed, 3),
             "gpu_ms_per_step": round(gpu_ms, 3),          # HIP events around the K steps on the launch stream
-            "host_prepare_ms_per_step": round(host_prepare_ms, 3),  # drawing + checking the step's augmentation decisions
+            "host_prepare_ms_per_step": host_prepare_ms,  # drawing + checking the step's augmentation decisions (--full)
             "roofline": roof,
         }
         del graphed
@@ -791,8 +844,10 @@ def main():
 
     simclr = args.workload == "simclr_r18"
     B = args.batch or (256 if simclr else 64)
-    out, ds = run_training(args.workload, B, args.warmup, args.steps, 0 if args.no_kernel_timer else 3, keep=simclr)
-    if world == 1 and simclr and not args.no_secondary:
+    full_objects = args.full and world == 1 and simclr and not args.no_secondary
+    out, ds = run_training(args.workload, B, args.warmup, args.steps, 0 if args.no_kernel_timer else 3, keep=full_objects,
+                           dump=args.dump_outputs)
+    if full_objects:
         out["augment"] = augment_object(dev, ds, B)
         del ds
         torch.cuda.empty_cache()
@@ -803,7 +858,7 @@ def main():
                       "steps": vit["steps"], "hip_graph": vit["config"]["hip_graph"], "final_loss": vit["final_loss"],
                       "model_mfma_frac": vit["config"]["model_mfma_frac"], "roofline": vit["roofline"]}
         out["knn"] = knn_object(dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         if simclr and not args.no_secondary:
             out["knn"]["cpu_baseline"] = cpu_knn_baseline()

@@ -6,6 +6,7 @@ Run once in the build container (needs /root/reference; never runs on the GPU bo
 
 Inputs (reference checkout)                                        -> fixture (arrays only, LZMA-zipped .npz)
   data/processed/WM811K/train_1_split.pkl.xz    623 wafers + failureCode     -> wm811k_train_1_split.npz
+      (also copied verbatim -> wm811k_train_1_split.pkl.xz: the pandas pickle the ingest test reads)
   data/processed/WM811K/train_20_split.pkl.xz   12 449 wafers + failureCode  -> wm811k_train_20_split.npz
       (the file the reference's dummy mode trains on: scripts/WM811k_benchmark.py:87-97)
   data/interim/model_preds/SimSiam_preds_subset.pkl.xz  12 449 x 512 float16 backbone features of the SAME wafers
@@ -18,6 +19,7 @@ The wafer fixtures use WaferStore.save()'s keys (bytes, offsets, heights, widths
 `WaferStore.load(path)` reads them; np.load opens LZMA-compressed zip members transparently.
 """
 import io
+import shutil
 import zipfile
 from pathlib import Path
 
@@ -65,6 +67,7 @@ def mixed(name):
 def main():
     mixed("train_1_split")
     wafers("train_1_split")
+    shutil.copyfile(REF / "data/processed/WM811K/train_1_split.pkl.xz", OUT / "wm811k_train_1_split.pkl.xz")
     t20 = wafers("train_20_split")
     preds = pd.read_pickle(REF / "data/interim/model_preds/SimSiam_preds_subset.pkl.xz")
     emb = preds[list(range(512))].to_numpy().astype(np.float16)

@@ -13,6 +13,19 @@ import torch.multiprocessing as mp
 from oracle import ntxent as on
 
 
+@pytest.fixture(autouse=True)
+def _restore_kernel_entry_points():
+    """The stand-ins below replace kernel entry points of ssl_wafermap_amd.functional (and torch.cuda.synchronize) in
+    the process that runs them; put them back after every test, so that the GPU tests of the same session call the
+    kernels."""
+    import ssl_wafermap_amd.functional as F_hip
+
+    saved, sync = dict(vars(F_hip)), torch.cuda.synchronize
+    yield
+    vars(F_hip).update(saved)
+    torch.cuda.synchronize = sync
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

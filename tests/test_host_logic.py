@@ -230,18 +230,21 @@ def test_ingest_of_reference_pickles_and_flat_store_roundtrip(tmp_path):
         WaferStore.load(tmp_path / "bad.npz")
 
 
-_REF_SPLIT = "/root/reference/data/processed/WM811K/train_1_split.pkl.xz"
-
-
-@pytest.mark.skipif(not __import__("os").path.exists(_REF_SPLIT), reason="reference checkout not present")
 def test_ingest_reads_a_real_reference_split():
-    from ssl_wafermap_amd.data import read_wafer_pickle
+    """The reference's own processed file data/processed/WM811K/train_1_split.pkl.xz, stored verbatim as a fixture
+    (tests/golden/make_reference_data.py), reads into the same store as its converted .npz fixture."""
+    from conftest import GOLDEN
 
-    store, y = read_wafer_pickle(_REF_SPLIT)
+    from ssl_wafermap_amd.data import WaferStore, read_wafer_pickle
+
+    store, y = read_wafer_pickle(GOLDEN / "wm811k_train_1_split.pkl.xz")
     assert len(store) == len(y) > 100
     vals = np.unique(store.bytes_np)
     assert set(vals.tolist()) <= {0, 128, 255}
     assert 1 <= store.heights_np.min() and store.heights_np.max() <= 256
+    conv, y2 = WaferStore.load(GOLDEN / "wm811k_train_1_split.npz")
+    assert np.array_equal(store.bytes_np, conv.bytes_np) and np.array_equal(store.offsets_np, conv.offsets_np)
+    assert np.array_equal(y, y2)
 
 
 def test_multiply_high_division_identity():
@@ -308,3 +311,30 @@ def test_view_branches_and_parallel_branch_switches_fail_loudly_without_a_gpu():
     with ops.branch(1):
         assert ops.current_branch() == 1
     assert ops.current_branch() == 0
+
+
+def test_bench_dump_outputs_keeps_the_budget_and_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 (float64 for integer data), whole arrays within the budget; above it the small
+    arrays stay whole and the large ones are cut to a sample that is the same from run to run."""
+    import importlib.util
+    from pathlib import Path
+
+    spec = importlib.util.spec_from_file_location("bench", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    outs = {"loss": torch.tensor(2.5), "w": torch.randn(300, 100, generator=g).bfloat16(),
+            "idx": torch.arange(50, dtype=torch.int64), "big": torch.randn(40_000, generator=g)}
+    bench.dump_outputs(tmp_path / "whole", outs)
+    for k, v in outs.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == (np.float64 if k == "idx" else np.float32) and np.array_equal(a, v.double().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, outs)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in outs}
+    assert sum(v.nbytes for v in a.values()) <= 100_000
+    assert a["loss"] == 2.5 and np.array_equal(a["idx"], np.arange(50.0))
+    assert 0 < a["w"].size < 30_000 and np.isin(a["w"], outs["w"].float().numpy()).all()
+    assert 0 < a["big"].size < 40_000 and np.isin(a["big"], outs["big"].numpy()).all()
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in a.items())

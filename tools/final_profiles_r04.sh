@@ -1,9 +1,10 @@
 #!/bin/bash
 # End-of-round evidence on one MI355X -> gpurun_out/final_*  (python tools/collect_final_r04.py copies it into profiles/r04_*).
-#   tools/final_profiles_r04.sh            (~3 min of GPU time)
+#   tools/final_profiles_r04.sh <dir>      (~3 min of GPU time)
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$root"
-python bench.py > gpurun_out/final_bench_default.json 2> gpurun_out/final_bench_default.err
+out=${1:?"usage: $0 <directory of the final_* files: where tools/profile_bench.sh and tools/pmc_bench.sh write theirs>"}
+python bench.py --full > "$out/final_bench_default.json" 2> "$out/final_bench_default.err"
 # kernel tables: every launch alone on the device (the parallel branches of the step switched off -- rocprofv3 serialises
 # overlapping launches anyway, and a launch that shares the chip is not a measurement of the kernel)
 WM_VIEW_BRANCHES=0 WM_DINO_TEACHER_STREAM=0 WM_PROFILE_MARKER=sgd_step bash tools/profile_bench.sh final_trace_simclr_r18 10 14 --no-kernel-timer
@@ -13,7 +14,7 @@ WM_PROFILE_MARKER=adamw_kernel bash tools/profile_bench.sh final_trace_mae_vit_s
 WM_PROFILE_MARKER=sgd_step bash tools/profile_bench.sh final_trace_simclr_r18_branches 10 14 --no-kernel-timer
 WM_PROFILE_MARKER=adamw_kernel bash tools/profile_bench.sh final_trace_dino_vit_tiny_branches 10 14 --workload dino_vit_tiny --no-kernel-timer
 for w in dino_vit_tiny dino_vit_small mae_vit_small_16 mae_vit_b_32; do
-  python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/final_bench_$w.json 2>/dev/null
+  python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline > "$out/final_bench_$w.json" 2>/dev/null
 done
 python bench.py --workload knn_allpairs --batch 64 --steps 200 --warmup 20 > gpurun_out/final_bench_knn_allpairs_b64.json 2>/dev/null
 python bench.py --workload knn_allpairs --steps 50 --warmup 5 > gpurun_out/final_bench_knn_allpairs.json 2>/dev/null
