@@ -622,11 +622,12 @@ int wm_lars_step(float* params, const float* grads, float* momentum_buf, const l
  * gradient. */
 int wm_matmul_f32(const float* a, const float* b, float* c, int M, int N, int K, int trans_a, void* stream);
 
-/* ---- Float32 "parity" preset (csrc/f32path.hip): the FORWARD pass of the SimCLR / DINO / MAE steps with every activation,
- * weight and accumulator in float32 (reference call sites scripts/WM811k_benchmark.py:236-248, :578-588, :902-947).  The
- * production kernels keep activations in bf16; profiles/r04_error_budget_bf16.md shows that storage puts the step losses
- * 0.4e-4 .. 3.4e-4 from the float32 reference (north_star: 1e-4).  These entry points keep them in float32: a validation
- * preset (forward for all three models, backward for the ResNet-18 / head ops), selected by ssl_wafermap_amd.precision("float32").  Activations NHWC float32 / [rows][C]. */
+/* ---- Float32 "parity" preset (csrc/f32path.hip): the forward pass (and, below, the backward pieces) of the SimCLR / DINO /
+ * MAE steps with every activation, weight and accumulator in float32 (reference call sites scripts/WM811k_benchmark.py:236-248,
+ * :578-588, :902-947).  The production kernels keep activations in bf16; profiles/r04_error_budget_bf16.md shows that storage
+ * puts the step losses 0.4e-4 .. 3.4e-4 from the float32 reference (north_star: 1e-4).  These entry points keep them in
+ * float32: a validation preset (forward for all three models; backward for the ResNet-18 / head ops and the MAE / SimMIM
+ * transformer ops), selected by ssl_wafermap_amd.precision("float32").  Activations NHWC float32 / [rows][C]. */
 size_t wm_f32_conv2d_workspace_bytes(int C, int K, int R, int S);
 /* y = act(conv(x, w) + bias) + residual: x [N][H][W][C], w_oihw [K][C][R][S] (the float32 master layout), bias [K] or NULL,
  * residual [N][P][Q][K] or NULL, act 0 none / 1 GELU (erf) / 2 ReLU.  A Linear layer is the 1x1 case on a 1x1 image. */
@@ -674,6 +675,27 @@ int wm_f32_bn_bwd(const float* y, const float* dout, const float* out_relu, cons
                   void* workspace, size_t workspace_bytes, void* stream);
 int wm_f32_maxpool3x3s2_bwd(const float* x, const float* dy, int N, int H, int W, int C, float* dx, void* stream);
 int wm_f32_gap_bwd(const float* dy, int N, int HW, int C, float* dx, void* stream);
+/* Backward pieces of the transformer path (the float32 preset can take whole MAE / SimMIM optimiser steps:
+ * scripts/WM811k_benchmark.py:876-957, :960-1030).  No float atomics: sums over rows go through per-block slots added in a
+ * fixed order, so two runs give the same bits.
+ * wm_f32_layernorm_bwd: input gradient dx of wm_f32_layernorm for dy [rows][C] (statistics recomputed as the forward takes
+ * them); dgamma / dbeta [C] (either may be NULL) = sum dy * xhat, sum dy.  Workspace: wm_f32_layernorm_bwd_workspace_bytes. */
+size_t wm_f32_layernorm_bwd_workspace_bytes(long long rows, int C);
+int wm_f32_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, long long rows, int C, float* dx,
+                         float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dy * act'(x + bias) on [rows][C] (bias optional): act 1 exact GELU (Phi(v) + v phi(v)), 2 ReLU, 0 copies dy.  The bias
+ * gradient is wm_f32_colsum of dx; a fused-GELU Linear passes its recomputed pre-activation as x. */
+int wm_f32_bias_act_bwd(const float* x, const float* bias, const float* dy, int act, long long rows, int C, float* dx,
+                        void* stream);
+/* Gradient of wm_f32_attention: qkv [B*S][3][H][HD], out [B*S][H*HD] (the forward's output), dout [B*S][H*HD]
+ * -> dqkv [B*S][3][H][HD].  One workgroup per (image, head): a query pass (dq) then a key pass (dk, dv); HD 64 or 32, LDS
+ * (2 * S * HD + 3 * S) floats (WM_EUNSUPPORTED beyond 160 KiB). */
+int wm_f32_attention_bwd(const float* qkv, const float* out, const float* dout, int B, int S, int H, int HD, float scale,
+                         float* dqkv, void* stream);
+/* Gradient of wm_f32_reduce's losses: dpred = f'(pred - target) * scale * g, mode 1 (squared difference) f' = 2 (pred - target),
+ * mode 2 (absolute difference) f' = sign(pred - target); g = *grad_out (device scalar) or 1 when grad_out is NULL. */
+int wm_f32_loss_bwd(const float* pred, const float* target, long long n, int mode, double scale, const float* grad_out,
+                    float* dpred, void* stream);
 /* center = center * momentum + (1 - momentum) * column mean of teacher [rows][D]. */
 int wm_f32_center_update(float* center, const float* teacher, int rows, int D, float momentum, void* stream);
 

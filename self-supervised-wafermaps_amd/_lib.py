@@ -75,6 +75,12 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wm_f32_maxpool3x3s2_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "wm_f32_gap_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wm_f32_layernorm_bwd_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "wm_f32_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_longlong, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "wm_f32_bias_act_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
+    "wm_f32_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "wm_f32_loss_bwd": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "wm_version": (c_int, []),
     "wm_error_string": (c_char_p, [c_int]),
     "wm_ln_linear_fwd_ok": (c_int, [c_int, c_int, c_int]),

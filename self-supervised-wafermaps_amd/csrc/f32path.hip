@@ -9,7 +9,8 @@
 // those activations in float32: same module tree, same state_dict, same call sites
 // (scripts/WM811k_benchmark.py:236-248 SimCLR, :578-588 DINOViT, :902-947 MAE), plain loops instead of MFMA tiles.
 // It is a validation preset (~50x slower than the bf16 path): forward for all three models, backward for the ResNet-18 /
-// projection-head ops (whole SimCLR optimiser steps follow the oracle to 1e-5).
+// projection-head ops (whole SimCLR optimiser steps follow the oracle to 1e-5) and for the MAE / SimMIM transformer ops
+// (LayerNorm, GELU, attention, MSE / L1; DINO's loss has no backward here yet).
 //
 // Layouts: activations NHWC float32 ([rows][C] for token / feature matrices), weights in their float32 master layout
 // (OIHW / [K][C]); the implicit-GEMM kernel reads them through a [R*S*C][K] copy made per call.
@@ -663,6 +664,249 @@ __global__ __launch_bounds__(FT) void f32_colsum(const float* __restrict__ x, lo
   out[c] = (float)s;
 }
 
+// ---- backward pieces of the transformer path (MAE / SimMIM optimiser steps under the preset)
+// LayerNorm backward, one wave per row: the forward's statistics recomputed with the same arithmetic (double sums, float
+// mean / rstd); gg = dy * gamma, dx = rstd * (gg - mean(gg) - xhat * mean(gg * xhat)) with the two means in double.  The
+// row's (mean, rstd) go to `stats` [rows][2] for the parameter sums.
+__global__ __launch_bounds__(64) void f32_layernorm_bwd(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                       const float* __restrict__ dy, float eps, int C, float* __restrict__ dx,
+                                                       float* __restrict__ stats) {
+  const long long row = blockIdx.x;
+  const float* xr = x + row * C;
+  const float* gr = dy + row * C;
+  double s = 0.0;
+  for (int c = threadIdx.x; c < C; c += 64) s += (double)xr[c];
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  const double mean = s / C;
+  double q = 0.0;
+  for (int c = threadIdx.x; c < C; c += 64) {
+    const double d = (double)xr[c] - mean;
+    q += d * d;
+  }
+  for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
+  const float rstd = (float)(1.0 / sqrt(q / C + (double)eps)), fm = (float)mean;
+  double a = 0.0, b = 0.0;
+  for (int c = threadIdx.x; c < C; c += 64) {
+    const float gg = gr[c] * gamma[c];
+    a += (double)gg;
+    b += (double)gg * (double)((xr[c] - fm) * rstd);
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  const float ma = (float)(a / C), mb = (float)(b / C);
+  for (int c = threadIdx.x; c < C; c += 64) {
+    const float xh = (xr[c] - fm) * rstd;
+    dx[row * C + c] = rstd * (gr[c] * gamma[c] - ma - xh * mb);
+  }
+  if (threadIdx.x == 0) {
+    stats[row * 2 + 0] = fm;
+    stats[row * 2 + 1] = rstd;
+  }
+}
+
+// LayerNorm parameter sums over row slices (f32_bn_bwd_sums' layout with G = 1, per-row statistics):
+// part [RB][2][C] = (sum dy, sum dy * xhat) of slice rb; f32_bn_bwd_finalize adds the slices in order.
+__global__ __launch_bounds__(FT) void f32_ln_param_sums(const float* __restrict__ x, const float* __restrict__ dy,
+                                                       const float* __restrict__ stats, long long rows, int C, int RB,
+                                                       double* __restrict__ part) {
+  __shared__ double red[2][8][32];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + tx, rb = blockIdx.y;
+  double s1 = 0.0, s2 = 0.0;
+  if (c < C) {
+    for (long long r = (long long)rb * 8 + ty; r < rows; r += (long long)RB * 8) {
+      const size_t o = (size_t)r * C + c;
+      const float gv = dy[o];
+      s1 += (double)gv;
+      s2 += (double)gv * (double)((x[o] - stats[r * 2 + 0]) * stats[r * 2 + 1]);
+    }
+  }
+  red[0][ty][tx] = s1;
+  red[1][ty][tx] = s2;
+  __syncthreads();
+  if (ty == 0 && c < C) {
+    double a = 0.0, b = 0.0;
+    for (int i = 0; i < 8; ++i) {
+      a += red[0][i][tx];
+      b += red[1][i][tx];
+    }
+    part[((size_t)rb * 2 + 0) * C + c] = a;
+    part[((size_t)rb * 2 + 1) * C + c] = b;
+  }
+}
+
+// dx = dy * act'(x + bias): exact GELU' = Phi(v) + v * phi(v), ReLU' = (v > 0); act 0 copies dy
+__global__ __launch_bounds__(FT) void f32_act_bwd(const float* __restrict__ x, const float* __restrict__ bias,
+                                                 const float* __restrict__ dy, int act, long long rows, int C,
+                                                 float* __restrict__ dx) {
+  const long long total = rows * C;
+  for (long long i = (long long)blockIdx.x * FT + threadIdx.x; i < total; i += (long long)gridDim.x * FT) {
+    float g = dy[i];
+    if (act != 0) {
+      float v = x[i];
+      if (bias) v += bias[i % C];
+      if (act == 1) {
+        const float cdf = 0.5f * (1.f + erff(v * 0.70710678118654752440f));
+        const float pdf = 0.39894228040143267794f * expf(-0.5f * v * v);
+        g *= cdf + v * pdf;
+      } else if (!(v > 0.f)) {
+        g = 0.f;
+      }
+    }
+    dx[i] = g;
+  }
+}
+
+// d pred = f'(pred - target) * scale * g: mode 1 (MSE) 2 (pred - target), mode 2 (L1) sign(pred - target) (0 at 0);
+// g = *grad_out (the loss's incoming gradient, on the device) or 1
+__global__ __launch_bounds__(FT) void f32_loss_bwd(const float* __restrict__ pred, const float* __restrict__ target, long long n,
+                                                  int mode, float scale, const float* __restrict__ grad_out,
+                                                  float* __restrict__ dpred) {
+  const float gs = (grad_out ? grad_out[0] : 1.f) * scale;
+  for (long long i = (long long)blockIdx.x * FT + threadIdx.x; i < n; i += (long long)gridDim.x * FT) {
+    const float d = pred[i] - target[i];
+    const float f = mode == 1 ? 2.f * d : (float)((d > 0.f) - (d < 0.f));
+    dpred[i] = f * gs;
+  }
+}
+
+// Attention backward of one (image, head), no atomics.  Every row (query or key) is served by L = HD / 16 adjacent lanes,
+// each holding 16 of its head dimensions; dot products are 16-term fmaf chains joined by an xor butterfly (every lane of
+// the group ends with the same bits).
+//   pass 1 (queries, K and V in LDS): the softmax statistics as the forward takes them (row maximum of s * scale, then the
+//          sum of the exponentials), D_i = dO_i . O_i, dq_i = scale * sum_j p_ij (dO_i . v_j - D_i) k_j.
+//   pass 2 (keys, Q and dO in LDS in place of K and V, statistics beside them): dv_j = sum_i p_ij dO_i,
+//          dk_j = scale * sum_i p_ij (dO_i . v_j - D_i) q_i -- p_ij recomputed from the same operands in the same order.
+// LDS: 2 * S * HD + 3 * S floats.  qkv / dqkv [B*S][3][H][HD], out / dout [B*S][H*HD].
+template <int L>
+__device__ __forceinline__ float f32_group_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < L; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ void f32_load16(float* r, const float* p) {
+#pragma unroll
+  for (int d = 0; d < 16; d += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(p + d);
+    r[d] = v.x;
+    r[d + 1] = v.y;
+    r[d + 2] = v.z;
+    r[d + 3] = v.w;
+  }
+}
+
+__device__ __forceinline__ float f32_dot16(const float* r, const float* p) {
+  float s = 0.f;
+#pragma unroll
+  for (int d = 0; d < 16; d += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(p + d);
+    s = fmaf(r[d], v.x, s);
+    s = fmaf(r[d + 1], v.y, s);
+    s = fmaf(r[d + 2], v.z, s);
+    s = fmaf(r[d + 3], v.w, s);
+  }
+  return s;
+}
+
+template <int HD>
+__global__ __launch_bounds__(FT) void f32_attention_bwd(const float* __restrict__ qkv, const float* __restrict__ out,
+                                                       const float* __restrict__ dout, int S, int H, float scale,
+                                                       float* __restrict__ dqkv) {
+  constexpr int L = HD / 16;
+  constexpr int RPI = FT / L;  // rows served per iteration
+  extern __shared__ __attribute__((aligned(16))) float f32_smem[];
+  float* sa = f32_smem;                     // pass 1: K, pass 2: Q
+  float* sb = f32_smem + (size_t)S * HD;    // pass 1: V, pass 2: dO
+  float* st = f32_smem + (size_t)2 * S * HD;  // [S][3]: row maximum, 1 / sum, D
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+  const size_t rs = (size_t)3 * H * HD, os = (size_t)H * HD;
+  const int t = threadIdx.x % L, r0 = threadIdx.x / L;
+  const int dof = t * 16;
+  for (int i = threadIdx.x; i < S * HD; i += FT) {
+    const int j = i / HD, d = i - j * HD;
+    const float* base = qkv + ((size_t)b * S + j) * rs + (size_t)h * HD + d;
+    sa[i] = base[(size_t)H * HD];
+    sb[i] = base[(size_t)2 * H * HD];
+  }
+  __syncthreads();
+  for (int i = r0; i < S; i += RPI) {
+    float q[16], g[16], acc[16];
+    const size_t row = (size_t)b * S + i;
+    f32_load16(q, qkv + row * rs + (size_t)h * HD + dof);
+    f32_load16(g, dout + row * os + (size_t)h * HD + dof);
+    const float dd = f32_group_sum<L>(f32_dot16(g, out + row * os + (size_t)h * HD + dof));
+    float mx = -INFINITY;
+    for (int j = 0; j < S; ++j) mx = fmaxf(mx, f32_group_sum<L>(f32_dot16(q, sa + (size_t)j * HD + dof)) * scale);
+    float l = 0.f;
+    for (int j = 0; j < S; ++j) l += expf(f32_group_sum<L>(f32_dot16(q, sa + (size_t)j * HD + dof)) * scale - mx);
+    const float inv = 1.f / l;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) acc[d] = 0.f;
+    for (int j = 0; j < S; ++j) {
+      const float* kj = sa + (size_t)j * HD + dof;
+      const float p = expf(f32_group_sum<L>(f32_dot16(q, kj)) * scale - mx) * inv;
+      const float dp = f32_group_sum<L>(f32_dot16(g, sb + (size_t)j * HD + dof));
+      const float ds = p * (dp - dd);
+#pragma unroll
+      for (int d = 0; d < 16; ++d) acc[d] = fmaf(ds, kj[d], acc[d]);
+    }
+    float* dq = dqkv + row * rs + (size_t)h * HD + dof;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) dq[d] = acc[d] * scale;
+    if (t == 0) {
+      st[i * 3 + 0] = mx;
+      st[i * 3 + 1] = inv;
+      st[i * 3 + 2] = dd;
+    }
+  }
+  __syncthreads();  // K and V are read no more: Q and dO take their place
+  for (int i = threadIdx.x; i < S * HD; i += FT) {
+    const int j = i / HD, d = i - j * HD;
+    sa[i] = qkv[((size_t)b * S + j) * rs + (size_t)h * HD + d];
+    sb[i] = dout[((size_t)b * S + j) * os + (size_t)h * HD + d];
+  }
+  __syncthreads();
+  for (int j = r0; j < S; j += RPI) {
+    float k[16], v[16], dk[16], dv[16];
+    const size_t row = (size_t)b * S + j;
+    f32_load16(k, qkv + row * rs + (size_t)H * HD + (size_t)h * HD + dof);
+    f32_load16(v, qkv + row * rs + (size_t)2 * H * HD + (size_t)h * HD + dof);
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+      dk[d] = 0.f;
+      dv[d] = 0.f;
+    }
+    for (int i = 0; i < S; ++i) {
+      const float* qi = sa + (size_t)i * HD + dof;
+      const float* gi = sb + (size_t)i * HD + dof;
+      // the same fmaf chain as pass 1's q . k_j (query operand first)
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < 16; ++d) s = fmaf(qi[d], k[d], s);
+      const float p = expf(f32_group_sum<L>(s) * scale - st[i * 3 + 0]) * st[i * 3 + 1];
+      float dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < 16; ++d) dp = fmaf(gi[d], v[d], dp);
+      const float ds = p * (f32_group_sum<L>(dp) - st[i * 3 + 2]);
+#pragma unroll
+      for (int d = 0; d < 16; ++d) {
+        dv[d] = fmaf(p, gi[d], dv[d]);
+        dk[d] = fmaf(ds, qi[d], dk[d]);
+      }
+    }
+    float* dkp = dqkv + row * rs + (size_t)H * HD + (size_t)h * HD + dof;
+    float* dvp = dqkv + row * rs + (size_t)2 * H * HD + (size_t)h * HD + dof;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+      dkp[d] = dk[d] * scale;
+      dvp[d] = dv[d];
+    }
+  }
+}
+
 inline int grid_for(long long items) {
   long long b = (items + FT - 1) / FT;
   if (b > 65535) b = 65535;
@@ -833,8 +1077,13 @@ extern "C" int wm_f32_conv2d_dgrad(const float* dy, const float* w_oihw, float* 
   return WM_OK;
 }
 
-static int f32_wgrad_slabs(long long M) {
-  long long z = (M + 4095) / 4096;
+// Pixel ranges of the weight gradient: 4096 pixels per slab for the convolutions; 256 rows for a Linear layer (the 1 x 1 case
+// on a 1 x 1 image, rows = tokens).  A transformer's weight gradients are the bulk of its gradient, and one 1576-term float
+// chain per weight (the MAE decoder's 8 x 197 tokens) put them 3x further from float64 than a blocked float32 GEMM lands;
+// slabs of 256 rows summed in double do not.  (A SimCLR projection head at batch 64, 128 rows, stays in one slab.)
+static int f32_wgrad_slabs(long long M, bool linear) {
+  const long long chunk = linear ? 256 : 4096;
+  long long z = (M + chunk - 1) / chunk;
   if (z > 256) z = 256;
   if (z < 1) z = 1;
   return (int)z;
@@ -842,7 +1091,8 @@ static int f32_wgrad_slabs(long long M) {
 
 extern "C" size_t wm_f32_conv2d_wgrad_workspace_bytes(int N, int P, int Q, int C, int K, int R, int S) {
   if (N <= 0 || P <= 0 || Q <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0) return 0;
-  return (size_t)f32_wgrad_slabs((long long)N * P * Q) * K * R * S * C * sizeof(float);
+  const bool linear = P == 1 && Q == 1 && R == 1 && S == 1;
+  return (size_t)f32_wgrad_slabs((long long)N * P * Q, linear) * K * R * S * C * sizeof(float);
 }
 
 extern "C" int wm_f32_conv2d_wgrad(const float* dy, const float* x, float* dw_oihw, int N, int H, int W, int C, int K, int R,
@@ -853,7 +1103,7 @@ extern "C" int wm_f32_conv2d_wgrad(const float* dy, const float* x, float* dw_oi
   WM_REQUIRE(P == (H + 2 * pad - R) / stride + 1 && Q == (W + 2 * pad - S) / stride + 1 && P > 0 && Q > 0, WM_EINVAL);
   WM_REQUIRE(workspace_bytes >= wm_f32_conv2d_wgrad_workspace_bytes(N, P, Q, C, K, R, S), WM_EWORKSPACE);
   const long long M = (long long)N * P * Q;
-  const int Z = f32_wgrad_slabs(M);
+  const int Z = f32_wgrad_slabs(M, P == 1 && Q == 1 && R == 1 && S == 1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   F32Wgrad a{dy, x, static_cast<float*>(workspace), N, H, W, C, K, R, S, P, Q, stride, pad, (M + Z - 1) / Z};
   f32_conv_wgrad<<<dim3((K + 63) / 64, (R * S * C + 63) / 64, Z), FT, 0, st>>>(a);
@@ -901,6 +1151,72 @@ extern "C" int wm_f32_maxpool3x3s2_bwd(const float* x, const float* dy, int N, i
 extern "C" int wm_f32_gap_bwd(const float* dy, int N, int HW, int C, float* dx, void* stream) {
   WM_REQUIRE(dy && dx && N > 0 && HW > 0 && C > 0, WM_EINVAL);
   f32_gap_bwd<<<grid_for((long long)N * HW * C), FT, 0, static_cast<hipStream_t>(stream)>>>(dy, N, HW, C, dx);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_f32_layernorm_bwd_workspace_bytes(long long rows, int C) {
+  if (rows <= 0 || C <= 0) return 0;
+  const int RB = 64;
+  return (size_t)RB * 2 * C * sizeof(double) + (size_t)2 * C * sizeof(float) + (size_t)rows * 2 * sizeof(float);
+}
+
+extern "C" int wm_f32_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, long long rows, int C,
+                                    float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  WM_REQUIRE(x && gamma && dy && dx && workspace && rows > 0 && rows < (1ll << 31) && C > 0, WM_EINVAL);
+  WM_REQUIRE(workspace_bytes >= wm_f32_layernorm_bwd_workspace_bytes(rows, C), WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int RB = 64;
+  double* part = static_cast<double*>(workspace);                        // [RB][2][C]
+  float* coef = reinterpret_cast<float*>(part + (size_t)RB * 2 * C);      // [2][C] (finalize's by-product, unused)
+  float* stats = coef + (size_t)2 * C;                                    // [rows][2]
+  f32_layernorm_bwd<<<(unsigned)rows, 64, 0, st>>>(x, gamma, dy, eps, C, dx, stats);
+  WM_LAUNCH_CHECK();
+  if (dgamma || dbeta) {
+    f32_ln_param_sums<<<dim3((C + 31) / 32, RB), FT, 0, st>>>(x, dy, stats, rows, C, RB, part);
+    WM_LAUNCH_CHECK();
+    f32_bn_bwd_finalize<<<(C + FT - 1) / FT, FT, 0, st>>>(part, RB, 1, C, rows, coef, dgamma, dbeta);
+    WM_LAUNCH_CHECK();
+  }
+  return WM_OK;
+}
+
+extern "C" int wm_f32_bias_act_bwd(const float* x, const float* bias, const float* dy, int act, long long rows, int C, float* dx,
+                                   void* stream) {
+  WM_REQUIRE(dy && dx && rows > 0 && C > 0 && act >= 0 && act <= 2 && (act == 0 || x), WM_EINVAL);
+  f32_act_bwd<<<grid_for(rows * C), FT, 0, static_cast<hipStream_t>(stream)>>>(x, bias, dy, act, rows, C, dx);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_f32_attention_bwd(const float* qkv, const float* out, const float* dout, int B, int S, int H, int HD,
+                                    float scale, float* dqkv, void* stream) {
+  WM_REQUIRE(qkv && out && dout && dqkv && B > 0 && S > 0 && H > 0, WM_EINVAL);
+  WM_REQUIRE(HD == 64 || HD == 32, WM_EUNSUPPORTED);
+  const size_t lds = ((size_t)2 * S * HD + (size_t)3 * S) * sizeof(float);
+  WM_REQUIRE(lds <= 160 * 1024, WM_EUNSUPPORTED);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t e;
+  if (HD == 64) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&f32_attention_bwd<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+    if (e != hipSuccess) return (int)e;
+    f32_attention_bwd<64><<<B * H, FT, lds, st>>>(qkv, out, dout, S, H, scale, dqkv);
+  } else {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&f32_attention_bwd<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+    if (e != hipSuccess) return (int)e;
+    f32_attention_bwd<32><<<B * H, FT, lds, st>>>(qkv, out, dout, S, H, scale, dqkv);
+  }
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_f32_loss_bwd(const float* pred, const float* target, long long n, int mode, double scale, const float* grad_out,
+                               float* dpred, void* stream) {
+  WM_REQUIRE(pred && target && dpred && n > 0 && (mode == 1 || mode == 2), WM_EINVAL);
+  f32_loss_bwd<<<grid_for(n), FT, 0, static_cast<hipStream_t>(stream)>>>(pred, target, n, mode, (float)scale, grad_out, dpred);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

@@ -159,7 +159,7 @@ class MAEBackbone(nn.Module):
     def encode_tokens(self, tokens, batch: int):
         """lightly MAEEncoder.forward(tokens): + positional embedding, encoder blocks, final LayerNorm."""
         seq, c = self.seq_length, self.hidden_dim
-        pos = self.encoder.pos_embedding.to(ops.act_dtype()).expand(batch, seq, c).reshape(batch * seq, c)
+        pos = vit_ops.broadcast_rows(self.encoder.pos_embedding, batch).reshape(batch * seq, c)
         t = vit_ops.bias_act(tokens.reshape(batch * seq, c), None, vit_ops.ACT_NONE, residual=pos)
         return self.encoder.run_layers(t, batch, seq).view(batch, seq, c)
 
@@ -202,7 +202,7 @@ class MAEDecoder(nn.Module):
 
     def decode(self, x):
         b, s, c = x.shape
-        pos = self.pos_embedding.to(ops.act_dtype()).expand(b, s, c).reshape(b * s, c)
+        pos = vit_ops.broadcast_rows(self.pos_embedding, b).reshape(b * s, c)
         t = vit_ops.bias_act(x.reshape(b * s, c), None, vit_ops.ACT_NONE, residual=pos)
         for blk in self.layers:
             t = blk(t, b, s)

@@ -8,7 +8,8 @@ the reference's float32 CPU path (loss 1e-4 relative, embeddings 1e-3 cosine).  
 profiles/r04_error_budget_bf16.md shows why the bf16 preset cannot: bf16 storage of the inter-layer activations, the
 same distance torch's own bf16 autocast lands at.  A validation preset (~50x slower): the ResNet-18 / projection-head
 path (convolution, BatchNorm, pooling, Linear, NT-Xent) has its backward pass, so whole SimCLR optimiser steps follow the
-oracle to 1e-5; the transformer steps (DINO, MAE) run forward only and raise when differentiated.
+oracle to 1e-5; so do the MAE and SimMIM transformer steps (LayerNorm, GELU, attention, token moves, MSE / L1 backward).
+DINO's loss has no backward pass under the preset yet and raises when differentiated.
 
     with ssl_wafermap_amd.precision("float32"):
         loss = model.training_step(batch, 0)

@@ -109,8 +109,21 @@ def random_token_mask(size: Tuple[int, int], mask_ratio: float = 0.6, mask_class
     return indices[:, :num_keep], indices[:, num_keep:]
 
 
+def _f32_token_rows(token: torch.Tensor, rows: int):
+    """float32 preset, device token [1, 1, C]: `rows` copies whose gradient is summed by the library (f32path.broadcast);
+    None otherwise."""
+    from .. import f32path, precision
+
+    if precision.is_f32() and token.is_cuda and token.dim() == 3 and token.shape[0] == token.shape[1] == 1:
+        return f32path.broadcast(token, rows)
+    return None
+
+
 def repeat_token(token: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     batch_size, sequence_length = size
+    rows = _f32_token_rows(token, batch_size * sequence_length)
+    if rows is not None:
+        return rows.view(batch_size, sequence_length, token.shape[-1])
     return token.repeat(batch_size, sequence_length, 1)
 
 
@@ -125,6 +138,8 @@ def patchify(images: torch.Tensor, patch_size: int) -> torch.Tensor:
     from .. import precision
 
     if precision.is_f32():   # float32 preset: pure data movement (lightly's einsum "nchpwq->nhwpqc")
+        if images.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("patchify (float32 preset): no gradient to the images (they are the MAE / SimMIM target)")
         g = h // patch_size
         x = images.detach().float().reshape(n, c, g, patch_size, g, patch_size)
         return x.permute(0, 2, 4, 3, 5, 1).reshape(n, g * g, patch_size * patch_size * c).contiguous()
@@ -153,6 +168,9 @@ def set_at_index(tokens: torch.Tensor, index: torch.Tensor, value: torch.Tensor)
 
 def mask_at_index(tokens: torch.Tensor, index: torch.Tensor, mask_token: torch.Tensor) -> torch.Tensor:
     b, k = index.shape
+    rows = _f32_token_rows(mask_token, b * k)
+    if rows is not None:
+        return set_at_index(tokens, index, rows.view(b, k, tokens.shape[2]))
     return set_at_index(tokens, index, mask_token.to(tokens.dtype).expand(b, k, tokens.shape[2]))
 
 

@@ -339,6 +339,14 @@ def const_matmul(m: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
     return _ConstMatmul.apply(m, p)
 
 
+def broadcast_rows(t: torch.Tensor, n: int) -> torch.Tensor:
+    """[n, *t.shape[1:]]: t [1, ...] (a positional embedding or a token) repeated over n images, in the activation dtype.
+    Under the float32 preset the gradient sums the n copies with the library's ordered column sum (f32path.broadcast)."""
+    if _precision.is_f32():
+        return f32path.broadcast(t, int(n)).view(int(n), *t.shape[1:])
+    return t.to(ops.act_dtype()).expand(int(n), *t.shape[1:])
+
+
 class _MlpGelu(torch.autograd.Function):
     """y = fc2(gelu(fc1(x))) (+ residual), four GEMM-shaped launches forward + backward each carrying the
     element-wise work in its epilogue: fc1 + bias + GELU (pre-activation kept), fc2 + bias + residual; backward:
