@@ -522,10 +522,12 @@ int wm_layernorm_bwd_parts(const void* x, const void* dy, const float* gamma, co
                            long long rows, int C, const void* dres, void* dx, float* part, void* stream);
 
 /* y = act(x + bias) (+ residual).  act: 0 identity, 1 exact GELU (erf), 2 ReLU (the bias-carrying heads:
- * lightly MoCoProjectionHead).  bias / residual may be NULL. */
+ * lightly MoCoProjectionHead), 3 Mish x tanh(softplus(x)), softplus(x) = x above 20 as in torch (nn.Mish of the
+ * reference's TwoLayerMultilabelClassifier, src/ssl_wafermap/models/evals.py:155-165).  bias / residual may be NULL. */
 #define WM_ACT_NONE 0
 #define WM_ACT_GELU 1
 #define WM_ACT_RELU 2
+#define WM_ACT_MISH 3
 int wm_bias_act_fwd(const void* x, const float* bias, const void* residual, int act, long long rows, int C,
                     void* y, void* stream);
 /* dx = dy * act'(x + bias) (dx may be NULL for act 0: only the bias gradient is wanted);
@@ -698,6 +700,26 @@ int wm_f32_loss_bwd(const float* pred, const float* target, long long n, int mod
                     float* dpred, void* stream);
 /* center = center * momentum + (1 - momentum) * column mean of teacher [rows][D]. */
 int wm_f32_center_update(float* center, const float* teacher, int rows, int D, float momentum, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Downstream evaluation (scripts/MixedWM38_evals.py, src/ssl_wafermap/models/evals.py:80-165).
+ *
+ * Per-label AUROC of multi-label scores: torchmetrics MultilabelAUROC(num_labels, average=None, thresholds=None), the
+ * metric of the reference's probes (evals.py:88-96, MixedWM38_evals.py:103-111).  scores [rows][L] (WM_F32 / WM_BF16,
+ * row-major), targets [rows][L] int8 (non-zero = positive).  When any score lies outside [0, 1] every score is replaced
+ * by its float32 sigmoid first (torchmetrics' rule).  auc[l] = U / (P Q), U = #{(pos, neg): s_pos > s_neg} + #ties / 2,
+ * counted exactly in 64-bit integers (same bits on every call); a label without positives or without negatives gets 0.
+ * pos_count [L] (may be NULL) receives P per label.  rows * L < 2^31, L <= 1024.
+ * Workspace: wm_multilabel_auroc_workspace_bytes(rows, L). */
+size_t wm_multilabel_auroc_workspace_bytes(int rows, int L);
+int wm_multilabel_auroc(const void* scores, int dtype, const int8_t* targets, int rows, int L, double* auc, int* pos_count,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Inverted dropout (torch.nn.Dropout(p) in training mode, evals.py:162): element i is kept when
+ * rand01(seed, i) >= p (the counter RNG of the augmentation kernel's DieNoise) and scaled by 1 / (1 - p); p = 1 gives
+ * zeros.  x, y [n] WM_F32 / WM_BF16 (y may equal x), n <= 2^32, 0 <= p <= 1.  The backward pass regenerates the mask
+ * from (seed, i): dx = dy * mask / (1 - p), no mask is stored. */
+int wm_dropout_fwd(const void* x, int dtype, long long n, float p, uint32_t seed, void* y, void* stream);
+int wm_dropout_bwd(const void* dy, int dtype, long long n, float p, uint32_t seed, void* dx, void* stream);
 
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it

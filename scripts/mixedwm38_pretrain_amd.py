@@ -15,7 +15,9 @@ What the reference does, and where it is here:
   :566-649  for each model: seed, loader, model(), Trainer.fit (no validation), run record, results.csv -> main()
 Model classes are this repo's (same names / hyper-parameters as the script's: DINOViT with batch_norm=False heads
 :146-151, MAE on torchvision's ViT-B/32 geometry :261-281, ...).  `--mae-backbone vit_small_16` selects BASELINE.json
-configs[3] (MAE ViT-S/16) instead of the reference's ViT-B/32.  Not carried over: TensorBoard logger, ModelCheckpoint.
+configs[3] (MAE ViT-S/16) instead of the reference's ViT-B/32.  Not carried over: TensorBoard logger.  ModelCheckpoint
+is opt-in: `--save-checkpoints` writes <out>/<Model>/checkpoints/last.ckpt after fit, in Lightning's layout
+(utils/checkpoint.py), which scripts/mixedwm38_evals_amd.py reads.
 
 Data: `--data-root` = the reference's `data/` directory.  Without it the subset mode runs from the data-only fixture
 tests/golden/mixedwm38_train_1_split.npz (381 maps; the reference's own subset file is train_5_split).
@@ -64,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--limit-train-batches", type=int, default=None)
     ap.add_argument("--mae-backbone", default="vit_b_32", choices=["vit_b_32", "vit_small_16"])
     ap.add_argument("--log-every", type=int, default=50)
+    ap.add_argument("--save-checkpoints", action="store_true",
+                    help="write <out>/<Model>/checkpoints/last.ckpt (Lightning layout) after fit")
     args = ap.parse_args(argv)
 
     import pandas as pd
@@ -138,6 +142,10 @@ def main(argv=None):
                 print(run, flush=True)
                 pd.DataFrame(runs).to_csv(log_dir / "results.csv", index=False)
                 pd.DataFrame(trainer.loss_log, columns=["step", "loss", "rep_std"]).to_csv(log_dir / "loss_log.csv", index=False)
+                if args.save_checkpoints:
+                    from ssl_wafermap_amd.utils.checkpoint import save_checkpoint
+
+                    save_checkpoint(model, log_dir / "checkpoints" / "last.ckpt", trainer.current_epoch, trainer.global_step)
             del model, trainer
             torch.cuda.empty_cache()
         results[model_name] = runs

@@ -270,6 +270,12 @@ SIGNATURES = {
     "wm_linear_bias_gelu_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wm_linear_dgrad_gelu": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "wm_wgrad_fold": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    # ---- downstream evaluation
+    "wm_multilabel_auroc_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_multilabel_auroc": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "wm_dropout_fwd": (c_int, [c_void_p, c_int, c_longlong, c_float, c_uint32, c_void_p, c_void_p]),
+    "wm_dropout_bwd": (c_int, [c_void_p, c_int, c_longlong, c_float, c_uint32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -30,20 +30,6 @@ constexpr int AUG_ROW_BLOCKS = 4;
 constexpr int AUG_MAX_SIDE = 256;  // largest wafer side / img_size / out_size supported
 constexpr int AUG_LDS_ELEMS = 8192; // elements per LDS image (wafers up to ~90 x 90 run from LDS)
 
-// Counter RNG shared with the oracle (oracle/augment.py: rand01): lowbias32 finaliser.
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float rand01(uint32_t seed, uint32_t idx) {
-  const uint32_t x = lowbias32(idx ^ lowbias32(seed ^ 0x9E3779B9U));
-  return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
-
 __device__ __forceinline__ uint8_t die_only(uint8_t v) { return (v == 128 || v == 255) ? v : 0; }
 
 // PIL nearest-resize source index for every destination index (sequential double accumulation).

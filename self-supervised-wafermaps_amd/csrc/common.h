@@ -199,6 +199,22 @@ __device__ __forceinline__ float wm_gelu_grad(float v) {
 }
 
 
+// Counter RNG shared with the oracle (oracle/augment.py: rand01): lowbias32 finaliser.  DieNoise (augment.hip) and
+// dropout (evalops.hip) draw from it.
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352dU;
+  x ^= x >> 15;
+  x *= 0x846ca68bU;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ float rand01(uint32_t seed, uint32_t idx) {
+  const uint32_t x = lowbias32(idx ^ lowbias32(seed ^ 0x9E3779B9U));
+  return (float)(x >> 8) * (1.0f / 16777216.0f);
+}
+
+
 // ---- bit-reproducible reductions across workgroups: NO floating-point atomics anywhere on the training path.
 // f32 atomics add in arrival order, so two runs of one launch differ in the last bits and bf16 roundings downstream
 // flip (round 2: 4-10 % run-to-run gradient noise from the BatchNorm statistics and the split-K weight gradients).

@@ -261,6 +261,16 @@ __global__ __launch_bounds__(TF_THREADS) void ln_bwd(const uint16_t* __restrict_
 __device__ __forceinline__ float gelu_f(float v) { return wm_gelu(v); }
 __device__ __forceinline__ float gelu_grad(float v) { return wm_gelu_grad(v); }
 
+// Mish x tanh(softplus(x)) with torch's softplus threshold (softplus(x) = x for x > 20), and its derivative
+// tanh(sp) + x sigmoid(x) (1 - tanh(sp)^2) (torch.nn.Mish, the reference's TwoLayerMultilabelClassifier).
+__device__ __forceinline__ float mish_sp(float v) { return v > 20.f ? v : log1pf(expf(v)); }
+__device__ __forceinline__ float mish_f(float v) { return v * tanhf(mish_sp(v)); }
+__device__ __forceinline__ float mish_grad(float v) {
+  const float t = tanhf(mish_sp(v));
+  const float sg = 1.f / (1.f + expf(-v));
+  return fmaf(v * sg, 1.f - t * t, t);
+}
+
 template <int ACT>
 __global__ __launch_bounds__(TF_THREADS) void bias_act_fwd(const uint16_t* __restrict__ x, const float* __restrict__ bias,
                                                            const uint16_t* __restrict__ res, long long rows, int C,
@@ -283,6 +293,9 @@ __global__ __launch_bounds__(TF_THREADS) void bias_act_fwd(const uint16_t* __res
     } else if (ACT == WM_ACT_RELU) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+    } else if (ACT == WM_ACT_MISH) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = mish_f(f[e]);
     }
     if (res != nullptr) {
       float r[8];
@@ -298,6 +311,14 @@ __global__ __launch_bounds__(TF_THREADS) void bias_act_fwd(const uint16_t* __res
 // walks rows, so the per-channel sums stay in registers until the end of the block.
 // MODE 0: colsum of src only.  MODE 1: dx = dy (identity act) is not written, colsum of dy.
 // MODE 2: GELU: dx = dy * gelu'(x + bias), colsum of dx.  MODE 3: ReLU: dx = dy * (x + bias > 0).
+// MODE 4: Mish: dx = dy * mish'(x + bias).
+template <int MODE>
+__device__ __forceinline__ float colsum_act_grad(float v) {
+  if constexpr (MODE == 2) return gelu_grad(v);
+  else if constexpr (MODE == 3) return v > 0.f ? 1.f : 0.f;
+  else return mish_grad(v);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(TF_THREADS) void colsum_kernel(const uint16_t* __restrict__ x, const float* __restrict__ bias,
                                                             const uint16_t* __restrict__ dy, long long rows, int C,
@@ -337,7 +358,7 @@ __global__ __launch_bounds__(TF_THREADS) void colsum_kernel(const uint16_t* __re
           float fx[8];
           unpack8(vx[u], fx);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) fd[e] *= MODE == 2 ? gelu_grad(fx[e] + b[e]) : (fx[e] + b[e] > 0.f ? 1.f : 0.f);
+          for (int e = 0; e < 8; ++e) fd[e] *= colsum_act_grad<MODE>(fx[e] + b[e]);
           const uint4 pk = pack8(fd);
           *reinterpret_cast<uint4*>(dx + (size_t)(r + u * RL) * C + ch * 8) = pk;
           unpack8(pk, fd);  // the sums see the rounded gradient, like a separate reduction would
@@ -354,7 +375,7 @@ __global__ __launch_bounds__(TF_THREADS) void colsum_kernel(const uint16_t* __re
         float fx[8];
         unpack8(*reinterpret_cast<const uint4*>(x + off), fx);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) fd[e] *= MODE == 2 ? gelu_grad(fx[e] + b[e]) : (fx[e] + b[e] > 0.f ? 1.f : 0.f);
+        for (int e = 0; e < 8; ++e) fd[e] *= colsum_act_grad<MODE>(fx[e] + b[e]);
         const uint4 pk = pack8(fd);
         *reinterpret_cast<uint4*>(dx + off) = pk;
         unpack8(pk, fd);
@@ -949,7 +970,7 @@ extern "C" int wm_bias_act_fwd(const void* x, const float* bias, const void* res
                                void* y, void* stream) {
   WM_REQUIRE(x && y, WM_EINVAL);
   WM_REQUIRE(rows > 0 && C > 0 && C % 8 == 0, WM_EINVAL);
-  WM_REQUIRE(act == WM_ACT_NONE || act == WM_ACT_GELU || act == WM_ACT_RELU, WM_EUNSUPPORTED);
+  WM_REQUIRE(act == WM_ACT_NONE || act == WM_ACT_GELU || act == WM_ACT_RELU || act == WM_ACT_MISH, WM_EUNSUPPORTED);
   WM_REQUIRE(al16(x) && al16(y) && al16(bias) && al16(residual), WM_EALIGN);
   const int blocks = ew_blocks(rows * (C >> 3));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -959,6 +980,10 @@ extern "C" int wm_bias_act_fwd(const void* x, const float* bias, const void* res
                                                              static_cast<uint16_t*>(y));
   else if (act == WM_ACT_GELU)
     bias_act_fwd<WM_ACT_GELU><<<blocks, TF_THREADS, 0, st>>>(static_cast<const uint16_t*>(x), bias,
+                                                             static_cast<const uint16_t*>(residual), rows, C,
+                                                             static_cast<uint16_t*>(y));
+  else if (act == WM_ACT_MISH)
+    bias_act_fwd<WM_ACT_MISH><<<blocks, TF_THREADS, 0, st>>>(static_cast<const uint16_t*>(x), bias,
                                                              static_cast<const uint16_t*>(residual), rows, C,
                                                              static_cast<uint16_t*>(y));
   else
@@ -979,8 +1004,9 @@ extern "C" int wm_bias_act_bwd(const void* x, const float* bias, const void* dy,
     if (dbias == nullptr) return WM_OK;
     return launch_colsum<1>(nullptr, nullptr, dy, rows, C, nullptr, dbias, st);
   }
-  WM_REQUIRE(act == WM_ACT_GELU || act == WM_ACT_RELU, WM_EUNSUPPORTED);
+  WM_REQUIRE(act == WM_ACT_GELU || act == WM_ACT_RELU || act == WM_ACT_MISH, WM_EUNSUPPORTED);
   WM_REQUIRE(x && dx, WM_EINVAL);
+  if (act == WM_ACT_MISH) return launch_colsum<4>(x, bias, dy, rows, C, dx, dbias, st);
   return act == WM_ACT_GELU ? launch_colsum<2>(x, bias, dy, rows, C, dx, dbias, st)
                             : launch_colsum<3>(x, bias, dy, rows, C, dx, dbias, st);
 }
@@ -1002,8 +1028,9 @@ extern "C" int wm_bias_act_bwd_parts(const void* x, const float* bias, const voi
   WM_REQUIRE(al16(x) && al16(dy) && al16(dx) && al16(bias), WM_EALIGN);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (act == WM_ACT_NONE) return launch_colsum<1>(nullptr, nullptr, dy, rows, C, nullptr, nullptr, st, part);
-  WM_REQUIRE(act == WM_ACT_GELU || act == WM_ACT_RELU, WM_EUNSUPPORTED);
+  WM_REQUIRE(act == WM_ACT_GELU || act == WM_ACT_RELU || act == WM_ACT_MISH, WM_EUNSUPPORTED);
   WM_REQUIRE(x && dx, WM_EINVAL);
+  if (act == WM_ACT_MISH) return launch_colsum<4>(x, bias, dy, rows, C, dx, nullptr, st, part);
   return act == WM_ACT_GELU ? launch_colsum<2>(x, bias, dy, rows, C, dx, nullptr, st, part)
                             : launch_colsum<3>(x, bias, dy, rows, C, dx, nullptr, st, part);
 }

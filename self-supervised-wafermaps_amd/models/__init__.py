@@ -7,6 +7,8 @@ from .mae import MAE, MAEBackbone, MAEDecoder, SimMIM, masked_autoencoder, vit_b
 from .moco import MoCo  # noqa: F401
 from .siamese import BYOL, FastSiam, SimSiam  # noqa: F401
 from .evals import LinearClassifier, MultilabelLinearClassifier, SupervisedR18, fit_linear_probe  # noqa: F401
+from .evals import (EarlyStopping, MultilabelSupervisedR18, TwoLayerMultilabelClassifier, evaluate_multilabel,  # noqa: F401
+                    fit_probe, multilabel_auroc, multilabel_metrics, pos_weight_from_labels, predict_logits)
 from .dclw import DCLW  # noqa: F401
 from .barlow import BarlowTwins  # noqa: F401
 from .vicreg import VICReg  # noqa: F401

@@ -8,7 +8,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops, vit_ops
+from . import evalops, ops, vit_ops
+from . import precision as _precision
 
 
 class Conv2d(nn.Module):
@@ -257,6 +258,38 @@ class GELU(nn.Module):
 
     def forward(self, x):
         return vit_ops.bias_act(x, None, vit_ops.ACT_GELU)
+
+
+class Mish(nn.Module):
+    """torch.nn.Mish: x tanh(softplus(x)) on bf16 [rows, C] (C % 8 == 0), the bias-act epilogue kernel with
+    WM_ACT_MISH.  Not built under the float32 preset: raises there."""
+
+    def forward(self, x):
+        if _precision.is_f32():
+            raise NotImplementedError("Mish is not built under the float32 preset (bf16 path only)")
+        return vit_ops.bias_act(x, None, vit_ops.ACT_MISH)
+
+
+class Dropout(nn.Module):
+    """torch.nn.Dropout(p): the identity in eval mode and for p = 0; in training mode the counter-RNG kernel
+    (csrc/evalops.hip) with a 32-bit seed drawn from torch's default CPU generator once per forward pass, so
+    torch.manual_seed makes a run repeatable (the mask stream is not torch's)."""
+
+    def __init__(self, p: float = 0.5):
+        super().__init__()
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+        self.p = float(p)
+        self.last_seed = None
+
+    def extra_repr(self) -> str:
+        return f"p={self.p}"
+
+    def forward(self, x):
+        if not self.training or self.p == 0.0:
+            return x
+        self.last_seed = int(torch.randint(0, 2 ** 32, (1,), dtype=torch.int64))
+        return evalops.dropout(x, self.p, self.last_seed)
 
 
 class ReLU(nn.Module):

@@ -18,7 +18,7 @@ from . import precision as _precision
 from ._lib import check, ptr, stream_ptr
 from .ops import _arena_grad, _need_cuda
 
-ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
+ACT_NONE, ACT_GELU, ACT_RELU, ACT_MISH = 0, 1, 2, 3
 
 
 def _bf16_rows(x: torch.Tensor) -> torch.Tensor:
@@ -234,8 +234,14 @@ class _BiasAct(torch.autograd.Function):
 def bias_act(x: torch.Tensor, bias: Optional[torch.Tensor], act: int = ACT_NONE,
              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     if _precision.is_f32():
+        _f32_act_built(act)
         return f32path.bias_act(x, bias, int(act), residual)
     return _BiasAct.apply(x, bias, residual, int(act))
+
+
+def _f32_act_built(act: int) -> None:
+    if int(act) == ACT_MISH:
+        raise NotImplementedError("Mish is not built under the float32 preset (bf16 path only)")
 
 
 class _LinearBias(torch.autograd.Function):
@@ -291,6 +297,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(x @ W^T + bias) (+ residual) on bf16 [rows, C]: the GEMM kernel, then one epilogue pass."""
     if _precision.is_f32():
+        _f32_act_built(act)
         return f32path.linear(x, weight, bias, int(act), residual)
     if act == ACT_NONE and (bias is not None or residual is not None):
         return _LinearBias.apply(x, weight, bias, residual)
