@@ -721,6 +721,31 @@ int wm_multilabel_auroc(const void* scores, int dtype, const int8_t* targets, in
 int wm_dropout_fwd(const void* x, int dtype, long long n, float p, uint32_t seed, void* y, void* stream);
 int wm_dropout_bwd(const void* dy, int dtype, long long n, float p, uint32_t seed, void* dx, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Model inspection (notebooks/2.0-Figures-DINO-attention.ipynb, notebooks/2.0-Figures-GradCAM.ipynb).  No atomics:
+ * two calls give the same bits.
+ *
+ * Attention probabilities softmax(scale q k^T) per head: dino's VisionTransformer.get_last_selfattention, which the
+ * attention notebook calls on the last block (with visualize_attention.py's maps of the class-token row).  qkv
+ * [B][S][3][H][head_dim] (WM_BF16 or WM_F32, 16-byte aligned), head_dim 64 or 32, S <= 256.  probs float32
+ * [B][H][R][S] (16-byte aligned), R = S, or R = 1 when cls_only (the class-token row only; equal to row 0 of the full
+ * output bit for bit).  bf16 scores come from the same MFMA products as wm_attention_fwd's. */
+int wm_attention_probs(const void* qkv, int dtype, int B, int S, int H, int head_dim, float scale, int cls_only,
+                       float* probs, void* stream);
+/* visualize_attention.py --threshold: per row of attn [rows][ld] (float32), over entries 0..n-1: keep[row][i] = 1 when
+ * sum_{j: a_j < a_i or (a_j = a_i and j <= i)} a_j / sum_j a_j > 1 - threshold (the stable ascending sort + cumsum of
+ * the reference, summed in double), else 0.  keep uint8 [rows][n].  n <= 256, ld >= n, 0 <= threshold <= 1. */
+int wm_attention_mass_mask(const float* attn, long long rows, int n, long long ld, double threshold, uint8_t* keep,
+                           void* stream);
+/* pytorch_grad_cam EigenCAM (get_2d_projection + BaseCAM + scale_cam_image) of backbone.layer4[-1] activations, as the
+ * GradCAM notebook runs it.  act [N][H][W][C] memory (channels_last [N,C,H,W]; WM_BF16 or WM_F32), H * W <= 64.  Per
+ * image: NaN -> 0; A = activations [HW][C] minus the per-channel mean; p = A v1 = sqrt(lambda1) u1 from the leading
+ * eigenpair of A A^T (cyclic Jacobi in double); the sign of p chosen so that sum_i p_i r_i >= 0, r_i = the channel
+ * sum of the uncentred activations at position i; ReLU; x -= min, x /= 1e-7 + max; bilinear resize to out_h x out_w
+ * (half-pixel centres, edges clamped: F.interpolate(mode="bilinear", align_corners=False)); min-max again.  An image
+ * with lambda1 = 0 gives zeros.  cam float32 [N][out_h][out_w], out_h, out_w <= 4096. */
+int wm_eigencam(const void* act, int dtype, int N, int C, int H, int W, int out_h, int out_w, float* cam, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -276,6 +276,10 @@ SIGNATURES = {
                                     c_void_p]),
     "wm_dropout_fwd": (c_int, [c_void_p, c_int, c_longlong, c_float, c_uint32, c_void_p, c_void_p]),
     "wm_dropout_bwd": (c_int, [c_void_p, c_int, c_longlong, c_float, c_uint32, c_void_p, c_void_p]),
+    # ---- model inspection
+    "wm_attention_probs": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "wm_attention_mass_mask": (c_int, [c_void_p, c_longlong, c_int, c_longlong, c_double, c_void_p, c_void_p]),
+    "wm_eigencam": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -26,6 +26,7 @@
 // Roofline: MFMA-issue/LDS bound, but ~8 % of a ViT-S block's FLOPs (4 S^2 64 per head vs the
 // 24 S 384^2 of its four Linear layers at S = 197): correctness first, tuning later.
 #include "common.h"
+#include "attn_frag.h"
 #include <stdlib.h>
 
 namespace {
@@ -34,15 +35,6 @@ namespace {
 // backward: 4 waves (it needs > 128 registers per lane; measured 1.4x slower with 8)
 constexpr int AT_FWD_THREADS = 512;
 constexpr int AT_BWD_THREADS = 256;
-// LDS bytes per token row: HD bf16 + 16 B pad (144 for head dim 64, 80 for 32: in both, 16
-// consecutive rows start on 16 distinct 4-bank groups)
-#define AT_ROWB (HD * 2 + 16)
-
-template <int HD>
-__device__ __forceinline__ bf16x8_t frag_rows(const uint8_t* base, int row, int ks, int fg) {
-  return *reinterpret_cast<const bf16x8_t*>(base + row * AT_ROWB + ks * 64 + fg * 16);
-}
-
 // Operand with k running along the ROWS of the LDS image: 32 rows from row0, the 16 columns of
 // block blk.  k-slot (fg, e) <-> row0 + 4 fg + e (e < 4) / row0 + 16 + 4 fg + (e - 4).
 template <int HD>
@@ -60,27 +52,6 @@ __device__ __forceinline__ bf16x8_t pack_slots(const f32x4_t a, const f32x4_t b)
   const s16x8_t v = {(short)f2bf(a[0]), (short)f2bf(a[1]), (short)f2bf(a[2]), (short)f2bf(a[3]),
                      (short)f2bf(b[0]), (short)f2bf(b[1]), (short)f2bf(b[2]), (short)f2bf(b[3])};
   return __builtin_bit_cast(bf16x8_t, v);
-}
-
-// One fragment (row, 32-wide k-slab ks, 16-byte piece fg) of a [token][HD] operand straight from global memory:
-// what frag_rows reads from an LDS image.  Rows >= S read as zeros.  The forward kernel takes a strip's own query rows
-// this way (only that wave uses them): the request is in flight under the K / V staging, and Q needs no LDS.
-__device__ __forceinline__ bf16x8_t frag_global(const uint16_t* base, size_t row_stride, int row, int S, int ks, int fg) {
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (row < S) v = *reinterpret_cast<const uint4*>(base + (size_t)row * row_stride + ks * 32 + fg * 8);
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
-// rows [0, S) of one [token][64] operand of (image b, head h) -> LDS; rows [S, SP) zero
-template <int HD>
-__device__ __forceinline__ void stage_rows(const uint16_t* src, size_t row_stride, int S, int SP, uint8_t* dst) {
-  constexpr int CPR = HD / 8;  // 16-byte chunks per row
-  for (int i = threadIdx.x; i < SP * CPR; i += blockDim.x) {
-    const int r = i / CPR, c = i % CPR;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < S) v = *reinterpret_cast<const uint4*>(src + (size_t)r * row_stride + c * 8);
-    *reinterpret_cast<uint4*>(dst + r * AT_ROWB + c * 16) = v;
-  }
 }
 
 template <int NT, int HD>

@@ -206,6 +206,40 @@ class VisionTransformer(nn.Module):
         cls = vit_ops.gather_rows(tok, idx, n, seq)
         return self.norm(cls)
 
+    # ---- inspection (dino's get_last_selfattention / get_intermediate_layers) -------------------
+    def last_qkv(self, x):
+        """images -> (qkv [N * S, 3 * D] of the last block: blocks[:-1], then its norm1 + qkv Linear as its forward runs
+        them, N, S)."""
+        tok, n, seq = self.prepare_tokens(x)
+        for blk in self.blocks[:-1]:
+            tok = blk(tok, n, seq)
+        last = self.blocks[-1]
+        qkv = vit_ops.ln_linear(tok, last.norm1.weight, last.norm1.bias, last.norm1.eps, last.attn.qkv.weight,
+                                last.attn.qkv.bias)
+        if qkv is None:
+            qkv = last.attn.qkv(last.norm1(tok))
+        return qkv, n, seq
+
+    def get_last_selfattention(self, x):
+        """images [N, 3, S, S] -> float32 [N, H, T, T] (T tokens): the softmax(q k^T scale) of the last block, as dino's.
+        Inference only: runs without gradients."""
+        from ..interpret import attention_probs
+
+        attn = self.blocks[-1].attn
+        with torch.no_grad():
+            qkv, n, seq = self.last_qkv(x)
+            return attention_probs(qkv, n, seq, attn.num_heads, attn.scale)
+
+    def get_intermediate_layers(self, x, n: int = 1):
+        """images -> list of norm(tokens) [N, T, D] after each of the last n blocks, as dino's."""
+        tok, b, seq = self.prepare_tokens(x)
+        out = []
+        for i, blk in enumerate(self.blocks):
+            tok = blk(tok, b, seq)
+            if len(self.blocks) - i <= n:
+                out.append(self.norm(tok).reshape(b, seq, -1))
+        return out
+
 
 def vit_small(patch_size: int = 16, **kw) -> VisionTransformer:
     """dino_vits16: dim 384, depth 12, 6 heads, MLP x4, qkv bias, LayerNorm eps 1e-6."""
