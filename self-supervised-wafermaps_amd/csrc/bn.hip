@@ -660,15 +660,22 @@ __global__ __launch_bounds__(BN_THREADS) void stats_prereduce(const float* __res
   out[i] = v;
 }
 
+// Slots per group the finalize kernels read directly, and what the pre-reduction of more than that leaves per group.
+constexpr int STAT_SLOTS_DIRECT = 512, STAT_SLOTS_REDUCED = 128;
+inline size_t stat_scratch_floats(int T, int G, int C) {
+  return T > STAT_SLOTS_DIRECT ? (size_t)G * STAT_SLOTS_REDUCED * 2 * C : 0;
+}
+
 // Statistics slots of a convolution epilogue -> the partial-sum array the finalize kernels read: the slots themselves
-// (<= 512 per group), else their pre-reduction into <= 128 per group inside `scratch` (G * 128 * 2 * C floats).
+// (up to STAT_SLOTS_DIRECT per group), else their pre-reduction into at most STAT_SLOTS_REDUCED per group inside
+// `scratch` (stat_scratch_floats).
 inline const float* stat_partials(const float* stat_part, int T, int G, int C, float* scratch, int* nblk, hipStream_t st) {
-  if (T <= 512) {
+  if (T <= STAT_SLOTS_DIRECT) {
     *nblk = T;
     return stat_part;
   }
   int R = 1;
-  while ((T + R - 1) / R > 128) R *= 2;
+  while ((T + R - 1) / R > STAT_SLOTS_REDUCED) R *= 2;
   const int To = (T + R - 1) / R;
   const long long total = (long long)G * To * 2 * C;
   stats_prereduce<<<wm_cdiv(total, BN_THREADS), BN_THREADS, 0, st>>>(stat_part, T, R, To, G * 2 * C, 2 * C, scratch);
@@ -715,17 +722,31 @@ inline int stream_grid(long long items) {
   return (int)b;
 }
 
-inline void launch_bn_apply(const void* y, const void* residual, const float* scale, const float* shift, long long rows,
-                            int C, int rpg, int relu, void* out, hipStream_t st, void* relu_mask = nullptr) {
+// The void* activations of the C ABI are bf16 bit patterns: each impl converts them once, the launch helpers take these.
+inline const uint16_t* bf16(const void* p) { return static_cast<const uint16_t*>(p); }
+inline uint16_t* bf16(void* p) { return static_cast<uint16_t*>(p); }
+
+inline void launch_bn_apply(const uint16_t* y, const uint16_t* residual, const float* scale, const float* shift,
+                            long long rows, int C, int rpg, int relu, uint16_t* out, hipStream_t st,
+                            uint8_t* relu_mask = nullptr) {
   int csh = 0;
-  if (chunk_pow2(C, &csh))
-    bn_apply<true><<<stream_grid(rows * (C >> 3)), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(residual), scale, shift, rows, C, rpg, relu, csh,
-        static_cast<uint16_t*>(out), static_cast<uint8_t*>(relu_mask));
-  else
-    bn_apply<false><<<stream_grid(rows * (C >> 3)), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(residual), scale, shift, rows, C, rpg, relu, csh,
-        static_cast<uint16_t*>(out), static_cast<uint8_t*>(relu_mask));
+  const auto kernel = chunk_pow2(C, &csh) ? bn_apply<true> : bn_apply<false>;
+  kernel<<<stream_grid(rows * (C >> 3)), BN_THREADS, 0, st>>>(y, residual, scale, shift, rows, C, rpg, relu, csh, out,
+                                                              relu_mask);
+}
+
+// The POW2 x FORM dispatch of the backward apply pass.  FORM 0: (y, dout) only; 1: ReLU mask (from out_relu or recomputed)
+// and / or a dz copy; 2: dout gathered from the pooled gradient `ps`.
+inline void launch_bn_bwd_apply(int form, const uint16_t* y, const uint16_t* dout, const uint16_t* out_relu,
+                                const float* coef, long long rows, int C, int rpg, bool remask, uint16_t* dy, uint16_t* dz,
+                                const PoolSrc& ps, hipStream_t st) {
+  int csh = 0;
+  const bool pow2 = chunk_pow2(C, &csh);
+  const auto kernel = form == 0   ? (pow2 ? bn_bwd_apply<true, 0> : bn_bwd_apply<false, 0>)
+                      : form == 1 ? (pow2 ? bn_bwd_apply<true, 1> : bn_bwd_apply<false, 1>)
+                                  : (pow2 ? bn_bwd_apply<true, 2> : bn_bwd_apply<false, 2>);
+  kernel<<<stream_grid(rows * (C >> 3)), BN_THREADS, 0, st>>>(y, dout, out_relu, coef, rows, C, rpg, remask ? 1 : 0, csh, dy,
+                                                              dz, ps);
 }
 
 // ---- wide, short matrices (projection heads: C > 2048, a few hundred rows): one thread per channel walks
@@ -870,6 +891,162 @@ int bn_shape_check(long long rows, int C, int G) {
   return WM_OK;
 }
 
+// ---- host-side steps.  Every entry point below is a composition of: partial sums (launch_reduce, or the producing
+// convolution's slots through stat_partials) -> finalize (launch_finalize) -> apply (launch_bn_apply /
+// launch_bn_bwd_apply).  Each kernel has its launch geometry in exactly one of these helpers.
+
+// `nblk` blocks per group, each over ceil(rpg / nblk) of the group's `rpg` rows.
+template <int MODE>
+inline void launch_reduce(const uint16_t* y, const uint16_t* dout, const uint16_t* out, const float* mean,
+                          const float* invstd, const float* gamma_m, const float* beta_m, int rpg, int C, int G, int nblk,
+                          float* part, const PoolSrc& ps, hipStream_t st) {
+  const int tpr = C >> 3, rpp = BN_THREADS / tpr;
+  const size_t lds = (size_t)2 * rpp * C * sizeof(float);
+  bn_reduce<MODE><<<dim3(nblk, G), BN_THREADS, lds, st>>>(y, dout, out, mean, invstd, gamma_m, beta_m, rpg, C,
+                                                          wm_cdiv(rpg, nblk), part, ps);
+}
+
+// The forward's partial sums [G][*nblk][2][C]: the slots of the producing convolution when it accumulated them (stat_part
+// non-NULL; `scratch` then holds stat_scratch_floats), else reduced from y into `scratch` (G * reduce_blocks * 2 * C).
+inline const float* fwd_partials(const uint16_t* y, const float* stat_part, int stat_tiles, int rpg, int C, int G,
+                                 float* scratch, int* nblk, hipStream_t st) {
+  if (stat_part) return stat_partials(stat_part, stat_tiles, G, C, scratch, nblk, st);
+  *nblk = reduce_blocks(rpg, C);
+  launch_reduce<0>(y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpg, C, G, *nblk, scratch, PoolSrc{}, st);
+  return scratch;
+}
+
+// Smallest workspace when all of it is the `scratch` of fwd_partials (wm_bn_train_stats, wm_bn_sync_fwd_sums).
+inline size_t fwd_partials_bytes(const float* stat_part, int stat_tiles, long long rows, int C, int G) {
+  return stat_part ? stat_scratch_floats(stat_tiles, G, C) * sizeof(float) : wm_bn_workspace_bytes(rows, C, G);
+}
+
+// The finalize kernels (bn_fwd_finalize, bn_bwd_finalize, bn_sums_finalize) share one geometry: 32 channels per block of
+// 1024 threads.  `args` are the kernel's own, after the partial sums [G][nblk][2][C] it starts with.
+template <typename Kernel, typename... Args>
+inline void launch_finalize(Kernel kernel, int C, hipStream_t st, const float* part, Args... args) {
+  kernel<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(part), args...);
+}
+
+inline void launch_eval_params(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                               float eps, int C, float* scale, float* shift, hipStream_t st) {
+  bn_eval_params<<<1, C < 1024 ? ((C + 63) / 64) * 64 : 1024, 0, st>>>(gamma, beta, running_mean, running_var, eps, C, scale,
+                                                                       shift);
+}
+
+// The ReLU mask of the backward is recomputed from y when the caller kept no output tensor to read it from.
+inline bool relu_remask(int relu_from_y, const void* out_relu) { return relu_from_y && !out_relu; }
+
+// The statistics half of the training forward: partials -> finalize (save_mean / save_invstd, running statistics, scale and
+// shift [G][C]).  `scratch` as fwd_partials.
+int bn_fwd_stats(const uint16_t* y, const float* stat_part, int stat_tiles, const float* gamma, const float* beta,
+                 float* running_mean, float* running_var, long long* num_batches_tracked, int rpg, int C, int G, float eps,
+                 float momentum, float* save_mean, float* save_invstd, float* scale, float* shift, float* scratch,
+                 hipStream_t st) {
+  int nblk = 0;
+  const float* part = fwd_partials(y, stat_part, stat_tiles, rpg, C, G, scratch, &nblk, st);
+  WM_LAUNCH_CHECK();
+  launch_finalize(bn_fwd_finalize, C, st, part, nblk, G, C, rpg, 0, gamma, beta, eps, momentum, running_mean, running_var,
+                  num_batches_tracked, save_mean, save_invstd, scale, shift);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+// Training forward.  stat_part non-NULL: the producing convolution already accumulated the statistics
+// (wm_conv2d_fwd_stats) in stat_part [G][stat_tiles][2][C].  Workspace: scale, shift [G][C], then the partial sums.
+int bn_train_fwd_impl(const void* y_, const void* residual, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, long long* num_batches_tracked, long long rows, int C, int G, float eps,
+                      float momentum, int relu, float* save_mean, float* save_invstd, void* out_, void* relu_mask,
+                      const float* stat_part, int stat_tiles, void* workspace, size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(y_ && out_ && save_mean && save_invstd && workspace, WM_EINVAL);
+  const int rc = bn_shape_check(rows, C, G);
+  if (rc != WM_OK) return rc;
+  const size_t need = stat_part ? ((size_t)2 * G * C + stat_scratch_floats(stat_tiles, G, C)) * sizeof(float)
+                                : wm_bn_workspace_bytes(rows, C, G);   // (its coefficient planes hold scale and shift)
+  WM_REQUIRE(workspace_bytes >= need, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint16_t *y = bf16(y_), *res = bf16(residual);
+  uint16_t* out = bf16(out_);
+  const int rpg = (int)(rows / G);
+  if (!stat_part && bn_wide(rows, C, G)) {   // (with slots, finalize + apply serve any width)
+    WM_REQUIRE(relu_mask == nullptr, WM_EUNSUPPORTED);
+    bn_col_fwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(y, res, gamma, beta, running_mean, running_var,
+                                                              num_batches_tracked, rpg, C, G, eps, momentum, relu, 1,
+                                                              save_mean, save_invstd, out);
+    WM_LAUNCH_CHECK();
+    return WM_OK;
+  }
+  float* scale = static_cast<float*>(workspace);  // (the backward's coefficient planes, reused)
+  float* shift = scale + (size_t)G * C;
+  const int rs = bn_fwd_stats(y, stat_part, stat_tiles, gamma, beta, running_mean, running_var, num_batches_tracked, rpg, C, G,
+                              eps, momentum, save_mean, save_invstd, scale, shift, shift + (size_t)G * C, st);
+  if (rs != WM_OK) return rs;
+  launch_bn_apply(y, res, scale, shift, rows, C, rpg, relu, out, st, static_cast<uint8_t*>(relu_mask));
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+// Training backward.  The gradient entering the BN is `dout`, or is gathered from the pooled gradient `ps` (the fused
+// stem; `ysel` then optionally holds the inputs the max-pool selected).  Workspace: partial sums, then the coefficients.
+int bn_bwd_impl(const void* y_, const void* dout_, const void* out_relu_, int relu_from_y, const float* gamma,
+                const float* beta, const float* save_mean, const float* save_invstd, long long rows, int C, int G,
+                float* dgamma, float* dbeta, int accumulate, void* dy_, void* dz_, void* workspace, size_t workspace_bytes,
+                void* stream, const PoolSrc ps, const void* ysel) {
+  WM_REQUIRE(y_ && (dout_ || ps.dy) && save_mean && save_invstd && dy_ && workspace, WM_EINVAL);
+  const int rc = bn_shape_check(rows, C, G);
+  if (rc != WM_OK) return rc;
+  WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint16_t *y = bf16(y_), *dout = bf16(dout_), *out_relu = bf16(out_relu_);
+  uint16_t *dy = bf16(dy_), *dz = bf16(dz_);
+  const int rpg = (int)(rows / G);
+  const bool remask = relu_remask(relu_from_y, out_relu);
+  if (bn_wide(rows, C, G)) {
+    WM_REQUIRE(ps.dy == nullptr && dout, WM_EUNSUPPORTED);
+    bn_col_bwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(y, dout, out_relu, remask ? 1 : 0, gamma, beta, save_mean,
+                                                              save_invstd, rpg, C, G, dgamma, dbeta, accumulate, dy, dz);
+    WM_LAUNCH_CHECK();
+    return WM_OK;
+  }
+  const int nblk = reduce_blocks(rpg, C);
+  float* part = static_cast<float*>(workspace);
+  float* coef = part + (size_t)G * nblk * 2 * C;
+  const int tpr = C >> 3;
+  WM_REQUIRE(!remask || (gamma && beta), WM_EINVAL);
+  int nblk_used = nblk;
+  if (ps.dy != nullptr && ysel != nullptr) {
+    // pooled source with the selected inputs at hand: the sums run over the pooled tensor (a quarter of
+    // the rows, no gather); 1/M in the finalize stays the full row count
+    const long long prow = (long long)(rows / ((long long)ps.H * ps.W)) * ps.P * ps.Q;
+    WM_REQUIRE(prow % G == 0, WM_EUNSUPPORTED);
+    const int prpg = (int)(prow / G);
+    nblk_used = reduce_blocks(prpg, C);
+    if (nblk_used > nblk) nblk_used = nblk;  // the workspace was sized for nblk
+    launch_reduce<1>(bf16(ysel), ps.dy, nullptr, save_mean, save_invstd, gamma, beta, prpg, C, G, nblk_used, part, PoolSrc{},
+                     st);
+  } else {
+    launch_reduce<1>(y, dout, out_relu, save_mean, save_invstd, remask ? gamma : nullptr, remask ? beta : nullptr, rpg, C, G,
+                     nblk, part, ps, st);
+  }
+  WM_LAUNCH_CHECK();
+  launch_finalize(bn_bwd_finalize, C, st, part, nblk_used, G, C, rpg, gamma, beta, save_mean, save_invstd, dgamma, dbeta,
+                  accumulate, coef, 0);
+  WM_LAUNCH_CHECK();
+  if (ps.dy != nullptr && !dz && !out_relu && (ps.H & 1) == 0 && (ps.W & 1) == 0 && BN_THREADS % tpr == 0 &&
+      rows * tpr < (1ll << 31) && (size_t)G * 7 * C * sizeof(float) <= 32768) {  // (32-bit item indices; coefficient rows in LDS)
+    const int n_img = (int)(rows / ((long long)ps.H * ps.W));
+    bn_pool_bwd_apply<<<stream_grid(rows / 4 * tpr), BN_THREADS, (size_t)G * 7 * C * sizeof(float), st>>>(
+        y, coef, G * 7 * C, n_img, C, n_img / G, remask ? 1 : 0, dy, ps, wm_div_make((uint32_t)(C >> 3)),
+        wm_div_make((uint32_t)(ps.W >> 1)), wm_div_make((uint32_t)(ps.H >> 1)), wm_div_make((uint32_t)(n_img / G)));
+    WM_LAUNCH_CHECK();
+    return WM_OK;
+  }
+  const int form = ps.dy != nullptr ? 2 : (out_relu == nullptr && !remask && dz == nullptr) ? 0 : 1;
+  launch_bn_bwd_apply(form, y, dout, out_relu, coef, rows, C, rpg, remask, dy, dz, ps, st);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
 }  // namespace
 
 extern "C" size_t wm_bn_workspace_bytes(long long rows, int C, int G) {
@@ -884,39 +1061,12 @@ extern "C" int wm_bn_train_fwd(const void* y, const void* residual, const float*
                                long long* num_batches_tracked, long long rows, int C, int G, float eps, float momentum, int relu,
                                float* save_mean, float* save_invstd, void* out, void* relu_mask, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(y && out && save_mean && save_invstd && workspace, WM_EINVAL);
-  const int rc = bn_shape_check(rows, C, G);
-  if (rc != WM_OK) return rc;
-  WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = (int)(rows / G);
-  if (bn_wide(rows, C, G)) {
-    WM_REQUIRE(relu_mask == nullptr, WM_EUNSUPPORTED);
-    bn_col_fwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(residual), gamma, beta, running_mean, running_var,
-        num_batches_tracked, rpg, C, G, eps, momentum, relu, 1, save_mean, save_invstd, static_cast<uint16_t*>(out));
-    WM_LAUNCH_CHECK();
-    return WM_OK;
-  }
-  const int nblk = reduce_blocks(rpg, C);
-  float* part = static_cast<float*>(workspace);
-  float* scale = part + (size_t)G * nblk * 2 * C;  // reuse the coefficient planes: scale, shift
-  float* shift = scale + (size_t)G * C;
-  const int tpr = C >> 3, rpp = BN_THREADS / tpr;
-  const size_t lds = (size_t)2 * rpp * C * sizeof(float);
-  bn_reduce<0><<<dim3(nblk, G), BN_THREADS, lds, st>>>(static_cast<const uint16_t*>(y), nullptr, nullptr, nullptr,
-                                                       nullptr, nullptr, nullptr, rpg, C, wm_cdiv(rpg, nblk), part, PoolSrc{});
-  WM_LAUNCH_CHECK();
-  bn_fwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(part, nblk, G, C, rpg, 0, gamma, beta, eps, momentum, running_mean,
-                                                   running_var, num_batches_tracked, save_mean, save_invstd, scale, shift);
-  WM_LAUNCH_CHECK();
-  launch_bn_apply(y, residual, scale, shift, rows, C, rpg, relu, out, st, relu_mask);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  return bn_train_fwd_impl(y, residual, gamma, beta, running_mean, running_var, num_batches_tracked, rows, C, G, eps, momentum,
+                           relu, save_mean, save_invstd, out, relu_mask, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
 // Forward when the producing convolution already accumulated the statistics
-// (wm_conv2d_fwd_stats): finalize (and clear) stat_part [G][stat_buckets][2][C], then apply.
+// (wm_conv2d_fwd_stats): finalize stat_part [G][stat_tiles][2][C], then apply.
 extern "C" int wm_bn_train_fwd_from_stats(const void* y, const void* residual, const float* gamma,
                                           const float* beta, float* running_mean, float* running_var,
                                           long long* num_batches_tracked, long long rows, int C, int G, float eps,
@@ -924,24 +1074,10 @@ extern "C" int wm_bn_train_fwd_from_stats(const void* y, const void* residual, c
                                           float* save_mean, float* save_invstd, void* out, void* relu_mask,
                                           const float* stat_part, int stat_tiles, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(y && out && save_mean && save_invstd && workspace && stat_part, WM_EINVAL);
-  WM_REQUIRE(stat_tiles > 0, WM_EINVAL);
-  const int rc = bn_shape_check(rows, C, G);
-  if (rc != WM_OK) return rc;
-  WM_REQUIRE(workspace_bytes >= ((size_t)2 * G * C + (stat_tiles > 512 ? (size_t)G * 128 * 2 * C : 0)) * sizeof(float), WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = (int)(rows / G);
-  float* scale = static_cast<float*>(workspace);
-  float* shift = scale + (size_t)G * C;
-  int nblk = 0;
-  const float* part = stat_partials(stat_part, stat_tiles, G, C, shift + (size_t)G * C, &nblk, st);
-  WM_LAUNCH_CHECK();
-  bn_fwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(part), nblk, G, C, rpg, 0, gamma, beta, eps, momentum,
-                                                   running_mean, running_var, num_batches_tracked, save_mean, save_invstd, scale, shift);
-  WM_LAUNCH_CHECK();
-  launch_bn_apply(y, residual, scale, shift, rows, C, rpg, relu, out, st, relu_mask);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  WM_REQUIRE(stat_part && stat_tiles > 0, WM_EINVAL);
+  return bn_train_fwd_impl(y, residual, gamma, beta, running_mean, running_var, num_batches_tracked, rows, C, G, eps, momentum,
+                           relu, save_mean, save_invstd, out, relu_mask, stat_part, stat_tiles, workspace, workspace_bytes,
+                           stream);
 }
 
 // Statistics only (no apply pass): mean/invstd/running stats + per-(group, channel) scale and shift
@@ -954,30 +1090,11 @@ extern "C" int wm_bn_train_stats(const void* y, const float* gamma, const float*
   WM_REQUIRE(y && save_mean && save_invstd && scale && shift && workspace, WM_EINVAL);
   const int rc = bn_shape_check(rows, C, G);
   if (rc != WM_OK) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = (int)(rows / G);
-  if (stat_part) {
-    WM_REQUIRE(stat_tiles > 0, WM_EINVAL);
-    WM_REQUIRE(stat_tiles <= 512 || workspace_bytes >= (size_t)G * 128 * 2 * C * sizeof(float), WM_EWORKSPACE);
-    int nblk = 0;
-    const float* part = stat_partials(stat_part, stat_tiles, G, C, static_cast<float*>(workspace), &nblk, st);
-    WM_LAUNCH_CHECK();
-    bn_fwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(part), nblk, G, C, rpg, 0, gamma, beta, eps, momentum,
-                                                     running_mean, running_var, num_batches_tracked, save_mean, save_invstd, scale, shift);
-  } else {
-    WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
-    const int nblk = reduce_blocks(rpg, C);
-    float* part = static_cast<float*>(workspace);
-    const int tpr = C >> 3, rpp = BN_THREADS / tpr;
-    const size_t lds = (size_t)2 * rpp * C * sizeof(float);
-    bn_reduce<0><<<dim3(nblk, G), BN_THREADS, lds, st>>>(static_cast<const uint16_t*>(y), nullptr, nullptr, nullptr,
-                                                         nullptr, nullptr, nullptr, rpg, C, wm_cdiv(rpg, nblk), part, PoolSrc{});
-    WM_LAUNCH_CHECK();
-    bn_fwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(part, nblk, G, C, rpg, 0, gamma, beta, eps, momentum, running_mean,
-                                                     running_var, num_batches_tracked, save_mean, save_invstd, scale, shift);
-  }
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  WM_REQUIRE(!stat_part || stat_tiles > 0, WM_EINVAL);
+  WM_REQUIRE(workspace_bytes >= fwd_partials_bytes(stat_part, stat_tiles, rows, C, G), WM_EWORKSPACE);
+  return bn_fwd_stats(bf16(y), stat_part, stat_tiles, gamma, beta, running_mean, running_var, num_batches_tracked,
+                      (int)(rows / G), C, G, eps, momentum, save_mean, save_invstd, scale, shift,
+                      static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 // Eval-mode scale/shift [C] from the running statistics (for the fused stem in eval mode).
@@ -985,44 +1102,37 @@ extern "C" int wm_bn_eval_scale_shift(const float* gamma, const float* beta, con
                                       const float* running_var, int C, float eps, float* scale, float* shift,
                                       void* stream) {
   WM_REQUIRE(running_mean && running_var && scale && shift && C > 0, WM_EINVAL);
-  bn_eval_params<<<1, C < 1024 ? ((C + 63) / 64) * 64 : 1024, 0, static_cast<hipStream_t>(stream)>>>(
-      gamma, beta, running_mean, running_var, eps, C, scale, shift);
+  launch_eval_params(gamma, beta, running_mean, running_var, eps, C, scale, shift, static_cast<hipStream_t>(stream));
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-extern "C" int wm_bn_eval_fwd(const void* y, const void* residual, const float* gamma, const float* beta,
+extern "C" int wm_bn_eval_fwd(const void* y_, const void* residual, const float* gamma, const float* beta,
                               const float* running_mean, const float* running_var, long long rows, int C,
-                              float eps, int relu, void* out, void* workspace, size_t workspace_bytes,
+                              float eps, int relu, void* out_, void* workspace, size_t workspace_bytes,
                               void* stream) {
-  WM_REQUIRE(y && out && running_mean && running_var && workspace, WM_EINVAL);
+  WM_REQUIRE(y_ && out_ && running_mean && running_var && workspace, WM_EINVAL);
   const int rc = bn_shape_check(rows, C, 1);
   if (rc != WM_OK) return rc;
   WM_REQUIRE(workspace_bytes >= (size_t)2 * C * sizeof(float), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint16_t *y = bf16(y_), *res = bf16(residual);
+  uint16_t* out = bf16(out_);
   if (bn_wide(rows, C, 1)) {
-    bn_col_fwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(residual), gamma, beta,
-        const_cast<float*>(running_mean), const_cast<float*>(running_var), nullptr, (int)rows, C, 1, eps, 0.f, relu, 0, nullptr,
-        nullptr, static_cast<uint16_t*>(out));
+    bn_col_fwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(y, res, gamma, beta, const_cast<float*>(running_mean),
+                                                              const_cast<float*>(running_var), nullptr, (int)rows, C, 1, eps,
+                                                              0.f, relu, 0, nullptr, nullptr, out);
     WM_LAUNCH_CHECK();
     return WM_OK;
   }
   float* scale = static_cast<float*>(workspace);
   float* shift = scale + C;
-  bn_eval_params<<<1, C < 1024 ? ((C + 63) / 64) * 64 : 1024, 0, st>>>(gamma, beta, running_mean, running_var, eps,
-                                                                     C, scale, shift);
+  launch_eval_params(gamma, beta, running_mean, running_var, eps, C, scale, shift, st);
   WM_LAUNCH_CHECK();
-  launch_bn_apply(y, residual, scale, shift, rows, C, (int)(rows < (1ll << 31) - 1 ? rows : (1ll << 31) - 1), relu, out,
-                  st);
+  launch_bn_apply(y, res, scale, shift, rows, C, (int)(rows < (1ll << 31) - 1 ? rows : (1ll << 31) - 1), relu, out, st);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
-
-static int bn_bwd_impl(const void* y, const void* dout, const void* out_relu, int relu_from_y, const float* gamma,
-                       const float* beta, const float* save_mean, const float* save_invstd, long long rows, int C,
-                       int G, float* dgamma, float* dbeta, int accumulate, void* dy, void* dz, void* workspace,
-                       size_t workspace_bytes, void* stream, const PoolSrc ps, const void* ysel = nullptr);
 
 extern "C" int wm_bn_train_bwd(const void* y, const void* dout, const void* out_relu, int relu_from_y,
                                const float* gamma, const float* beta, const float* save_mean,
@@ -1031,11 +1141,11 @@ extern "C" int wm_bn_train_bwd(const void* y, const void* dout, const void* out_
                                size_t workspace_bytes, void* stream) {
   WM_REQUIRE(dout, WM_EINVAL);
   return bn_bwd_impl(y, dout, out_relu, relu_from_y, gamma, beta, save_mean, save_invstd, rows, C, G, dgamma, dbeta,
-                     accumulate, dy, dz, workspace, workspace_bytes, stream, PoolSrc{});
+                     accumulate, dy, dz, workspace, workspace_bytes, stream, PoolSrc{}, nullptr);
 }
 
 // Backward when the producing dgrad (wm_conv2d_dgrad_bnstat) already took the gradient through the ReLU and
-// accumulated (sum g, sum g * xhat): finalize (and clear) the buckets, then ONE pass over (y, g).
+// accumulated (sum g, sum g * xhat): finalize the buckets, then ONE pass over (y, g).
 extern "C" int wm_bn_train_bwd_from_stats(const void* y, const void* g, const float* gamma, const float* beta,
                                           const float* save_mean, const float* save_invstd, long long rows, int C,
                                           int G, float* dgamma, float* dbeta, int accumulate, void* dy,
@@ -1045,26 +1155,17 @@ extern "C" int wm_bn_train_bwd_from_stats(const void* y, const void* g, const fl
   const int rc = bn_shape_check(rows, C, G);
   if (rc != WM_OK) return rc;
   WM_REQUIRE(!bn_wide(rows, C, G), WM_EUNSUPPORTED);
-  WM_REQUIRE(workspace_bytes >= ((size_t)7 * G * C + (stat_tiles > 512 ? (size_t)G * 128 * 2 * C : 0)) * sizeof(float), WM_EWORKSPACE);
+  WM_REQUIRE(workspace_bytes >= ((size_t)7 * G * C + stat_scratch_floats(stat_tiles, G, C)) * sizeof(float), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rpg = (int)(rows / G);
   float* coef = static_cast<float*>(workspace);
   int nblk = 0;
   const float* part = stat_partials(stat_part, stat_tiles, G, C, coef + (size_t)7 * G * C, &nblk, st);
   WM_LAUNCH_CHECK();
-  bn_bwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(part), nblk, G, C, rpg, gamma, beta,
-                                                   save_mean, save_invstd, dgamma, dbeta, accumulate, coef, 1);
+  launch_finalize(bn_bwd_finalize, C, st, part, nblk, G, C, rpg, gamma, beta, save_mean, save_invstd, dgamma, dbeta, accumulate,
+                  coef, 1);   // (1: the dgrad epilogue's second sum is sum g * (y - mean))
   WM_LAUNCH_CHECK();
-  const int tpr = C >> 3;
-  int csh = 0;
-  if (chunk_pow2(C, &csh))
-    bn_bwd_apply<true, 0><<<stream_grid(rows * tpr), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(g), nullptr, coef, rows, C, rpg, 0, csh,
-        static_cast<uint16_t*>(dy), nullptr, PoolSrc{});
-  else
-    bn_bwd_apply<false, 0><<<stream_grid(rows * tpr), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(g), nullptr, coef, rows, C, rpg, 0, csh,
-        static_cast<uint16_t*>(dy), nullptr, PoolSrc{});
+  launch_bn_bwd_apply(0, bf16(y), bf16(g), nullptr, coef, rows, C, rpg, false, bf16(dy), nullptr, PoolSrc{}, st);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
@@ -1079,90 +1180,11 @@ extern "C" int wm_bn_relu_maxpool_bwd(const void* y, const void* ysel, const voi
   WM_REQUIRE(pooled_dy && pool_idx && gamma && beta, WM_EINVAL);
   WM_REQUIRE(N > 0 && H > 1 && W > 1 && (long long)N * H * W < (1ll << 31), WM_EINVAL);
   PoolSrc ps;
-  ps.dy = static_cast<const uint16_t*>(pooled_dy);
+  ps.dy = bf16(pooled_dy);
   ps.idx = static_cast<const uint8_t*>(pool_idx);
   ps.H = H; ps.W = W; ps.P = (H + 2 - 3) / 2 + 1; ps.Q = (W + 2 - 3) / 2 + 1;
   return bn_bwd_impl(y, nullptr, nullptr, 1, gamma, beta, save_mean, save_invstd, (long long)N * H * W, C, G, dgamma,
                      dbeta, accumulate, dy, nullptr, workspace, workspace_bytes, stream, ps, ysel);
-}
-
-static int bn_bwd_impl(const void* y, const void* dout, const void* out_relu, int relu_from_y, const float* gamma,
-                       const float* beta, const float* save_mean, const float* save_invstd, long long rows, int C,
-                       int G, float* dgamma, float* dbeta, int accumulate, void* dy, void* dz, void* workspace,
-                       size_t workspace_bytes, void* stream, const PoolSrc ps, const void* ysel) {
-  WM_REQUIRE(y && (dout || ps.dy) && save_mean && save_invstd && dy && workspace, WM_EINVAL);
-  const int rc = bn_shape_check(rows, C, G);
-  if (rc != WM_OK) return rc;
-  WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = (int)(rows / G);
-  if (bn_wide(rows, C, G)) {
-    WM_REQUIRE(ps.dy == nullptr && dout, WM_EUNSUPPORTED);
-    const bool rm = relu_from_y && !out_relu;
-    bn_col_bwd<<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        rm ? 1 : 0, gamma, beta, save_mean, save_invstd, rpg, C, G, dgamma, dbeta, accumulate, static_cast<uint16_t*>(dy),
-        static_cast<uint16_t*>(dz));
-    WM_LAUNCH_CHECK();
-    return WM_OK;
-  }
-  const int nblk = reduce_blocks(rpg, C);
-  float* part = static_cast<float*>(workspace);
-  float* coef = part + (size_t)G * nblk * 2 * C;
-  const int tpr = C >> 3, rpp = BN_THREADS / tpr;
-  const size_t lds = (size_t)2 * rpp * C * sizeof(float);
-  const bool remask = relu_from_y && !out_relu;
-  WM_REQUIRE(!remask || (gamma && beta), WM_EINVAL);
-  int nblk_used = nblk;
-  if (ps.dy != nullptr && ysel != nullptr) {
-    // pooled source with the selected inputs at hand: the sums run over the pooled tensor (a quarter of
-    // the rows, no gather); 1/M in the finalize stays the full row count
-    const long long prow = (long long)(rows / ((long long)ps.H * ps.W)) * ps.P * ps.Q;
-    WM_REQUIRE(prow % G == 0, WM_EUNSUPPORTED);
-    const int prpg = (int)(prow / G);
-    nblk_used = reduce_blocks(prpg, C);
-    if (nblk_used > nblk) nblk_used = nblk;  // the workspace was sized for nblk
-    bn_reduce<1><<<dim3(nblk_used, G), BN_THREADS, lds, st>>>(
-        static_cast<const uint16_t*>(ysel), ps.dy, nullptr, save_mean, save_invstd, gamma, beta, prpg, C,
-        wm_cdiv(prpg, nblk_used), part, PoolSrc{});
-  } else {
-    bn_reduce<1><<<dim3(nblk, G), BN_THREADS, lds, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        save_mean, save_invstd, remask ? gamma : nullptr, remask ? beta : nullptr, rpg, C, wm_cdiv(rpg, nblk), part, ps);
-  }
-  WM_LAUNCH_CHECK();
-  bn_bwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(part, nblk_used, G, C, rpg, gamma, beta, save_mean, save_invstd,
-                                                   dgamma, dbeta, accumulate, coef, 0);
-  WM_LAUNCH_CHECK();
-  int csh = 0;
-  if (ps.dy != nullptr && !dz && !out_relu && (ps.H & 1) == 0 && (ps.W & 1) == 0 && BN_THREADS % tpr == 0 &&
-      rows * tpr < (1ll << 31) && (size_t)G * 7 * C * sizeof(float) <= 32768) {  // (32-bit item indices; coefficient rows in LDS)
-    const int n_img = (int)(rows / ((long long)ps.H * ps.W));
-    bn_pool_bwd_apply<<<stream_grid(rows / 4 * tpr), BN_THREADS, (size_t)G * 7 * C * sizeof(float), st>>>(
-        static_cast<const uint16_t*>(y), coef, G * 7 * C, n_img, C, n_img / G, remask ? 1 : 0, static_cast<uint16_t*>(dy), ps,
-        wm_div_make((uint32_t)(C >> 3)), wm_div_make((uint32_t)(ps.W >> 1)), wm_div_make((uint32_t)(ps.H >> 1)),
-        wm_div_make((uint32_t)(n_img / G)));
-    WM_LAUNCH_CHECK();
-    return WM_OK;
-  }
-  const bool pow2 = chunk_pow2(C, &csh);
-  auto launch = [&](auto kernel) {
-    kernel<<<stream_grid(rows * tpr), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        coef, rows, C, rpg, remask ? 1 : 0, csh, static_cast<uint16_t*>(dy), static_cast<uint16_t*>(dz), ps);
-  };
-  if (ps.dy != nullptr) {
-    if (pow2) launch(bn_bwd_apply<true, 2>);
-    else launch(bn_bwd_apply<false, 2>);
-  } else if (out_relu == nullptr && !remask && dz == nullptr) {
-    if (pow2) launch(bn_bwd_apply<true, 0>);
-    else launch(bn_bwd_apply<false, 0>);
-  } else {
-    if (pow2) launch(bn_bwd_apply<true, 1>);
-    else launch(bn_bwd_apply<false, 1>);
-  }
-  WM_LAUNCH_CHECK();
-  return WM_OK;
 }
 
 // ---- synchronised BatchNorm (torch.nn.SyncBatchNorm semantics: statistics over the batches of ALL ranks) -------------
@@ -1176,29 +1198,17 @@ extern "C" int wm_bn_sync_fwd_sums(const void* y, long long rows, int C, int G, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int rpg = (int)(rows / G);
   if (bn_wide(rows, C, G)) {   // projection-head widths (BYOL: BatchNorm1d(4096)): one thread per channel
-    bn_col_sums<0><<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(static_cast<const uint16_t*>(y), nullptr, nullptr, 0, nullptr,
-                                                                 nullptr, nullptr, nullptr, rpg, C, G, sums);
+    bn_col_sums<0><<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(bf16(y), nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                                                                 nullptr, rpg, C, G, sums);
     WM_LAUNCH_CHECK();
     return WM_OK;
   }
+  WM_REQUIRE(!stat_part || stat_tiles > 0, WM_EINVAL);
+  WM_REQUIRE(workspace_bytes >= fwd_partials_bytes(stat_part, stat_tiles, rows, C, G), WM_EWORKSPACE);
   int nblk = 0;
-  const float* part;
-  if (stat_part) {
-    WM_REQUIRE(stat_tiles > 0, WM_EINVAL);
-    WM_REQUIRE(stat_tiles <= 512 || workspace_bytes >= (size_t)G * 128 * 2 * C * sizeof(float), WM_EWORKSPACE);
-    part = stat_partials(stat_part, stat_tiles, G, C, static_cast<float*>(workspace), &nblk, st);
-  } else {
-    WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
-    nblk = reduce_blocks(rpg, C);
-    const int tpr = C >> 3, rpp = BN_THREADS / tpr;
-    const size_t lds = (size_t)2 * rpp * C * sizeof(float);
-    bn_reduce<0><<<dim3(nblk, G), BN_THREADS, lds, st>>>(static_cast<const uint16_t*>(y), nullptr, nullptr, nullptr,
-                                                         nullptr, nullptr, nullptr, rpg, C, wm_cdiv(rpg, nblk),
-                                                         static_cast<float*>(workspace), PoolSrc{});
-    part = static_cast<float*>(workspace);
-  }
+  const float* part = fwd_partials(bf16(y), stat_part, stat_tiles, rpg, C, G, static_cast<float*>(workspace), &nblk, st);
   WM_LAUNCH_CHECK();
-  bn_sums_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(part), nblk, G, C, sums);
+  launch_finalize(bn_sums_finalize, C, st, part, nblk, G, C, sums);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
@@ -1216,50 +1226,46 @@ extern "C" int wm_bn_sync_fwd_apply(const void* y, const void* residual, const f
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* scale = static_cast<float*>(workspace);
   float* shift = scale + (size_t)G * C;
-  bn_fwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(sums), 1, G, C, (int)group_count, 0, gamma, beta, eps,
-                                                   momentum, running_mean, running_var, num_batches_tracked, save_mean,
-                                                   save_invstd, scale, shift);
+  launch_finalize(bn_fwd_finalize, C, st, sums, 1, G, C, (int)group_count, 0, gamma, beta, eps, momentum, running_mean,
+                  running_var, num_batches_tracked, save_mean, save_invstd, scale, shift);
   WM_LAUNCH_CHECK();
-  launch_bn_apply(y, residual, scale, shift, rows, C, (int)(rows / G), relu, out, st);
+  launch_bn_apply(bf16(y), bf16(residual), scale, shift, rows, C, (int)(rows / G), relu, bf16(out), st);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
 // Local (sum g, sum g * xhat) per (group, channel) -> sums [G][2][C], and this rank's dgamma / dbeta (torch's
 // SyncBatchNorm leaves their reduction to the gradient exchange).  Workspace as wm_bn_train_bwd.
-extern "C" int wm_bn_sync_bwd_sums(const void* y, const void* dout, const void* out_relu, int relu_from_y,
+extern "C" int wm_bn_sync_bwd_sums(const void* y_, const void* dout_, const void* out_relu_, int relu_from_y,
                                    const float* gamma, const float* beta, const float* save_mean,
                                    const float* save_invstd, long long rows, int C, int G, float* dgamma, float* dbeta,
                                    int accumulate, float* sums, void* workspace, size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(y && dout && save_mean && save_invstd && sums && workspace, WM_EINVAL);
+  WM_REQUIRE(y_ && dout_ && save_mean && save_invstd && sums && workspace, WM_EINVAL);
   const int rc = bn_shape_check(rows, C, G);
   if (rc != WM_OK) return rc;
   WM_REQUIRE(workspace_bytes >= wm_bn_workspace_bytes(rows, C, G), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint16_t *y = bf16(y_), *dout = bf16(dout_), *out_relu = bf16(out_relu_);
   const int rpg = (int)(rows / G);
   const int nblk = reduce_blocks(rpg, C);
   float* part = static_cast<float*>(workspace);
   float* coef = part + (size_t)G * nblk * 2 * C;
-  const bool remask = relu_from_y && !out_relu;
+  const bool remask = relu_remask(relu_from_y, out_relu);
   WM_REQUIRE(!remask || (gamma && beta), WM_EINVAL);
   if (bn_wide(rows, C, G)) {
-    bn_col_sums<1><<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        remask ? 1 : 0, gamma, beta, save_mean, save_invstd, rpg, C, G, sums);
+    bn_col_sums<1><<<wm_cdiv(C, BN_THREADS), BN_THREADS, 0, st>>>(y, dout, out_relu, remask ? 1 : 0, gamma, beta, save_mean,
+                                                                 save_invstd, rpg, C, G, sums);
     WM_LAUNCH_CHECK();
   } else {
-    const int tpr = C >> 3, rpp = BN_THREADS / tpr;
-    const size_t lds = (size_t)2 * rpp * C * sizeof(float);
-    bn_reduce<1><<<dim3(nblk, G), BN_THREADS, lds, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        save_mean, save_invstd, remask ? gamma : nullptr, remask ? beta : nullptr, rpg, C, wm_cdiv(rpg, nblk), part, PoolSrc{});
+    launch_reduce<1>(y, dout, out_relu, save_mean, save_invstd, remask ? gamma : nullptr, remask ? beta : nullptr, rpg, C, G,
+                     nblk, part, PoolSrc{}, st);
     WM_LAUNCH_CHECK();
-    bn_sums_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(part, nblk, G, C, sums);
+    launch_finalize(bn_sums_finalize, C, st, part, nblk, G, C, sums);
     WM_LAUNCH_CHECK();
   }
   if (dgamma || dbeta) {  // the local parameter gradients from the local totals (coef is scratch here)
-    bn_bwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(sums, 1, G, C, rpg, gamma, beta, save_mean, save_invstd, dgamma,
-                                                     dbeta, accumulate, coef, 0);
+    launch_finalize(bn_bwd_finalize, C, st, sums, 1, G, C, rpg, gamma, beta, save_mean, save_invstd, dgamma, dbeta, accumulate,
+                    coef, 0);
     WM_LAUNCH_CHECK();
   }
   return WM_OK;
@@ -1277,23 +1283,14 @@ extern "C" int wm_bn_sync_bwd_apply(const void* y, const void* dout, const void*
   WM_REQUIRE(group_count >= rows / G && group_count < (1ll << 31), WM_EINVAL);   // (finalize + apply serve any width)
   WM_REQUIRE(workspace_bytes >= (size_t)7 * G * C * sizeof(float), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = (int)(rows / G);
   float* coef = static_cast<float*>(workspace);
-  const bool remask = relu_from_y && !out_relu;
+  const bool remask = relu_remask(relu_from_y, out_relu);
   WM_REQUIRE(!remask || (gamma && beta), WM_EINVAL);
-  bn_bwd_finalize<<<wm_cdiv(C, 32), 1024, 0, st>>>(const_cast<float*>(sums), 1, G, C, (int)group_count, gamma, beta,
-                                                   save_mean, save_invstd, nullptr, nullptr, 0, coef, 0);
+  launch_finalize(bn_bwd_finalize, C, st, sums, 1, G, C, (int)group_count, gamma, beta, save_mean, save_invstd, nullptr,
+                  nullptr, 0, coef, 0);
   WM_LAUNCH_CHECK();
-  const int tpr = C >> 3;
-  int csh = 0;
-  if (chunk_pow2(C, &csh))
-    bn_bwd_apply<true, 1><<<stream_grid(rows * tpr), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        coef, rows, C, rpg, remask ? 1 : 0, csh, static_cast<uint16_t*>(dy), static_cast<uint16_t*>(dz), PoolSrc{});
-  else
-    bn_bwd_apply<false, 1><<<stream_grid(rows * tpr), BN_THREADS, 0, st>>>(
-        static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(dout), static_cast<const uint16_t*>(out_relu),
-        coef, rows, C, rpg, remask ? 1 : 0, csh, static_cast<uint16_t*>(dy), static_cast<uint16_t*>(dz), PoolSrc{});
+  launch_bn_bwd_apply(1, bf16(y), bf16(dout), bf16(out_relu), coef, rows, C, (int)(rows / G), remask, bf16(dy), bf16(dz),
+                      PoolSrc{}, st);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
@@ -1301,8 +1298,7 @@ extern "C" int wm_bn_sync_bwd_apply(const void* y, const void* dout, const void*
 extern "C" int wm_add_bf16(const void* a, const void* b, long long n, void* out, void* stream) {
   WM_REQUIRE(a && b && out && n > 0, WM_EINVAL);
   WM_REQUIRE(n % 8 == 0, WM_EUNSUPPORTED);
-  add_bf16_kernel<<<stream_grid(n / 8), BN_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      static_cast<const uint16_t*>(a), static_cast<const uint16_t*>(b), n / 8, static_cast<uint16_t*>(out));
+  add_bf16_kernel<<<stream_grid(n / 8), BN_THREADS, 0, static_cast<hipStream_t>(stream)>>>(bf16(a), bf16(b), n / 8, bf16(out));
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
