@@ -124,7 +124,7 @@ class ViewBranches:
     convolutions on the chip (tools/probes/overlap_probe.py: a convolution and a BatchNorm pass of equal length on two
     streams take 0.76 of their sum).  Same arithmetic per view.  What a module caches for "its" launches is kept per
     branch (statistics slots: stats_buffer; scratch: per stream), parameter gradients of the side branch join the pass's
-    ordered fold instead of adding into the slots directly (ops._BatchNorm.backward), and the side branch's batch
+    ordered fold instead of adding into the slots directly (ops._bn_param_grads, _StemConv.backward), and the side branch's batch
     statistics reach the running statistics through merge().
 
     The BatchNorm layers' running statistics are moved into ONE flat buffer (the modules' buffers become views of it),

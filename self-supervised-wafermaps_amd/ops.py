@@ -151,27 +151,37 @@ def current_branch() -> int:
     return _BRANCH
 
 
-def _bn_fold_buffers(gamma: torch.Tensor, c: int, device):
-    """Persistent (dgamma, dbeta) buffers of a BatchNorm whose backward runs on a side branch: stable addresses (the
-    fold's descriptor table is cached by them, and a captured graph bakes them in), one pair per use in a pass."""
-    idx = getattr(gamma, "_hip_pending", 0)
-    bufs = getattr(gamma, "_hip_bn_fold", None)
+def _use_buffer(owner: torch.Tensor, attr: str, numel: int, device) -> torch.Tensor:
+    """Persistent f32 scratch [numel] of `owner` (a parameter), kept under `attr`: one buffer per use of the parameter in
+    a backward pass (`_hip_pending` counts the uses already queued for the fold, which reads them all at the end of the
+    pass), so its address is stable from step to step -- the fold's descriptor table is cached by it and a captured hipGraph
+    bakes it in.  Reallocated when the size or the device changes; a buffer that was handed out during a capture then
+    stays referenced beside its replacement (as StatSlots.get: the graph writes it at every replay)."""
+    idx = getattr(owner, "_hip_pending", 0)
+    bufs = getattr(owner, attr, None)
     if bufs is None:
-        bufs = gamma._hip_bn_fold = []
+        bufs = []
+        setattr(owner, attr, bufs)
     while len(bufs) <= idx:
         bufs.append(None)
-    b = bufs[idx]
-    if b is None or b.numel() != 2 * c or b.device != device:
-        b = bufs[idx] = torch.empty(2 * c, dtype=torch.float32, device=device)
-    return b[:c], b[c:]
+    ent = bufs[idx]   # [buffer, a capture has seen it]
+    if ent is None or ent[0].numel() != numel or ent[0].device != device:
+        if ent is not None and ent[1]:
+            retired = getattr(owner, attr + "_retired", None)
+            if retired is None:
+                retired = []
+                setattr(owner, attr + "_retired", retired)
+            retired.append(ent[0])
+        ent = bufs[idx] = [torch.empty(numel, dtype=torch.float32, device=device), False]
+    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        ent[1] = True
+    return ent[0]
 
 
-def _flat_fold_buffer(owner: torch.Tensor, numel: int, device) -> torch.Tensor:
-    """A persistent f32 buffer of `owner` for a gradient that joins the fold as one flat row (see _bn_fold_buffers)."""
-    b = getattr(owner, "_hip_flat_fold", None)
-    if b is None or b.numel() != numel or b.device != device:
-        b = owner._hip_flat_fold = torch.empty(numel, dtype=torch.float32, device=device)
-    return b
+def _pad_grads(ctx, *grads):
+    """`grads` for the leading forward arguments, None for the rest: a backward's return tuple, as long as its forward's
+    argument list."""
+    return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 class _StackRows(torch.autograd.Function):
@@ -406,34 +416,6 @@ def wgrad_splits(n, h, w, c, k, r, s, p, q, stride, pad) -> int:
     return v
 
 
-def _slab_buffers(owner: torch.Tensor, nsplit: int, numel: int, bias_k: int = 0):
-    """Persistent slab buffers of one parameter: f32 [nsplit * numel] (+ [nsplit * bias_k]).  Every wgrad launch
-    overwrites all of its slabs, so nothing is ever zeroed.  A parameter used by several wgrad launches of ONE backward
-    pass (shared weights) gets one buffer per launch: the fold at the end of the pass reads them all."""
-    idx = getattr(owner, "_hip_pending", 0)
-    bufs = getattr(owner, "_hip_wgrad_slabs", None)
-    if bufs is None:
-        bufs = owner._hip_wgrad_slabs = []
-    while len(bufs) <= idx:
-        bufs.append(None)
-    ent = bufs[idx]
-    capturing = owner.is_cuda and torch.cuda.is_current_stream_capturing()
-    if (ent is None or ent[0].numel() != nsplit * numel or ent[0].device != owner.device
-            or (bias_k > 0 and (ent[1] is None or ent[1].numel() != nsplit * bias_k))):
-        if ent is not None and ent[2]:
-            # (as StatSlots.get: the slabs a captured graph writes stay alive beside their replacement)
-            retired = getattr(owner, "_hip_wgrad_retired", None)
-            if retired is None:
-                retired = owner._hip_wgrad_retired = []
-            retired.append(ent)
-        ent = [torch.empty(nsplit * numel, dtype=torch.float32, device=owner.device),
-               torch.empty(nsplit * bias_k, dtype=torch.float32, device=owner.device) if bias_k > 0 else None, False]
-        bufs[idx] = ent
-    if capturing:
-        ent[2] = True
-    return ent[0], ent[1]
-
-
 # ---- weight gradients on a SIDE stream.  Nothing in the backward chain waits for a weight gradient: only the fold at
 # the end of the pass reads the slabs.  The chain itself alternates MFMA-bound launches (dgrad) with HBM-bound ones
 # (BatchNorm / LayerNorm backward), so the MFMA-bound wgrad launches run beside it on a second stream: fork = the side
@@ -468,10 +450,13 @@ def side_join() -> None:
 
 
 def wgrad(dy, x, owner, n, h, w, c, k, r, s, p, q, stride, pad, bias_k: int = 0, name: str = "conv_wgrad"):
-    """Launch the weight-gradient kernel of one layer into `owner`'s slab buffer.
+    """Launch the weight-gradient kernel of one layer into `owner`'s persistent slab buffers: f32 [nsplit * K*R*S*C]
+    (+ [nsplit * bias_k]).  Every launch overwrites all of its slabs, so nothing is ever zeroed; a parameter used by
+    several wgrad launches of ONE backward pass (shared weights) has one buffer per launch (_use_buffer).
     Returns (slabs, bias slabs or None, nsplit)."""
     ns = wgrad_splits(n, h, w, c, k, r, s, p, q, stride, pad)
-    slabs, bslabs = _slab_buffers(owner, ns, k * r * s * c, bias_k)
+    slabs = _use_buffer(owner, "_hip_wgrad_slabs", ns * k * r * s * c, owner.device)
+    bslabs = _use_buffer(owner, "_hip_wgrad_bias_slabs", ns * bias_k, owner.device) if bias_k > 0 else None
     lib = _lib.load()
     if dy.is_cuda:
         _WGRAD_STREAMS.add(torch.cuda.current_stream(dy.device))   # the fold waits for every stream that wrote slabs
@@ -497,15 +482,29 @@ def rows_outer_product(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     slabs = torch.empty(ns * k * c, dtype=torch.float32, device=a.device)
     lib = _lib.load()
     check(lib.wm_conv2d_wgrad(ptr(a), ptr(b), ptr(slabs), n, 1, 1, c, k, 1, 1, 1, 1, 1, 0, stream_ptr()), "wm_conv2d_wgrad")
-    out = torch.empty((k, c), dtype=torch.float32, device=a.device)
-    check(lib.wm_wgrad_finalize(ptr(slabs), ns, k, c, 1, 1, ptr(out), 0, stream_ptr()), "wm_wgrad_finalize")
-    return out
+    return finalize_into(slabs, ns, k, c, 1, 1, None, (k, c))
+
+
+def finalize_into(slabs, ns, k, c, r, s, param, shape, stem: bool = False):
+    """Sum the `ns` slabs ([K][R][S][C] f32 each) of one gradient in slab order: ADDED into `param`'s gradient slot when a
+    fused optimiser owns it (returns None: nothing for autograd), else stored as a new float32 tensor of `shape`, which is
+    returned (`param` None: always).  stem: the slabs are those of the stem's space-to-depth form ([K][4][4][16] -> OIHW
+    [K, 3, 7, 7], wm_stem_wgrad_finalize)."""
+    lib = _lib.load()
+    slot = _arena_grad(param) if param is not None else None
+    tgt = slot if slot is not None else torch.empty(shape, dtype=torch.float32, device=slabs.device)
+    if stem:
+        check(lib.wm_stem_wgrad_finalize(ptr(slabs), ns, k, ptr(tgt), int(slot is not None), stream_ptr()),
+              "wm_stem_wgrad_finalize")
+    else:
+        check(lib.wm_wgrad_finalize(ptr(slabs), ns, k, c, r, s, ptr(tgt), int(slot is not None), stream_ptr()),
+              "wm_wgrad_finalize")
+    return None if slot is not None else tgt
 
 
 def wgrad_deliver(weight, slabs, ns, k, c, r, s, bias=None, bslabs=None):
     """Turn the slabs of one wgrad launch into gradients: queued for the pass's batched fold when a fused optimiser owns
-    the gradient slot (returns None for that gradient), else summed now into a new tensor.  Returns (dw, dbias)."""
-    lib = _lib.load()
+    the gradient slot (returns None for that gradient), else summed now (finalize_into).  Returns (dw, dbias)."""
     slot = _arena_grad(weight)
     bslot = _arena_grad(bias) if bias is not None else None
     dw = db = None
@@ -515,17 +514,9 @@ def wgrad_deliver(weight, slabs, ns, k, c, r, s, bias=None, bslabs=None):
     if fold_w:
         _queue_fold(weight, slabs, ns, slot, k, c, r * s, bslabs if bslot is not None else None, bslot)
     else:
-        tgt = slot
-        if tgt is None:
-            dw = tgt = torch.empty((k, c, r, s) if weight.dim() == 4 else (k, c), dtype=torch.float32, device=slabs.device)
-        check(lib.wm_wgrad_finalize(ptr(slabs), ns, k, c, r, s, ptr(tgt), int(slot is not None), stream_ptr()),
-              "wm_wgrad_finalize")
+        dw = finalize_into(slabs, ns, k, c, r, s, weight, (k, c, r, s) if weight.dim() == 4 else (k, c))
     if bias is not None and bslabs is not None and not (fold_w and bslot is not None):
-        tgt = bslot
-        if tgt is None:
-            db = tgt = torch.empty((k,), dtype=torch.float32, device=slabs.device)
-        check(lib.wm_wgrad_finalize(ptr(bslabs), ns, k, 1, 1, 1, ptr(tgt), int(bslot is not None), stream_ptr()),
-              "wm_wgrad_finalize(bias)")
+        db = finalize_into(bslabs, ns, k, 1, 1, 1, bias, (k,))
     return dw, db
 
 
@@ -700,6 +691,22 @@ def _out_hw(h, w, r, s, stride, pad):
     return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
 
 
+def _conv_fwd(x, wk, y, geom, work, stats, groups, tag: str = "") -> None:
+    """The forward convolution launch of geometry `geom` = (n, h, w, c, k, r, s, p, q, stride, pad) with kernel-layout
+    weights `wk`: with the BatchNorm statistics of the output stored per tile in its epilogue when a StatSlots object is
+    given and `stats_fusable`, else the plain entry point."""
+    n, p, q = geom[0], geom[7], geom[8]
+    rows = n * p * q
+    lib = _lib.load()
+    if stats is not None and stats_fusable(rows, groups):
+        tiles = fwd_stat_tiles(*geom, rows // groups)
+        check(_run("conv_fwd", work, lib.wm_conv2d_fwd_stats, ptr(x), ptr(wk), y.data_ptr(), *geom,
+                   ptr(stats.get(groups, tiles, x.device)), tiles, rows // groups, stream_ptr()), "wm_conv2d_fwd_stats" + tag)
+    else:
+        check(_run("conv_fwd", work, lib.wm_conv2d_fwd, ptr(x), ptr(wk), y.data_ptr(), *geom, stream_ptr()),
+              "wm_conv2d_fwd" + tag)
+
+
 class _Conv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, stride, pad, stats=None, groups=1, pass_input=False, link=None):
@@ -713,17 +720,11 @@ class _Conv2d(torch.autograd.Function):
         train = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
         krsc, _ = _WCACHE.get(weight, need_crsk=train and x.requires_grad)
         y = _empty_nhwc(n, k, p, q, x.device)
-        if stats is not None and stats_fusable(n * p * q, groups):
-            tiles = fwd_stat_tiles(n, h, w, c, k, r, s, p, q, stride, pad, n * p * q // groups)
-            check(_run("conv_fwd", 2.0 * n * p * q * k * r * s * c, _lib.load().wm_conv2d_fwd_stats, ptr(x), ptr(krsc),
-                       y.data_ptr(), n, h, w, c, k, r, s, p, q, stride, pad, ptr(stats.get(groups, tiles, x.device)), tiles,
-                       n * p * q // groups, stream_ptr()), "wm_conv2d_fwd_stats")
-        else:
-            check(_run("conv_fwd", 2.0 * n * p * q * k * r * s * c, _lib.load().wm_conv2d_fwd, ptr(x), ptr(krsc),
-                       y.data_ptr(), n, h, w, c, k, r, s, p, q, stride, pad, stream_ptr()), "wm_conv2d_fwd")
+        geom = (n, h, w, c, k, r, s, p, q, stride, pad)
+        _conv_fwd(x, krsc, y, geom, 2.0 * n * p * q * k * r * s * c, stats, groups)
         ctx.save_for_backward(x)
         ctx.weight = weight
-        ctx.geom = (n, h, w, c, k, r, s, p, q, stride, pad)
+        ctx.geom = geom
         ctx.link = link if (_BN_FUSE_BWD and link is not None and link.y.shape == x.shape) else None
         if pass_input:
             # second output: the input itself (identity).  Its gradient comes back to THIS backward,
@@ -744,30 +745,30 @@ class _Conv2d(torch.autograd.Function):
             dx = _empty_nhwc(n, c, h, w, dy.device)
             if dres is not None:
                 dres = _as_nhwc(dres)
+
+            def dgrad(entry, *mid, tail=()):   # entry(dy, weights, *mid, dx, geometry, *tail, stream)
+                check(_run("conv_dgrad", 2.0 * n * p * q * k * r * s * c, getattr(lib, entry), dy.data_ptr(), ptr(crsk), *mid,
+                           dx.data_ptr(), *ctx.geom, *tail, stream_ptr()), entry)
+
             link = ctx.link
             if (link is not None and not link.ready and getattr(link.stats, "_hip_busy", None) is None
                     and lib.wm_conv2d_dgrad_bnstat_ok(n, h, w, c, k, r, s, p, q, stride, pad, link.groups)):
                 # the input was relu(BN(link.y) (+ shortcut)): ReLU backward + that BatchNorm's backward sums in the epilogue
                 tiles = n * h * w // link.groups // 128
-                check(_run("conv_dgrad", 2.0 * n * p * q * k * r * s * c, lib.wm_conv2d_dgrad_bnstat, dy.data_ptr(), ptr(crsk),
-                           dres.data_ptr() if dres is not None else 0, dx.data_ptr(), n, h, w, c, k, r, s, p, q, stride, pad,
-                           link.y.data_ptr(), x.data_ptr() if (link.has_res and link.mask is None) else 0,
-                           ptr(link.mask) if (link.has_res and link.mask is not None) else 0, ptr(link.gamma), ptr(link.beta),
-                           ptr(link.mean), ptr(link.invstd), link.groups, ptr(link.stats.get(link.groups, tiles, dy.device)),
-                           tiles, stream_ptr()), "wm_conv2d_dgrad_bnstat")
+                dgrad("wm_conv2d_dgrad_bnstat", ptr(dres), tail=(
+                    link.y.data_ptr(), x.data_ptr() if (link.has_res and link.mask is None) else 0,
+                    ptr(link.mask) if link.has_res else 0, ptr(link.gamma), ptr(link.beta), ptr(link.mean),
+                    ptr(link.invstd), link.groups, ptr(link.stats.get(link.groups, tiles, dy.device)), tiles))
                 link.ready, link.g_ptr, link.g_version = True, dx.data_ptr(), dx._version
                 link.stats._hip_busy = True
             elif dres is not None:
-                check(_run("conv_dgrad", 2.0 * n * p * q * k * r * s * c, lib.wm_conv2d_dgrad_add, dy.data_ptr(),
-                           ptr(crsk), dres.data_ptr(), dx.data_ptr(), n, h, w, c, k, r, s, p, q, stride, pad,
-                           stream_ptr()), "wm_conv2d_dgrad_add")
+                dgrad("wm_conv2d_dgrad_add", dres.data_ptr())
             else:
-                check(_run("conv_dgrad", 2.0 * n * p * q * k * r * s * c, lib.wm_conv2d_dgrad, dy.data_ptr(), ptr(crsk),
-                           dx.data_ptr(), n, h, w, c, k, r, s, p, q, stride, pad, stream_ptr()), "wm_conv2d_dgrad")
+                dgrad("wm_conv2d_dgrad")
         if ctx.needs_input_grad[1]:
             slabs, _, ns = wgrad(dy, x, weight, n, h, w, c, k, r, s, p, q, stride, pad)
             dw, _ = wgrad_deliver(weight, slabs, ns, k, c, r, s)
-        return dx, dw, None, None, None, None, None, None
+        return _pad_grads(ctx, dx, dw)
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1, padding: int = 0,
@@ -820,14 +821,7 @@ class _StemConv(torch.autograd.Function):
             check(lib.wm_image_to_s2d(x.data_ptr(), fmt, n, h, w, ptr(xs), stream_ptr()), "wm_image_to_s2d")
         ws2d, _ = _WCACHE.get(weight, kind="stem")
         y = _empty_nhwc(n, k, h2, w2, x.device)
-        if stats is not None and stats_fusable(n * h2 * w2, groups):
-            tiles = fwd_stat_tiles(n, h2, w2, 16, k, 4, 4, h2, w2, 1, 2, n * h2 * w2 // groups)
-            check(_run("conv_fwd", 2.0 * n * h2 * w2 * k * 147, lib.wm_conv2d_fwd_stats, ptr(xs), ptr(ws2d), y.data_ptr(),
-                       n, h2, w2, 16, k, 4, 4, h2, w2, 1, 2, ptr(stats.get(groups, tiles, xs.device)), tiles,
-                       n * h2 * w2 // groups, stream_ptr()), "wm_conv2d_fwd_stats(stem)")
-        else:
-            check(_run("conv_fwd", 2.0 * n * h2 * w2 * k * 147, lib.wm_conv2d_fwd, ptr(xs), ptr(ws2d), y.data_ptr(), n, h2,
-                       w2, 16, k, 4, 4, h2, w2, 1, 2, stream_ptr()), "wm_conv2d_fwd(stem)")
+        _conv_fwd(xs, ws2d, y, (n, h2, w2, 16, k, 4, 4, h2, w2, 1, 2), 2.0 * n * h2 * w2 * k * 147, stats, groups, "(stem)")
         ctx.save_for_backward(xs)
         ctx.weight = weight
         ctx.geom = (n, h2, w2, k)
@@ -845,17 +839,13 @@ class _StemConv(torch.autograd.Function):
         slot = _arena_grad(ctx.weight)
         if slot is not None and ctx.branch != 0:
             # a side branch must not add into the slot beside the main branch: its gradient goes into a buffer of its own and
-            # joins the pass's ordered fold as one flat row
-            tmp = _flat_fold_buffer(ctx.weight, k * 147, dy.device)
+            # joins the pass's ordered fold as one flat row.  (The main branch adds into the slot directly and queues nothing, so
+            # with one side branch this is the weight's use 0; a further side branch would get a buffer of its own.)
+            tmp = _use_buffer(ctx.weight, "_hip_flat_fold", k * 147, dy.device)
             check(lib.wm_stem_wgrad_finalize(ptr(slabs), ns, k, ptr(tmp), 0, stream_ptr()), "wm_stem_wgrad_finalize")
             _queue_fold(ctx.weight, tmp, 1, slot, 1, k * 147, 1)
-            return None, None, None, None
-        if slot is not None:
-            check(lib.wm_stem_wgrad_finalize(ptr(slabs), ns, k, ptr(slot), 1, stream_ptr()), "wm_stem_wgrad_finalize")
-            return None, None, None, None
-        dw = torch.empty((k, 3, 7, 7), dtype=torch.float32, device=dy.device)
-        check(lib.wm_stem_wgrad_finalize(ptr(slabs), ns, k, ptr(dw), 0, stream_ptr()), "wm_stem_wgrad_finalize")
-        return None, dw, None, None
+            return _pad_grads(ctx)
+        return _pad_grads(ctx, None, finalize_into(slabs, ns, k, 3, 7, 7, ctx.weight, (k, 3, 7, 7), stem=True))
 
 
 def stem_conv(x: torch.Tensor, weight: torch.Tensor, stats: Optional[torch.Tensor] = None, groups: int = 1) -> torch.Tensor:
@@ -901,17 +891,59 @@ def _as_act(x: torch.Tensor) -> torch.Tensor:
     return x.contiguous()
 
 
+def _bn_inputs(y, residual, what: str):
+    """Forward prologue of the BatchNorm Functions -> (y, residual, rows, C), activations in kernel layout."""
+    _need_cuda(y, what)
+    y = _as_act(y)
+    if residual is not None:
+        residual = _as_act(residual)
+        if residual.shape != y.shape:
+            raise ValueError(f"{what}: residual shape mismatch")
+    return (y, residual) + tuple(_rows_c(y))
+
+
+def _bn_save(ctx, y, out, mean, invstd, gamma, beta, relu, has_res) -> bool:
+    """Forward epilogue of the BatchNorm Functions: what the backward reads.  Returns mask_from_y: a ReLU'd BN without
+    residual recomputes its mask from y in the backward, so `out` is not kept."""
+    mask_from_y = relu and not has_res and gamma is not None and beta is not None
+    ctx.save_for_backward(y, out if (relu and not mask_from_y) else None, mean, invstd)
+    ctx.affine = (gamma, beta)
+    return mask_from_y
+
+
+def _bn_param_grads(gamma, beta, c: int, device, branch: int):
+    """Where a BatchNorm backward's (dgamma, dbeta) go -> (dgamma buffer, dbeta buffer, direct, finish):
+      * a fused optimiser owns both gradient slots: the kernel adds straight into them (direct = 1);
+      * the same on a side branch (`branch` != 0: the second view's pass on its own stream), which must not
+        read-modify-write the slots the main branch adds into at the same time: the sums are stored in persistent buffers
+        of their own and join the pass's ordered fold (pass branch = 0 where that route must not be taken);
+      * else new tensors, handed to autograd.
+    finish(), after the launch, queues the folds if needed and returns the pair for autograd (None, None unless new)."""
+    sg, sb = _arena_grad(gamma), _arena_grad(beta)
+    direct = sg is not None and sb is not None
+    via_fold = direct and branch != 0 and c % 4 == 0
+    if via_fold:
+        direct = False
+        both = _use_buffer(gamma, "_hip_bn_fold", 2 * c, device)
+        dgamma, dbeta = both[:c], both[c:]
+    else:
+        dgamma = sg if direct else torch.empty((c,), dtype=torch.float32, device=device)
+        dbeta = sb if direct else torch.empty((c,), dtype=torch.float32, device=device)
+
+    def finish():
+        if via_fold:
+            _queue_fold(gamma, dgamma, 1, sg, 1, c, 1)
+            _queue_fold(beta, dbeta, 1, sb, 1, c, 1)
+        return (None, None) if (direct or via_fold) else (dgamma, dbeta)
+
+    return dgamma, dbeta, direct, finish
+
+
 class _BatchNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, residual, gamma, beta, running_mean, running_var, training, groups, eps, momentum, relu,
                 stats=None, counter=None, bwd_stats=None):
-        _need_cuda(y, "batch_norm")
-        y = _as_act(y)
-        if residual is not None:
-            residual = _as_act(residual)
-            if residual.shape != y.shape:
-                raise ValueError("batch_norm: residual shape mismatch")
-        rows, c = _rows_c(y)
+        y, residual, rows, c = _bn_inputs(y, residual, "batch_norm")
         lib = _lib.load()
         out = torch.empty_like(y)
         ws = _bn_workspace(rows, c, groups if training else 1, y.device)
@@ -940,10 +972,7 @@ class _BatchNorm(torch.autograd.Function):
                                           ptr(beta), ptr(running_mean), ptr(running_var), ptr(counter), rows, c, groups, eps,
                                           momentum, int(relu), ptr(mean), ptr(invstd), out.data_ptr(), ptr(mask), ptr(ws),
                                           ws.numel(), stream_ptr()), "wm_bn_train_fwd")
-            # a ReLU'd BN without residual recomputes its mask from y in the backward: `out` is not needed
-            mask_from_y = relu and residual is None and gamma is not None and beta is not None
-            ctx.save_for_backward(y, out if (relu and not mask_from_y) else None, mean, invstd)
-            ctx.affine = (gamma, beta)
+            mask_from_y = _bn_save(ctx, y, out, mean, invstd, gamma, beta, relu, residual is not None)
             ctx.meta = (rows, c, groups, relu, residual is not None, mask_from_y)
             ctx.branch = current_branch()
             if will_link:
@@ -965,17 +994,7 @@ class _BatchNorm(torch.autograd.Function):
         dout = _as_act(dout)
         lib = _lib.load()
         dy = torch.empty_like(y)
-        sg, sb = _arena_grad(gamma), _arena_grad(beta)
-        direct = sg is not None and sb is not None
-        # a side branch (the second view's pass on its own stream) must not read-modify-write the gradient slots the main
-        # branch adds into at the same time: its sums go into their own buffers and join the pass's ordered fold
-        via_fold = direct and getattr(ctx, "branch", 0) != 0 and c % 4 == 0
-        if via_fold:
-            direct = False
-            dgamma, dbeta = _bn_fold_buffers(gamma, c, y.device)
-        else:
-            dgamma = sg if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
-            dbeta = sb if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
+        dgamma, dbeta, direct, finish = _bn_param_grads(gamma, beta, c, y.device, getattr(ctx, "branch", 0))
         ws = _bn_workspace(rows, c, groups, y.device)
         link = ctx.link
         fused = False
@@ -1002,13 +1021,7 @@ class _BatchNorm(torch.autograd.Function):
                                       int(mask_from_y), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), rows, c, groups,
                                       ptr(dgamma), ptr(dbeta), int(direct), dy.data_ptr(), dz.data_ptr() if has_res else 0,
                                       ptr(ws), ws.numel(), stream_ptr()), "wm_bn_train_bwd")
-        if via_fold:
-            _queue_fold(gamma, dgamma, 1, sg, 1, c, 1)
-            _queue_fold(beta, dbeta, 1, sb, 1, c, 1)
-            return (dy, dz) + (None,) * 12
-        if direct:
-            return (dy, dz) + (None,) * 12
-        return (dy, dz, dgamma, dbeta) + (None,) * 10
+        return _pad_grads(ctx, dy, dz, *finish())
 
 
 def batch_norm(y, gamma, beta, running_mean, running_var, training: bool, residual=None, relu: bool = False,
@@ -1043,13 +1056,7 @@ class _SyncBatchNorm(torch.autograd.Function):
                 group):
         import torch.distributed as dist
 
-        _need_cuda(y, "sync_batch_norm")
-        y = _as_act(y)
-        if residual is not None:
-            residual = _as_act(residual)
-            if residual.shape != y.shape:
-                raise ValueError("sync_batch_norm: residual shape mismatch")
-        rows, c = _rows_c(y)
+        y, residual, rows, c = _bn_inputs(y, residual, "sync_batch_norm")
         if rows % groups:
             raise ValueError("sync_batch_norm: rows not divisible by groups")
         lib = _lib.load()
@@ -1069,9 +1076,7 @@ class _SyncBatchNorm(torch.autograd.Function):
                                        ptr(running_mean), ptr(running_var), ptr(counter), rows, c, groups, count, eps,
                                        momentum, int(relu), ptr(mean), ptr(invstd), out.data_ptr(), ptr(sums), ptr(ws),
                                        ws.numel(), stream_ptr()), "wm_bn_sync_fwd_apply")
-        mask_from_y = relu and residual is None and gamma is not None and beta is not None
-        ctx.save_for_backward(y, out if (relu and not mask_from_y) else None, mean, invstd)
-        ctx.affine = (gamma, beta)
+        mask_from_y = _bn_save(ctx, y, out, mean, invstd, gamma, beta, relu, residual is not None)
         ctx.meta = (rows, c, groups, relu, residual is not None, mask_from_y, count, group)
         return out
 
@@ -1085,10 +1090,8 @@ class _SyncBatchNorm(torch.autograd.Function):
         dout = _as_act(dout)
         lib = _lib.load()
         dy = torch.empty_like(y)
-        sg, sb = _arena_grad(gamma), _arena_grad(beta)
-        direct = sg is not None and sb is not None
-        dgamma = sg if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
-        dbeta = sb if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
+        # (branch 0: this Function never takes the fold route of a side branch)
+        dgamma, dbeta, direct, finish = _bn_param_grads(gamma, beta, c, y.device, 0)
         ws = _bn_workspace(rows, c, groups, y.device)
         sums = torch.empty((groups, 2, c), dtype=torch.float32, device=y.device)
         mask = out.data_ptr() if (relu and not mask_from_y) else 0
@@ -1101,9 +1104,7 @@ class _SyncBatchNorm(torch.autograd.Function):
                                        ptr(mean), ptr(invstd), rows, c, groups, count, ptr(sums), dy.data_ptr(),
                                        dz.data_ptr() if has_res else 0, ptr(ws), ws.numel(), stream_ptr()),
               "wm_bn_sync_bwd_apply")
-        if direct:
-            return (dy, dz) + (None,) * 11
-        return (dy, dz, dgamma, dbeta) + (None,) * 9
+        return _pad_grads(ctx, dy, dz, *finish())
 
 
 def sync_batch_norm(y, gamma, beta, running_mean, running_var, residual=None, relu: bool = False, eps: float = 1e-5,
@@ -1172,27 +1173,13 @@ class _BnReluMaxPool(torch.autograd.Function):
         lib = _lib.load()
         dpooled = _as_nhwc(dpooled)
         dy = torch.empty_like(y)
-        sg, sb = _arena_grad(gamma), _arena_grad(beta)
-        direct = sg is not None and sb is not None
-        via_fold = direct and getattr(ctx, "branch", 0) != 0 and c % 4 == 0   # (as _BatchNorm.backward)
-        if via_fold:
-            direct = False
-            dgamma, dbeta = _bn_fold_buffers(gamma, c, y.device)
-        else:
-            dgamma = sg if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
-            dbeta = sb if direct else torch.empty((c,), dtype=torch.float32, device=y.device)
+        dgamma, dbeta, direct, finish = _bn_param_grads(gamma, beta, c, y.device, getattr(ctx, "branch", 0))
         ws = _bn_workspace(rows, c, g, y.device)
         # the pooled gradient is scattered back inside the two BN backward passes (no 112x112 dout tensor)
         check(lib.wm_bn_relu_maxpool_bwd(y.data_ptr(), ptr(ctx.ysel), dpooled.data_ptr(), ptr(ctx.idx), n, h, w, c, ptr(gamma), ptr(beta),
                                          ptr(mean), ptr(invstd), g, ptr(dgamma), ptr(dbeta), int(direct), dy.data_ptr(),
                                          ptr(ws), ws.numel(), stream_ptr()), "wm_bn_relu_maxpool_bwd")
-        if via_fold:
-            _queue_fold(gamma, dgamma, 1, sg, 1, c, 1)
-            _queue_fold(beta, dbeta, 1, sb, 1, c, 1)
-            return dy, None, None, None, None, None, None, None, None, None, None
-        if direct:
-            return dy, None, None, None, None, None, None, None, None, None, None
-        return dy, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return _pad_grads(ctx, dy, *finish())
 
 
 def bn_relu_maxpool(y, gamma, beta, running_mean, running_var, training: bool, eps: float = 1e-5,

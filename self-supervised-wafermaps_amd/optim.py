@@ -74,12 +74,34 @@ class _HyperUpload:
 
 
 class _ArenaStateMixin:
-    """state_dict / load_state_dict in torch.optim's own format (state[i]["momentum_buffer"] for SGD / LARS,
+    """What the arena optimisers share: the gradient arenas, zero_grad, the frame of step(), and
+    state_dict / load_state_dict in torch.optim's own format (state[i]["momentum_buffer"] for SGD / LARS,
     state[i]["step" | "exp_avg" | "exp_avg_sq"] for Adam(W)), so that a run resumes with its momentum, moments
     and bias-correction counters and a torch.optim checkpoint of the same parameter list loads here.  The
     tensors live in the flat arenas; torch's `self.state` stays empty."""
 
     _STATE_KEYS = ("momentum_buffer",)   # arena attribute order: momentum[, second]
+
+    @property
+    def grad_arenas(self) -> List[torch.Tensor]:
+        """Flat gradient buffers (one per param group): what data-parallel training all-reduces."""
+        return [a.grads for a in self._arenas]
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        ops.drop_pending_folds()  # (a backward pass that raised leaves its queue behind: ADVICE r2)
+        for a in self._arenas:
+            check(_lib.load().wm_fill_zero(ptr(a.grads), a.grads.numel() * 4, stream_ptr()), "wm_fill_zero")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One update of every parameter group: the optimiser's own `_update()` (hyper-parameter upload + kernel launch per
+        group) between what all of them share."""
+        loss = closure() if closure is not None else None
+        ops.fold_wgrads()  # no-op unless a backward pass ended without its end-of-pass callback
+        self._update()
+        ops.bump_weight_epoch()
+        ops.refresh_layouts(p for g in self.param_groups for p in g["params"])  # bf16 kernel layouts: one launch
+        return loss
 
     def _param_slices(self):
         """(packed torch index, arena, offset, parameter) for every parameter that owns an arena slot."""
@@ -150,20 +172,7 @@ class SGD(_ArenaStateMixin, torch.optim.Optimizer):
         self._upload = _HyperUpload(4)
         ops.bump_weight_epoch()
 
-    @property
-    def grad_arenas(self) -> List[torch.Tensor]:
-        """Flat gradient buffers (one per param group): what data-parallel training all-reduces."""
-        return [a.grads for a in self._arenas]
-
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        ops.drop_pending_folds()  # (a backward pass that raised leaves its queue behind: ADVICE r2)
-        for a in self._arenas:
-            check(_lib.load().wm_fill_zero(ptr(a.grads), a.grads.numel() * 4, stream_ptr()), "wm_fill_zero")
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        ops.fold_wgrads()  # no-op unless a backward pass ended without its end-of-pass callback
+    def _update(self) -> None:
         lib = _lib.load()
         for group, arena, hyper, i in zip(self.param_groups, self._arenas, self._hyper, range(len(self._arenas))):
             h = (float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), self.grad_scale)
@@ -172,9 +181,6 @@ class SGD(_ArenaStateMixin, torch.optim.Optimizer):
                 self._hyper_host[i] = h
             check(lib.wm_sgd_step(ptr(arena.params), ptr(arena.grads), ptr(arena.momentum), arena.numel, ptr(hyper),
                                   stream_ptr()), "wm_sgd_step")
-        ops.bump_weight_epoch()
-        ops.refresh_layouts(p for g in self.param_groups for p in g["params"])  # bf16 kernel layouts: one launch
-        return loss
 
 
 class AdamW(_ArenaStateMixin, torch.optim.Optimizer):
@@ -201,19 +207,7 @@ class AdamW(_ArenaStateMixin, torch.optim.Optimizer):
         self._upload = _HyperUpload(9)
         ops.bump_weight_epoch()
 
-    @property
-    def grad_arenas(self) -> List[torch.Tensor]:
-        return [a.grads for a in self._arenas]
-
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        ops.drop_pending_folds()  # (a backward pass that raised leaves its queue behind: ADVICE r2)
-        for a in self._arenas:
-            check(_lib.load().wm_fill_zero(ptr(a.grads), a.grads.numel() * 4, stream_ptr()), "wm_fill_zero")
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        ops.fold_wgrads()  # no-op unless a backward pass ended without its end-of-pass callback
+    def _update(self) -> None:
         lib = _lib.load()
         for i, (group, arena, hyper) in enumerate(zip(self.param_groups, self._arenas, self._hyper)):
             self._steps[i] += 1
@@ -224,9 +218,6 @@ class AdamW(_ArenaStateMixin, torch.optim.Optimizer):
             self._upload(hyper, h)
             check(lib.wm_adamw_step(ptr(arena.params), ptr(arena.grads), ptr(arena.momentum), ptr(arena.second),
                                     arena.numel, ptr(hyper), stream_ptr()), "wm_adamw_step")
-        ops.bump_weight_epoch()
-        ops.refresh_layouts(p for g in self.param_groups for p in g["params"])  # bf16 kernel layouts: one launch
-        return loss
 
 
 class LARS(_ArenaStateMixin, torch.optim.Optimizer):
@@ -256,19 +247,7 @@ class LARS(_ArenaStateMixin, torch.optim.Optimizer):
         self._upload = _HyperUpload(6)
         ops.bump_weight_epoch()
 
-    @property
-    def grad_arenas(self) -> List[torch.Tensor]:
-        return [a.grads for a in self._arenas]
-
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        ops.drop_pending_folds()  # (a backward pass that raised leaves its queue behind: ADVICE r2)
-        for a in self._arenas:
-            check(_lib.load().wm_fill_zero(ptr(a.grads), a.grads.numel() * 4, stream_ptr()), "wm_fill_zero")
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        ops.fold_wgrads()  # no-op unless a backward pass ended without its end-of-pass callback
+    def _update(self) -> None:
         lib = _lib.load()
         for group, arena, hyper, (seg, n), norms in zip(self.param_groups, self._arenas, self._hyper, self._seg,
                                                         self._norms):
@@ -278,9 +257,6 @@ class LARS(_ArenaStateMixin, torch.optim.Optimizer):
             # segments are (begin, end) pairs: 2n entries = n "segments" of stride 2 -> pass as 2n-1 boundaries
             check(lib.wm_lars_step(ptr(arena.params), ptr(arena.grads), ptr(arena.momentum), ptr(seg), 2 * n - 1,
                                    ptr(hyper), ptr(norms), stream_ptr()), "wm_lars_step")
-        ops.bump_weight_epoch()
-        ops.refresh_layouts(p for g in self.param_groups for p in g["params"])  # bf16 kernel layouts: one launch
-        return loss
 
 
 class Adam(AdamW):

@@ -66,19 +66,10 @@ def _grad_target(p: torch.Tensor):
     return g, g
 
 
-def _part_buffer(owner: torch.Tensor, attr: str, numel: int, device) -> torch.Tensor:
-    """A persistent f32 slot buffer of `owner` (one per use of the parameter inside one backward pass)."""
-    idx = getattr(owner, "_hip_pending", 0)
-    bufs = getattr(owner, attr, None)
-    if bufs is None:
-        bufs = []
-        setattr(owner, attr, bufs)
-    while len(bufs) <= idx:
-        bufs.append(None)
-    part = bufs[idx]
-    if part is None or part.numel() != numel or part.device != device:
-        part = bufs[idx] = torch.empty(numel, dtype=torch.float32, device=device)
-    return part
+def _slot_parts() -> bool:
+    """Column sums of LayerNorm / bias gradients as per-block slots for the ordered fold (WM_LN_SLOTS=0: the atomic form);
+    read per call."""
+    return os.environ.get("WM_LN_SLOTS", "1") != "0"
 
 
 def _ln_backward(x, dy, gamma, beta, mean, rstd, dskip):
@@ -90,9 +81,9 @@ def _ln_backward(x, dy, gamma, beta, mean, rstd, dskip):
     lib = _lib.load()
     dx = torch.empty_like(x)
     sg, sb = _arena_grad(gamma), _arena_grad(beta)
-    if sg is not None and sb is not None and c % 4 == 0 and os.environ.get("WM_LN_SLOTS", "1") != "0":
+    if sg is not None and sb is not None and c % 4 == 0 and _slot_parts():
         nb = int(lib.wm_layernorm_bwd_blocks(rows, c))
-        part = _part_buffer(gamma, "_hip_ln_parts", 2 * nb * c, x.device)   # (applied twice in one pass: two buffers)
+        part = ops._use_buffer(gamma, "_hip_ln_parts", 2 * nb * c, x.device)   # (applied twice in one pass: two buffers)
         check(lib.wm_layernorm_bwd_parts(ptr(x), ptr(dy), ptr(gamma), ptr(mean), ptr(rstd), rows, c,
                                          ptr(dskip) if dskip is not None else 0, ptr(dx), ptr(part), stream_ptr()),
               "wm_layernorm_bwd_parts")
@@ -208,10 +199,10 @@ class _BiasAct(torch.autograd.Function):
         db = db_ret = None
         lib = _lib.load()
         slot = _arena_grad(bias) if (bias is not None and bias.requires_grad) else None
-        if slot is not None and c % 4 == 0 and os.environ.get("WM_LN_SLOTS", "1") != "0":
+        if slot is not None and c % 4 == 0 and _slot_parts():
             # bias gradient as per-block slots added in order by the pass's batched fold (no f32 atomics)
             nb = int(lib.wm_colsum_blocks(rows, c))
-            part = _part_buffer(bias, "_hip_bias_parts", nb * c, dout.device)
+            part = ops._use_buffer(bias, "_hip_bias_parts", nb * c, dout.device)
             dx = dout if ctx.act == ACT_NONE else torch.empty_like(dout)
             check(lib.wm_bias_act_bwd_parts(ptr(x) if ctx.act != ACT_NONE else 0, ptr(bias) if ctx.act != ACT_NONE else 0,
                                             ptr(dout), ctx.act, rows, c, ptr(dx) if ctx.act != ACT_NONE else 0, ptr(part),
@@ -335,10 +326,8 @@ class _ConstMatmul(torch.autograd.Function):
         # dp [K, N] = m^T [K, M] @ dout [M, N]: op(a) = a^T with a = m stored [M][K]
         check(_lib.load().wm_matmul_f32(ptr(m), ptr(dout), ptr(dp), m.shape[1], dout.shape[1], m.shape[0], 1, stream_ptr()),
               "wm_matmul_f32")
-        slot = _arena_grad(p) if p.is_leaf else None
-        if slot is not None:
-            check(_lib.load().wm_wgrad_finalize(ptr(dp), 1, 1, dp.numel(), 1, 1, ptr(slot), 1, stream_ptr()), "wm_wgrad_finalize(add)")
-            return None, None
+        if p.is_leaf and _arena_grad(p) is not None:
+            return None, ops.finalize_into(dp, 1, 1, dp.numel(), 1, 1, p, None)   # (one "slab": the library's add into the slot)
         return None, dp.reshape(p.shape)
 
 
@@ -620,16 +609,10 @@ class _PatchEmbed(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[1]:
             dy = _bf16_rows(dy)
-            lib = _lib.load()
             # rows [m][k = p*p*3] x dy [m][d] as a 1 x 1 convolution; the slabs are [d][p][p][3] = KRSC of the patch filter
             slabs, _, ns = ops.wgrad(dy, rows, weight, m, 1, 1, k, d, 1, 1, 1, 1, 1, 0, name="gemm_wgrad")
             ops.side_join()   # the finalize below reads the slabs on this stream
-            slot = _arena_grad(weight)
-            if slot is not None:
-                check(lib.wm_wgrad_finalize(ptr(slabs), ns, d, 3, p, p, ptr(slot), 1, stream_ptr()), "wm_wgrad_finalize")
-            else:
-                dw = torch.empty((d, 3, p, p), dtype=torch.float32, device=dy.device)
-                check(lib.wm_wgrad_finalize(ptr(slabs), ns, d, 3, p, p, ptr(dw), 0, stream_ptr()), "wm_wgrad_finalize")
+            dw = ops.finalize_into(slabs, ns, d, 3, p, p, weight, (d, 3, p, p))
         return None, dw
 
 
@@ -657,11 +640,10 @@ def _tokens_assemble_bwd(dx, cls_p, pos_p, n, np_, d):
     s = np_ + 1
     lib = _lib.load()
     # sum over the images of the [s * d] token rows: per-block slots added in order (no f32 atomics)
-    dpos = torch.empty(s * d, dtype=torch.float32, device=dx.device)
     nb = int(lib.wm_colsum_blocks(n, s * d))
     part = torch.empty(nb * s * d, dtype=torch.float32, device=dx.device)
     check(lib.wm_bias_act_bwd_parts(0, 0, ptr(dx), ACT_NONE, n, s * d, 0, ptr(part), stream_ptr()), "wm_bias_act_bwd_parts")
-    check(lib.wm_wgrad_finalize(ptr(part), nb, 1, s * d, 1, 1, ptr(dpos), 0, stream_ptr()), "wm_wgrad_finalize")
+    dpos = ops.finalize_into(part, nb, 1, s * d, 1, 1, None, (s * d,))
     # the patch rows (every token but the class token of each image) by the row-gather kernel: a strided slice +
     # reshape would be an ATen copy kernel
     idx = cached_index(("patch_rows", n, np_, str(dx.device)),
@@ -669,14 +651,10 @@ def _tokens_assemble_bwd(dx, cls_p, pos_p, n, np_, d):
     dpatch = torch.empty((n * np_, d), dtype=torch.bfloat16, device=dx.device)
     check(lib.wm_gather_rows(ptr(dx), ptr(idx), n, s, np_, d, ptr(dpatch), stream_ptr()), "wm_gather_rows")
     dcls, dposr = dpos[:d].reshape(cls_p.shape), dpos.reshape(pos_p.shape)
-    sc = _arena_grad(cls_p) if cls_p.is_leaf else None
-    sp = _arena_grad(pos_p) if pos_p.is_leaf else None
-    if sc is not None:
-        check(lib.wm_wgrad_finalize(ptr(dpos), 1, 1, d, 1, 1, ptr(sc), 1, stream_ptr()), "wm_wgrad_finalize(add cls)")
-        dcls = None
-    if sp is not None:
-        check(lib.wm_wgrad_finalize(ptr(dpos), 1, 1, s * d, 1, 1, ptr(sp), 1, stream_ptr()), "wm_wgrad_finalize(add pos)")
-        dposr = None
+    if cls_p.is_leaf and _arena_grad(cls_p) is not None:    # (dpos as one "slab": the library's add into the slot)
+        dcls = ops.finalize_into(dpos, 1, 1, d, 1, 1, cls_p, None)
+    if pos_p.is_leaf and _arena_grad(pos_p) is not None:
+        dposr = ops.finalize_into(dpos, 1, 1, s * d, 1, 1, pos_p, None)
     return dpatch, dcls, dposr
 
 

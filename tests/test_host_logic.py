@@ -294,6 +294,30 @@ def test_fold_plan_merges_the_second_branch_and_orders_everything_else():
     assert both == [[(0, 0, 11, 10, 1, 8, 8, 1, 4), (0, 0, 21, 20, 2, 8, 8, 1, 4)]]
 
 
+def test_use_buffer_is_stable_per_use_and_reallocates_one_slot_only():
+    """ops._use_buffer (the persistent per-use scratch of a parameter; owners here are plain CPU tensors): the same owner,
+    attribute, use index and size give the same storage; another use index (`_hip_pending`) a different buffer; a changed
+    size reallocates that slot and leaves the other use's buffer alone; attributes do not share buffers."""
+    from ssl_wafermap_amd import ops
+
+    cpu = torch.device("cpu")
+    w = torch.zeros(4, dtype=torch.float32)
+    a = ops._use_buffer(w, "_hip_ln_parts", 24, cpu)
+    assert a.dtype == torch.float32 and a.numel() == 24 and a.device == cpu
+    assert ops._use_buffer(w, "_hip_ln_parts", 24, cpu).data_ptr() == a.data_ptr()
+    w._hip_pending = 1
+    b = ops._use_buffer(w, "_hip_ln_parts", 24, cpu)
+    assert b.data_ptr() != a.data_ptr()
+    assert ops._use_buffer(w, "_hip_ln_parts", 24, cpu).data_ptr() == b.data_ptr()
+    b2 = ops._use_buffer(w, "_hip_ln_parts", 40, cpu)   # (b stays referenced here: its address cannot be recycled for b2)
+    assert b2.numel() == 40 and b2.data_ptr() != b.data_ptr()
+    w._hip_pending = 0
+    assert ops._use_buffer(w, "_hip_ln_parts", 24, cpu).data_ptr() == a.data_ptr()
+    assert len(w._hip_ln_parts) == 2 and not hasattr(w, "_hip_ln_parts_retired")   # nothing was captured: nothing retired
+    other = ops._use_buffer(w, "_hip_bias_parts", 24, cpu)
+    assert other.data_ptr() != a.data_ptr() and ops._use_buffer(torch.zeros(4), "_hip_ln_parts", 24, cpu).data_ptr() != a.data_ptr()
+
+
 def test_view_branches_and_parallel_branch_switches_fail_loudly_without_a_gpu():
     """nn.ViewBranches is GPU state (a side stream, flat device buffers): a CPU model keeps the single-stream path, and the
     ResNet-18 backbone's branch test is False off the GPU (no silent CPU emulation of the branches)."""
