@@ -746,6 +746,31 @@ int wm_attention_mass_mask(const float* attn, long long rows, int n, long long l
  * with lambda1 = 0 gives zeros.  cam float32 [N][out_h][out_w], out_h, out_w <= 4096. */
 int wm_eigencam(const void* act, int dtype, int N, int C, int H, int W, int out_h, int out_w, float* cam, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Embedding clustering (notebooks/3.1-Embeddings-clustering.ipynb, 3.2-Embeddings-SSL-categories.ipynb: HDBSCAN on the
+ * dumped embeddings, scored by silhouette).  x float32 [n][d] row-major, 16-byte aligned, d % 4 == 0, d <= 1024.
+ * metric 0: Euclidean sqrt(sum (a_k - b_k)^2); 1: Manhattan sum |a_k - b_k| -- accumulated in float32 in index order from
+ * the differences themselves, so dist(i, j) and dist(j, i) are the same bits, equal rows are at distance exactly 0 and
+ * the relative error is at most (d + 3) * 2^-24 (csrc/cluster.hip).  No atomics: two calls give the same bits.
+ *
+ * wm_core_distance: out[i] = k-th smallest of dist(i, j) over all rows j, i itself included (so k = 1 gives 0:
+ * sklearn.cluster.HDBSCAN's min_samples convention).  1 <= k <= 64, k <= n. */
+size_t wm_core_distance_workspace_bytes(int n, int d, int k);
+int wm_core_distance(const float* x, int n, int d, int metric, int k, float* out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* One Boruvka round on the mutual-reachability graph w_ij = max(core[i], core[j], dist(i, j) * inv_alpha): for every row
+ * i the smallest w_ij over the rows j with comp[j] != comp[i] (comp: int32 component id per row) and that j; equal
+ * weights resolve to the lowest j.  A row whose component holds every row gets out_j = -1, out_w = +inf. */
+size_t wm_mreach_min_edge_workspace_bytes(int n, int d);
+int wm_mreach_min_edge(const float* x, const float* core, const int32_t* comp, int n, int d, int metric, float inv_alpha,
+                       float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream);
+/* out[i][c] = sum over the rows j with labels[j] == c of dist(i, j) (sklearn.metrics.silhouette_samples' reduction):
+ * float32 distances added in double in column order.  labels int32 in [-1, n_clusters); rows labelled -1 contribute
+ * nowhere and their own output rows are unspecified.  2 <= n_clusters <= n; out double [n][n_clusters].  Fastest when
+ * equal labels are adjacent (one running sum per cluster and row). */
+int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, int metric, int n_clusters, double* out,
+                         void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -1,0 +1,205 @@
+#!/usr/bin/env python3
+"""HDBSCAN hyper-parameter sweep on dumped embeddings on MI355X: the flow of the reference's
+notebooks/3.1-Embeddings-clustering.ipynb and 3.2-Embeddings-SSL-categories.ipynb on the HIP path
+(ssl_wafermap_amd.cluster).
+
+    python scripts/embedding_clustering_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
+                                               [--trials 30] [--design random|grid] [--seed 0] [--rows N]
+                                               [--metrics euclidean manhattan] [--no-scale] [--out DIR]
+
+What the notebooks do, and where it is here:
+  StandardScaler().fit_transform(embeddings)              -> retrieval.StandardScaler (skipped with --no-scale)
+  Ax search, 30 trials, over min_samples 1-60, min_cluster_size 10-100, cluster_selection_epsilon 0.1-1.5, metric
+                                                          -> a seeded random set or grid of --trials points over the
+                                                             same ranges (no Bayesian model); the trials draw their
+                                                             (metric, min_samples) from a few values, and one
+                                                             spanning tree serves all trials that share the pair
+  hdbscan.HDBSCAN(...).fit(data)                          -> cluster.HDBSCAN.fit / .refit
+  homogeneity / silhouette / calinski_harabasz / davies_bouldin on the non-noise rows
+                                                          -> cluster.homogeneity_score, silhouette_score, ...
+  get_pareto_optimal_parameters()                         -> the non-dominated rows of the table (silhouette,
+                                                             calinski_harabasz, homogeneity up; davies_bouldin
+                                                             down; and, beyond the notebooks' four scores,
+                                                             n_noise down)
+  nearest wafers of a member of each cluster              -> retrieval.nearest_neighbors (5 neighbours, L2)
+UMAP / DensMAP only draw the notebooks' 2-D pictures and are not part of this script; pass a reduced matrix as
+--embeddings to cluster one.  `min_samples` counts the point itself (sklearn's convention; the `hdbscan` package's
+generic path counts one neighbour more).  The canberra and braycurtis metrics of the notebook's search space have
+no kernel and are refused.
+
+Outputs under --out: trials.csv (parameters, n_clusters, n_noise, the four scores), pareto.csv, labels.npy (the
+chosen trial: the Pareto row with the best silhouette), summary.json.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+RANGES = {"min_samples": (1, 60), "min_cluster_size": (10, 100), "cluster_selection_epsilon": (0.1, 1.5)}
+COLUMNS = ["trial", "metric", "min_samples", "min_cluster_size", "cluster_selection_epsilon", "n_clusters", "n_noise",
+           "homogeneity", "silhouette", "calinski_harabasz", "davies_bouldin"]
+# (column, +1 when larger is better)
+OBJECTIVES = [("silhouette", 1), ("calinski_harabasz", 1), ("homogeneity", 1), ("davies_bouldin", -1), ("n_noise", -1)]
+
+
+def load_embeddings(path):
+    """(embeddings float32 [n, d], labels int [n]) from an .npz with `embeddings` / `labels` or a reference
+    *_preds_*.pkl.xz (a DataFrame with the feature columns 0..d-1 and failureCode)."""
+    path = Path(path)
+    if path.suffix == ".npz":
+        z = np.load(path)
+        return z["embeddings"].astype(np.float32), np.asarray(z["labels"]).astype(np.int64)
+    import pandas as pd
+
+    df = pd.read_pickle(path)
+    cols = [c for c in df.columns if isinstance(c, (int, np.integer))]
+    return df[cols].to_numpy().astype(np.float32), df["failureCode"].to_numpy().astype(np.int64)
+
+
+def design_trials(trials: int, design: str, seed: int, metrics, max_samples: int):
+    """`trials` parameter points.  The (metric, min_samples) pairs come from a pool of about trials / 3 distinct
+    values, so that several trials share one spanning tree."""
+    rng = np.random.default_rng(seed)
+    lo, hi = RANGES["min_samples"]
+    hi = min(hi, max_samples)
+    n_pairs = max(1, min(-(-trials // 3), (hi - lo + 1) * len(metrics)))
+    if design == "grid":
+        ms = np.unique(np.linspace(lo, hi, -(-n_pairs // len(metrics))).round().astype(int))
+        pairs = [(m, int(s)) for s in ms for m in metrics][:n_pairs]
+    else:
+        pairs = []
+        while len(pairs) < n_pairs:
+            cand = (metrics[int(rng.integers(len(metrics)))], int(rng.integers(lo, hi + 1)))
+            if cand not in pairs:
+                pairs.append(cand)
+    out = []
+    per = -(-trials // len(pairs))
+    for t in range(trials):
+        metric, ms = pairs[t // per] if design == "grid" else pairs[t % len(pairs)]
+        if design == "grid":
+            side = max(1, int(np.ceil(np.sqrt(per))))
+            a, b = divmod(t % per, side)
+            mcs = int(round(np.linspace(*RANGES["min_cluster_size"], side)[a % side]))
+            eps = float(np.linspace(*RANGES["cluster_selection_epsilon"], side)[b])
+        else:
+            mcs = int(rng.integers(RANGES["min_cluster_size"][0], RANGES["min_cluster_size"][1] + 1))
+            eps = float(rng.uniform(*RANGES["cluster_selection_epsilon"]))
+        out.append({"metric": metric, "min_samples": ms, "min_cluster_size": mcs, "cluster_selection_epsilon": eps})
+    return out
+
+
+def pareto_rows(rows):
+    """Indices of the rows no other row dominates on OBJECTIVES (rows without finite scores never qualify)."""
+    vals = np.array([[s * float(r[c]) for c, s in OBJECTIVES] for r in rows], dtype=np.float64)
+    ok = np.isfinite(vals).all(axis=1)
+    keep = []
+    for i in np.flatnonzero(ok):
+        dominated = any(j != i and (vals[j] >= vals[i]).all() and (vals[j] > vals[i]).any() for j in np.flatnonzero(ok))
+        if not dominated:
+            keep.append(int(i))
+    return keep
+
+
+def score_trial(x, truth, labels, metric):
+    from ssl_wafermap_amd import cluster
+
+    import torch
+
+    n_clusters, n_noise = int(labels.max()) + 1, int((labels == -1).sum())
+    row = {"n_clusters": n_clusters, "n_noise": n_noise, "homogeneity": float("nan"), "silhouette": float("nan"),
+           "calinski_harabasz": float("nan"), "davies_bouldin": float("nan")}
+    keep = labels != -1
+    if n_clusters >= 2:  # the scores are defined for 2 <= n_clusters <= n_kept - 1
+        xs = x[torch.from_numpy(np.flatnonzero(keep)).to(x.device)].contiguous()
+        row["homogeneity"] = cluster.homogeneity_score(truth[keep], labels[keep])
+        row["silhouette"] = cluster.silhouette_score(xs, labels[keep], metric)
+        row["calinski_harabasz"] = cluster.calinski_harabasz_score(xs, labels[keep])
+        row["davies_bouldin"] = cluster.davies_bouldin_score(xs, labels[keep])
+    return row
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--embeddings", required=True)
+    ap.add_argument("--trials", type=int, default=30)
+    ap.add_argument("--design", choices=["random", "grid"], default="random")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--rows", type=int, default=0, help="use the first N rows only")
+    ap.add_argument("--metrics", nargs="+", default=["euclidean", "manhattan"])
+    ap.add_argument("--no-scale", action="store_true")
+    ap.add_argument("--out", default="clustering_out")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+
+    import torch
+
+    from ssl_wafermap_amd import cluster
+    from ssl_wafermap_amd.retrieval import StandardScaler, nearest_neighbors
+
+    for m in a.metrics:
+        cluster.metric_code(m)  # canberra / braycurtis: NotImplementedError naming the metric
+    emb, truth = load_embeddings(a.embeddings)
+    if a.rows:
+        emb, truth = emb[:a.rows], truth[:a.rows]
+    x = torch.from_numpy(emb).to(a.device)
+    if not a.no_scale:
+        x = StandardScaler().fit_transform(x)
+    out = Path(a.out)
+    out.mkdir(parents=True, exist_ok=True)
+
+    trials = design_trials(a.trials, a.design, a.seed, list(a.metrics), min(64, x.shape[0]))
+    trees, rows, all_labels = {}, [], []
+    t0 = time.perf_counter()
+    for t, p in enumerate(trials):
+        key = (p["metric"], p["min_samples"])
+        if key not in trees:
+            trees[key] = cluster.HDBSCAN(min_cluster_size=p["min_cluster_size"], min_samples=p["min_samples"],
+                                         metric=p["metric"]).fit(x)
+        model = trees[key].refit(min_cluster_size=p["min_cluster_size"],
+                                 cluster_selection_epsilon=p["cluster_selection_epsilon"])
+        labels = model.labels_.copy()
+        all_labels.append(labels)
+        rows.append({"trial": t, **p, **score_trial(x, truth, labels, p["metric"])})
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+
+    with open(out / "trials.csv", "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=COLUMNS)
+        wr.writeheader()
+        wr.writerows(rows)
+    front = pareto_rows(rows)
+    with open(out / "pareto.csv", "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=COLUMNS)
+        wr.writeheader()
+        wr.writerows(rows[i] for i in front)
+    chosen = max(front, key=lambda i: rows[i]["silhouette"]) if front else None
+    summary = {"n": int(x.shape[0]), "d": int(x.shape[1]), "trials": len(rows), "n_trees": len(trees),
+               "sweep_seconds": wall, "pareto": front, "chosen": chosen}
+    if chosen is not None:
+        labels = all_labels[chosen]
+        np.save(out / "labels.npy", labels)
+        print(f"chosen trial {chosen}: {rows[chosen]}")
+        members = [int(np.flatnonzero(labels == c)[0]) for c in range(int(labels.max()) + 1)]
+        q = x[torch.tensor(members, device=x.device)].contiguous()
+        dist, idx = nearest_neighbors(q, x, min(6, x.shape[0]), metric="l2")
+        for c, (m, dr, ir) in enumerate(zip(members, dist.cpu().tolist(), idx.cpu().tolist())):
+            near = [(j, round(dd, 4), int(truth[j])) for j, dd in zip(ir, dr) if j != m][:5]
+            print(f"cluster {c}: member {m} (failure code {int(truth[m])}); nearest (row, L2, failure code): {near}")
+    (out / "summary.json").write_text(json.dumps(summary, indent=1))
+    print(f"{len(rows)} trials on {x.shape[0]} x {x.shape[1]} in {wall:.2f} s with {len(trees)} spanning trees; "
+          f"{len(front)} Pareto-optimal rows -> {out}")
+    return summary
+
+
+if __name__ == "__main__":
+    main()

@@ -280,6 +280,13 @@ SIGNATURES = {
     "wm_attention_probs": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "wm_attention_mass_mask": (c_int, [c_void_p, c_longlong, c_int, c_longlong, c_double, c_void_p, c_void_p]),
     "wm_eigencam": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # ---- embedding clustering
+    "wm_core_distance_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_core_distance": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_mreach_min_edge_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_mreach_min_edge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
+    "wm_cluster_dist_sums": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

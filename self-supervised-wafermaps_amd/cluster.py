@@ -1,0 +1,569 @@
+"""HDBSCAN clustering and cluster scores for dumped embeddings.
+
+The reference's flow (notebooks/3.1-Embeddings-clustering.ipynb, 3.2-Embeddings-SSL-categories.ipynb): HDBSCAN on
+the embedding matrix inside a hyper-parameter search over `min_cluster_size`, `min_samples`,
+`cluster_selection_epsilon` and `metric`, every trial scored with homogeneity, silhouette, Calinski-Harabasz and
+Davies-Bouldin.
+
+Here the O(N^2 D) parts are HIP kernels (csrc/cluster.hip): the core distances, the Boruvka rounds of the
+mutual-reachability spanning tree and the all-pairs pass of the silhouette.  The spanning tree depends on
+`(metric, min_samples, alpha)` only, so `HDBSCAN.refit` / `labels_from_mst` serve every
+`(min_cluster_size, cluster_selection_epsilon)` trial that shares them without touching the GPU again.
+
+What runs on the host, in numpy float64, and why: the per-component minimum and the union-find between Boruvka rounds
+(at most ceil(log2 n) rounds of O(n) work), and everything from the sorted tree edges to the labels (single-linkage
+tree, condensed tree, stabilities, selection: O(n log n) pointer chasing with no arithmetic to speak of).
+
+Semantics follow `sklearn.cluster.HDBSCAN`: `min_samples` counts the point itself (the core distance is the
+`min_samples`-th smallest distance with the zero self-distance as the first), which is one neighbour fewer than the
+generic path of the `hdbscan` package uses for the same number.  `alpha` divides the pairwise distance inside the
+mutual reachability, max(core_i, core_j, dist_ij / alpha), with the core distances unscaled.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, ptr, require_gpu, stream_ptr
+
+METRICS = {"euclidean": 0, "l2": 0, "manhattan": 1, "l1": 1, "cityblock": 1}
+_LISTED_NOT_BUILT = ("canberra", "braycurtis")  # in the notebook's search space; no kernel here
+
+CONDENSED_DTYPE = np.dtype([("parent", np.intp), ("child", np.intp), ("lambda_val", np.float64), ("child_size", np.intp)])
+
+
+def metric_code(metric: str) -> int:
+    """The kernels' code of a metric name (0 Euclidean, 1 Manhattan).  A metric the notebook lists but no kernel
+    computes raises NotImplementedError naming it; any other unknown name raises ValueError."""
+    if metric in _LISTED_NOT_BUILT:
+        raise NotImplementedError(f"metric {metric!r} is not implemented (available: euclidean, manhattan)")
+    if metric not in METRICS:
+        raise ValueError(f"unknown metric {metric!r} (available: euclidean, manhattan)")
+    return METRICS[metric]
+
+
+def _prep(x):
+    import torch
+
+    require_gpu(x)
+    if x.dim() != 2:
+        raise ValueError("expected [n_samples, n_features]")
+    x = x.float()
+    if x.shape[1] % 4:
+        x = torch.nn.functional.pad(x, (0, 4 - x.shape[1] % 4))  # zero columns change no distance
+    if x.shape[1] > 1024:
+        raise ValueError(f"at most 1024 features ({x.shape[1]} given): reduce the matrix first")
+    return x.contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ GPU: tree
+
+
+def core_distances(x, min_samples: int, metric: str = "euclidean"):
+    """Distance of every row of x [n, d] (device tensor) to its `min_samples`-th nearest row, itself included
+    (sklearn's convention): float32 [n] on the device.  1 <= min_samples <= min(n, 64)."""
+    import torch
+
+    code = metric_code(metric)
+    x = _prep(x)
+    n, d = x.shape
+    k = int(min_samples)
+    if not 1 <= k <= n:
+        raise ValueError(f"min_samples ({k}) must be in [1, n_samples = {n}]")
+    lib = _lib.load()
+    need = lib.wm_core_distance_workspace_bytes(n, d, k)
+    if need == 0:
+        raise ValueError(f"core_distances: unsupported sizes n={n} d={d} min_samples={k} (min_samples <= 64)")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(lib.wm_core_distance(ptr(x), n, d, code, k, ptr(out), ptr(ws), need, stream_ptr()), "wm_core_distance")
+    return out
+
+
+def min_outgoing_edges(x, core, comp, metric: str = "euclidean", alpha: float = 1.0):
+    """One Boruvka round: per row the lightest mutual-reachability edge to a row of another component
+    (`comp` int32 [n]) as (weight float32 [n], j int32 [n]); j = -1 / weight = inf when there is none."""
+    import torch
+
+    code = metric_code(metric)
+    x = _prep(x)
+    require_gpu(core, comp)
+    n, d = x.shape
+    if core.shape != (n,) or comp.shape != (n,) or core.dtype != torch.float32 or comp.dtype != torch.int32:
+        raise ValueError("core float32 [n] and comp int32 [n] expected")
+    lib = _lib.load()
+    need = lib.wm_mreach_min_edge_workspace_bytes(n, d)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    w = torch.empty(n, dtype=torch.float32, device=x.device)
+    j = torch.empty(n, dtype=torch.int32, device=x.device)
+    check(lib.wm_mreach_min_edge(ptr(x), ptr(core), ptr(comp), n, d, code, 1.0 / float(alpha), ptr(w), ptr(j), ptr(ws),
+                                 need, stream_ptr()), "wm_mreach_min_edge")
+    return w, j
+
+
+def _find_all(parent: np.ndarray) -> np.ndarray:
+    """Root of every element (pointer jumping: O(log depth) vectorised passes)."""
+    root = parent.copy()
+    while True:
+        nxt = root[root]
+        if np.array_equal(nxt, root):
+            return root
+        root = nxt
+
+
+def mutual_reachability_mst(x, min_samples: int, metric: str = "euclidean", alpha: float = 1.0, return_rounds: bool = False):
+    """Minimum spanning tree of the mutual-reachability graph max(core_i, core_j, dist_ij / alpha) of x [n, d]
+    (device tensor): (u, v, w) numpy arrays of the n - 1 edges, u < v, sorted by (w, u, v); w float64 holding the
+    kernels' float32 weights.
+
+    Boruvka: every round the kernel gives each row its lightest edge out of its component (ties to the lowest j);
+    the host takes the per-component minimum under the total order (w, min(i, j), max(i, j)) -- which the lowest-j
+    rule agrees with, and under which no round can close a cycle since an edge has the same weight bits from both
+    ends -- merges, and renumbers the components.  At most ceil(log2 n) rounds."""
+    import torch
+
+    if not alpha > 0:
+        raise ValueError("alpha must be positive")
+    x = _prep(x)
+    n = x.shape[0]
+    core = core_distances(x, min_samples, metric)
+    parent = np.arange(n, dtype=np.int64)
+    eu, ev, ew = [], [], []
+    n_comp, rounds = n, 0
+    comp = parent.copy()
+    while n_comp > 1:
+        w_d, j_d = min_outgoing_edges(x, core, torch.from_numpy(comp.astype(np.int32)).to(x.device), metric, alpha)
+        w, j = w_d.cpu().numpy(), j_d.cpu().numpy().astype(np.int64)
+        rounds += 1
+        i = np.flatnonzero(j >= 0)
+        if i.size == 0:
+            raise _lib.WaferHipError("mutual_reachability_mst: no outgoing edge although several components remain")
+        lo, hi = np.minimum(i, j[i]), np.maximum(i, j[i])
+        order = np.lexsort((hi, lo, w[i], comp[i]))
+        first = np.ones(order.size, dtype=bool)
+        first[1:] = comp[i][order][1:] != comp[i][order][:-1]
+        pick = order[first]  # one edge per component
+        edges = np.unique(np.stack([lo[pick], hi[pick]], axis=1), axis=0)  # two components may pick the same edge
+        for a, b in edges:
+            ra, rb = a, b
+            while parent[ra] != ra:
+                ra = parent[ra]
+            while parent[rb] != rb:
+                rb = parent[rb]
+            if ra == rb:
+                raise _lib.WaferHipError("mutual_reachability_mst: a Boruvka round closed a cycle")
+            parent[max(ra, rb)] = min(ra, rb)
+            eu.append(a)
+            ev.append(b)
+            ew.append(float(w[a]) if j[a] == b else float(w[b]))
+        comp = _find_all(parent)
+        parent = comp.copy()
+        n_comp = int(np.unique(comp).size)
+    u, v, wt = np.asarray(eu, dtype=np.int64), np.asarray(ev, dtype=np.int64), np.asarray(ew, dtype=np.float64)
+    order = np.lexsort((v, u, wt))
+    out = (u[order], v[order], wt[order])
+    return out + (rounds,) if return_rounds else out
+
+
+# ------------------------------------------------------------------------------------------------ host: tree -> labels
+
+
+def _single_linkage(u, v, w, n):
+    """scipy-format hierarchy (left, right, value, size as Python lists) from edges sorted by weight."""
+    parent = list(range(2 * n - 1))
+    size = [1] * n + [0] * (n - 1)
+    left, right = [0] * (n - 1), [0] * (n - 1)
+    for e in range(n - 1):
+        a, b = int(u[e]), int(v[e])
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a == b:
+            raise ValueError("labels_from_mst: the edges contain a cycle")
+        node = n + e
+        left[e], right[e] = a, b
+        size[node] = size[a] + size[b]
+        parent[a] = parent[b] = node
+    return left, right, [float(t) for t in w], size
+
+
+def _bfs(left, right, n, root):
+    """Level order of the hierarchy below `root` (sklearn's bfs_from_hierarchy)."""
+    out, level = [], [root]
+    while level:
+        out.extend(level)
+        nxt = []
+        for node in level:
+            if node >= n:
+                nxt.append(left[node - n])
+                nxt.append(right[node - n])
+        level = nxt
+    return out
+
+
+def _condense(left, right, value, size, n, min_cluster_size):
+    root = 2 * n - 2
+    relabel = {root: n}
+    next_label = n + 1
+    ignore = bytearray(2 * n - 1)
+    rows = []
+    for node in _bfs(left, right, n, root):
+        if node < n or ignore[node]:
+            continue
+        l, r, dist = left[node - n], right[node - n], value[node - n]
+        lam = 1.0 / dist if dist > 0.0 else math.inf
+        lc, rc = size[l], size[r]
+        me = relabel[node]
+        if lc >= min_cluster_size and rc >= min_cluster_size:
+            for child, cnt in ((l, lc), (r, rc)):
+                relabel[child] = next_label
+                rows.append((me, next_label, lam, cnt))
+                next_label += 1
+            continue
+        fall = []
+        if lc < min_cluster_size:
+            fall.append(l)
+        else:
+            relabel[l] = me
+        if rc < min_cluster_size:
+            fall.append(r)
+        else:
+            relabel[r] = me
+        for sub_root in fall:
+            for sub in _bfs(left, right, n, sub_root):
+                if sub < n:
+                    rows.append((me, sub, lam, 1))
+                ignore[sub] = 1
+    return np.array(rows, dtype=CONDENSED_DTYPE)
+
+
+def labels_from_mst(u, v, w, n: int, min_cluster_size: int, cluster_selection_epsilon: float = 0.0,
+                    cluster_selection_method: str = "eom", allow_single_cluster: bool = False
+                    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Flat HDBSCAN clustering from the n - 1 spanning-tree edges (u, v, w), sorted by weight: single-linkage tree,
+    condensed tree, stabilities, excess-of-mass or leaf selection, epsilon merge.  Pure numpy / Python on float64.
+
+    Returns (labels int64 [n] with -1 for noise, probabilities float64 [n], condensed_tree): the condensed tree is
+    a structured array (parent, child, lambda_val, child_size) in sklearn's row order.  Semantics are
+    sklearn.cluster.HDBSCAN's (_tree.pyx) with one deliberate difference in `probabilities`: a cluster's death is
+    the largest lambda over ALL its condensed rows, where sklearn takes the last contiguous run of them."""
+    u, v = np.asarray(u, dtype=np.int64), np.asarray(v, dtype=np.int64)
+    w = np.asarray(w, dtype=np.float64)
+    n, mcs = int(n), int(min_cluster_size)
+    if n < 2 or u.shape != (n - 1,) or v.shape != (n - 1,) or w.shape != (n - 1,):
+        raise ValueError("labels_from_mst needs n >= 2 and n - 1 edges")
+    if mcs < 2:
+        raise ValueError("min_cluster_size must be at least 2")
+    if cluster_selection_epsilon < 0:
+        raise ValueError("cluster_selection_epsilon must not be negative")
+    if cluster_selection_method not in ("eom", "leaf"):
+        raise ValueError("cluster_selection_method must be 'eom' or 'leaf'")
+    if u.min() < 0 or v.min() < 0 or max(u.max(), v.max()) >= n:
+        raise ValueError("edge endpoints must lie in [0, n)")
+    if np.isnan(w).any() or (np.diff(w) < 0).any():
+        raise ValueError("edge weights must be sorted ascending")
+    eps = float(cluster_selection_epsilon)
+
+    tree = _condense(*_single_linkage(u, v, w, n), n, mcs)
+    parent, child, lam, csize = tree["parent"], tree["child"], tree["lambda_val"], tree["child_size"]
+    root = n  # == parent.min()
+    n_nodes = int(parent.max()) + 1
+    is_cl = csize > 1
+    # ---- stabilities, summed in row order as sklearn does
+    births = np.full(max(int(child.max()), root) + 1, np.nan)
+    births[child] = lam
+    births[root] = 0.0
+    stab_arr = np.zeros(n_nodes)
+    with np.errstate(invalid="ignore"):
+        np.add.at(stab_arr, parent, (lam - births[parent]) * csize)
+    stability = {c: float(stab_arr[c]) for c in range(root, n_nodes)}
+    children = {c: [] for c in stability}
+    birth_lambda, cl_parent = {}, {}
+    for p_, c_, l_ in zip(parent[is_cl].tolist(), child[is_cl].tolist(), lam[is_cl].tolist()):
+        children[p_].append(c_)
+        birth_lambda[c_] = l_
+        cl_parent[c_] = p_
+
+    def descendants(c):
+        out, level = [], [c]
+        while level:
+            out.extend(level)
+            level = [g for p_ in level for g in children[p_]]
+        return out
+
+    def traverse_upwards(leaf):
+        p_ = cl_parent[leaf]
+        if p_ == root:
+            return p_ if allow_single_cluster else leaf
+        with np.errstate(divide="ignore"):
+            parent_eps = 1.0 / birth_lambda[p_] if birth_lambda[p_] != 0 else math.inf
+        return p_ if parent_eps > eps else traverse_upwards(p_)
+
+    def epsilon_search(leaves):
+        selected, processed = [], set()
+        for leaf in sorted(leaves):
+            leaf_eps = 1.0 / birth_lambda[leaf] if birth_lambda[leaf] != 0 else math.inf
+            if leaf_eps < eps:
+                if leaf not in processed:
+                    top = traverse_upwards(leaf)
+                    selected.append(top)
+                    processed.update(s for s in descendants(top) if s != top)
+            else:
+                selected.append(leaf)
+        return set(selected)
+
+    node_list = sorted(stability, reverse=True)
+    if not allow_single_cluster:
+        node_list = node_list[:-1]
+    is_cluster = {c: True for c in node_list}
+    has_cluster_rows = bool(is_cl.any())
+    if cluster_selection_method == "eom":
+        for node in node_list:
+            subtree = float(np.sum([stability[c] for c in children[node]]))
+            if subtree > stability[node]:
+                is_cluster[node] = False
+                stability[node] = subtree
+            else:
+                for sub in descendants(node):
+                    if sub != node:
+                        is_cluster[sub] = False
+        if eps != 0.0 and has_cluster_rows:
+            eom = [c for c in is_cluster if is_cluster[c]]
+            if len(eom) == 1 and eom[0] == root:
+                selected = set(eom) if allow_single_cluster else set()
+            else:
+                selected = epsilon_search(set(eom))
+            for c in is_cluster:
+                is_cluster[c] = c in selected
+    else:
+        leaves = {c for c in children if not children[c]} if has_cluster_rows else set()
+        if not leaves:
+            for c in is_cluster:
+                is_cluster[c] = False
+            is_cluster[root] = True
+            selected = set()
+        elif eps != 0.0:
+            selected = epsilon_search(leaves)
+        else:
+            selected = leaves
+        if leaves:
+            for c in is_cluster:
+                is_cluster[c] = c in selected
+    clusters = sorted(c for c in is_cluster if is_cluster[c])
+    label_of = {c: i for i, c in enumerate(clusters)}
+
+    # ---- labels: the nearest selected cluster on the way up from the point's condensed parent
+    top = np.full(n_nodes, root, dtype=np.int64)
+    selected_set = set(clusters)
+    for c in range(root + 1, n_nodes):  # (ids grow downwards: a parent is numbered before its children)
+        top[c] = c if c in selected_set else top[cl_parent[c]]
+    pts = ~is_cl
+    p_child, p_top, p_lam = child[pts], top[parent[pts]], lam[pts]
+    lab_map = np.full(n_nodes, -1, dtype=np.int64)
+    for c, i in label_of.items():
+        lab_map[c] = i
+    labels = np.full(n, -1, dtype=np.int64)
+    under = p_top != root
+    labels[p_child[under]] = lab_map[p_top[under]]
+    if len(clusters) == 1 and allow_single_cluster and (~under).any():
+        threshold = 1.0 / eps if eps != 0.0 else float(lam[parent == root].max())
+        keep = ~under & (p_lam >= threshold)
+        labels[p_child[keep]] = label_of.get(root, -1)
+    # ---- membership strengths
+    deaths = np.zeros(n_nodes)
+    np.maximum.at(deaths, parent, lam)
+    prob = np.zeros(n)
+    lab_pts = labels[p_child]
+    has = lab_pts >= 0
+    death = deaths[np.asarray(clusters, dtype=np.int64)[lab_pts[has]]] if clusters else np.zeros(0)
+    lam_h = p_lam[has]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        val = np.where((death == 0.0) | np.isinf(lam_h), 1.0, np.minimum(lam_h, death) / death)
+    prob[p_child[has]] = val
+    return labels, prob, tree
+
+
+class HDBSCAN:
+    """sklearn.cluster.HDBSCAN on device tensors: `.fit(x)` / `.fit_predict(x)` set `labels_`, `probabilities_`,
+    `condensed_tree_` and `minimum_spanning_tree_` (numpy [n - 1, 3]: u, v, weight; kept whether or not
+    `gen_min_span_tree` is set, since `refit` needs it).  `min_samples=None` means `min_cluster_size`.
+    `refit(min_cluster_size=..., cluster_selection_epsilon=...)` relabels from the stored tree: the tree depends on
+    (metric, min_samples, alpha) only."""
+
+    def __init__(self, min_cluster_size: int = 5, min_samples: Optional[int] = None, cluster_selection_epsilon: float = 0.0,
+                 metric: str = "euclidean", alpha: float = 1.0, cluster_selection_method: str = "eom",
+                 allow_single_cluster: bool = False, gen_min_span_tree: bool = False):
+        metric_code(metric)
+        if cluster_selection_method not in ("eom", "leaf"):
+            raise ValueError("cluster_selection_method must be 'eom' or 'leaf'")
+        if int(min_cluster_size) < 2:
+            raise ValueError("min_cluster_size must be at least 2")
+        if min_samples is not None and int(min_samples) < 1:
+            raise ValueError("min_samples must be at least 1")
+        if cluster_selection_epsilon < 0 or not alpha > 0:
+            raise ValueError("cluster_selection_epsilon >= 0 and alpha > 0 required")
+        self.min_cluster_size, self.min_samples = int(min_cluster_size), min_samples
+        self.cluster_selection_epsilon, self.metric, self.alpha = float(cluster_selection_epsilon), metric, float(alpha)
+        self.cluster_selection_method, self.allow_single_cluster = cluster_selection_method, bool(allow_single_cluster)
+        self.gen_min_span_tree = bool(gen_min_span_tree)
+        self.labels_ = self.probabilities_ = self.condensed_tree_ = self.minimum_spanning_tree_ = None
+        self._n = None
+
+    def fit(self, x) -> "HDBSCAN":
+        k = self.min_cluster_size if self.min_samples is None else int(self.min_samples)
+        if k > x.shape[0]:
+            raise ValueError(f"min_samples ({k}) must be at most the number of samples ({x.shape[0]})")
+        u, v, w = mutual_reachability_mst(x, k, self.metric, self.alpha)
+        self._n = int(x.shape[0])
+        self.minimum_spanning_tree_ = np.stack([u.astype(np.float64), v.astype(np.float64), w], axis=1)
+        return self._label()
+
+    def refit(self, min_cluster_size: Optional[int] = None, cluster_selection_epsilon: Optional[float] = None) -> "HDBSCAN":
+        if self.minimum_spanning_tree_ is None:
+            raise RuntimeError("HDBSCAN.refit before fit")
+        if min_cluster_size is not None:
+            self.min_cluster_size = int(min_cluster_size)
+        if cluster_selection_epsilon is not None:
+            self.cluster_selection_epsilon = float(cluster_selection_epsilon)
+        return self._label()
+
+    def _label(self) -> "HDBSCAN":
+        t = self.minimum_spanning_tree_
+        self.labels_, self.probabilities_, self.condensed_tree_ = labels_from_mst(
+            t[:, 0].astype(np.int64), t[:, 1].astype(np.int64), t[:, 2], self._n, self.min_cluster_size,
+            self.cluster_selection_epsilon, self.cluster_selection_method, self.allow_single_cluster)
+        return self
+
+    def fit_predict(self, x) -> np.ndarray:
+        return self.fit(x).labels_
+
+
+# ------------------------------------------------------------------------------------------------ scores
+
+
+def cluster_distance_sums(x, labels, n_clusters: int, metric: str = "euclidean"):
+    """out[i, c] = sum of dist(i, j) over the rows j with labels[j] == c: float64 [n, n_clusters] on the device
+    (wm_cluster_dist_sums).  labels: int32 device tensor in [-1, n_clusters)."""
+    import torch
+
+    code = metric_code(metric)
+    x = _prep(x)
+    require_gpu(labels)
+    n, d = x.shape
+    if labels.shape != (n,) or labels.dtype != torch.int32:
+        raise ValueError("labels int32 [n] expected")
+    out = torch.empty((n, n_clusters), dtype=torch.float64, device=x.device)
+    check(_lib.load().wm_cluster_dist_sums(ptr(x), ptr(labels), n, d, code, int(n_clusters), ptr(out), stream_ptr()),
+          "wm_cluster_dist_sums")
+    return out
+
+
+def silhouette_samples(x, labels, metric: str = "euclidean"):
+    """sklearn.metrics.silhouette_samples of x [n, d] (device tensor) under `labels` (any integer array or tensor;
+    every distinct value is a cluster, so drop noise rows first as the notebook does): float64 [n] on the device.
+    The all-pairs part is the kernel (rows sorted by label so that each cluster is one run of columns); the
+    per-sample arithmetic on the [n, n_clusters] sums is float64.  Singleton clusters score 0."""
+    import torch
+
+    metric_code(metric)
+    x = _prep(x)
+    n = x.shape[0]
+    lab = torch.as_tensor(np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels)).to(x.device)
+    if lab.shape != (n,):
+        raise ValueError("one label per row expected")
+    _, enc = torch.unique(lab, return_inverse=True)
+    c = int(enc.max()) + 1
+    if not 2 <= c <= n - 1:
+        raise ValueError(f"silhouette needs 2 <= n_clusters <= n_samples - 1 (got {c} clusters, {n} samples)")
+    order = torch.argsort(enc, stable=True)
+    enc_s = enc[order].to(torch.int32).contiguous()
+    sums = cluster_distance_sums(x[order].contiguous(), enc_s, c, metric)
+    counts = torch.bincount(enc_s.long(), minlength=c).double()
+    own = enc_s.long().unsqueeze(1)
+    intra = sums.gather(1, own).squeeze(1)
+    a = intra / (counts[enc_s.long()] - 1.0)
+    other = sums / counts.unsqueeze(0)
+    other.scatter_(1, own, float("inf"))
+    b = other.min(dim=1).values
+    s = (b - a) / torch.maximum(a, b)
+    s = torch.where(counts[enc_s.long()] == 1, torch.zeros_like(s), torch.nan_to_num(s))
+    out = torch.empty_like(s)
+    out[order] = s
+    return out
+
+
+def silhouette_score(x, labels, metric: str = "euclidean") -> float:
+    return float(silhouette_samples(x, labels, metric).mean())
+
+
+def _host64(x) -> np.ndarray:
+    return (x.detach().cpu().double().numpy() if hasattr(x, "detach") else np.asarray(x, dtype=np.float64))
+
+
+def _encode(labels) -> Tuple[np.ndarray, int]:
+    lab = np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels)
+    uniq, enc = np.unique(lab, return_inverse=True)
+    return enc, uniq.size
+
+
+def _cluster_means(x: np.ndarray, enc: np.ndarray, c: int):
+    counts = np.bincount(enc, minlength=c).astype(np.float64)
+    sums = np.zeros((c, x.shape[1]))
+    np.add.at(sums, enc, x)
+    return sums / counts[:, None], counts
+
+
+def calinski_harabasz_score(x, labels) -> float:
+    """sklearn.metrics.calinski_harabasz_score.  O(N D): float64 on the host from per-cluster sums (no kernel)."""
+    x = _host64(x)
+    enc, c = _encode(labels)
+    n = x.shape[0]
+    if not 2 <= c <= n - 1:
+        raise ValueError("calinski_harabasz_score needs 2 <= n_clusters <= n_samples - 1")
+    means, counts = _cluster_means(x, enc, c)
+    extra = float((counts * ((means - x.mean(axis=0)) ** 2).sum(axis=1)).sum())
+    intra = float(((x - means[enc]) ** 2).sum())
+    return 1.0 if intra == 0.0 else extra * (n - c) / (intra * (c - 1.0))
+
+
+def davies_bouldin_score(x, labels) -> float:
+    """sklearn.metrics.davies_bouldin_score (Euclidean).  O(N D): float64 on the host from per-cluster sums."""
+    x = _host64(x)
+    enc, c = _encode(labels)
+    if not 2 <= c <= x.shape[0] - 1:
+        raise ValueError("davies_bouldin_score needs 2 <= n_clusters <= n_samples - 1")
+    means, counts = _cluster_means(x, enc, c)
+    spread = np.bincount(enc, weights=np.sqrt(((x - means[enc]) ** 2).sum(axis=1)), minlength=c) / counts
+    sep = np.sqrt(((means[:, None, :] - means[None, :, :]) ** 2).sum(axis=2))
+    if np.allclose(spread, 0) or np.allclose(sep, 0):
+        return 0.0
+    sep[sep == 0] = np.inf
+    ratio = (spread[:, None] + spread[None, :]) / sep
+    return float(ratio.max(axis=1).mean())
+
+
+def homogeneity_score(labels_true, labels_pred) -> float:
+    """sklearn.metrics.homogeneity_score: 1 - H(C | K) / H(C), float64 on the host from the contingency table."""
+    t, nt = _encode(labels_true)
+    p, npred = _encode(labels_pred)
+    if t.shape != p.shape:
+        raise ValueError("labels_true and labels_pred differ in length")
+    if t.size == 0:
+        return 1.0
+    table = np.zeros((nt, npred))
+    np.add.at(table, (t, p), 1.0)
+    n = float(t.size)
+    pc = table.sum(axis=1) / n
+    h_c = float(-(pc[pc > 0] * np.log(pc[pc > 0])).sum())
+    if h_c == 0.0:
+        return 1.0
+    pk = table.sum(axis=0)
+    nz = table > 0
+    h_ck = float(-(table[nz] / n * np.log(table[nz] / np.broadcast_to(pk, table.shape)[nz])).sum())
+    return 1.0 - h_ck / h_c

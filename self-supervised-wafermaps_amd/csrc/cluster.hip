@@ -1,0 +1,455 @@
+// All-pairs distance kernels of the embedding-clustering flow (reference notebooks 3.1-Embeddings-clustering and
+// 3.2-Embeddings-SSL-categories: HDBSCAN on the dumped embedding matrix, scored by silhouette):
+//   wm_core_distance      k-th smallest distance of every row (the HDBSCAN core distance, self included);
+//   wm_mreach_min_edge    one Boruvka round on the mutual-reachability graph: per row the lightest edge that
+//                         leaves the row's component;
+//   wm_cluster_dist_sums  per row the sum of its distances to the members of every cluster (silhouette).
+//
+// ONE distance function serves all three (cl_accum / cl_finish below): the float32 differences a_k - b_k are
+// accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
+// correctly rounded square root; Manhattan: acc + |t|).  Not ||a||^2 + ||b||^2 - 2ab: wafer embeddings contain
+// near-duplicates, whose distance that form cancels away.  Two properties the host code and the tests rely on:
+//   (1) dist(i, j) and dist(j, i) are the same bits: a - b = -(b - a) exactly, t * t and |t| do not see the sign, and
+//       both directions add the same terms in the same order.  (Zero padding of the feature dimension adds exact
+//       zeros.)  So an edge has ONE weight whichever endpoint finds it, which Boruvka needs.
+//   (2) the relative error against the exact distance of the float32 rows is at most (d + 3) * 2^-24 (first order):
+//       one rounding per difference (twice in the square), one per accumulation step (d for the fused
+//       multiply-adds, d - 1 for the Manhattan additions), halved by the square root, plus the root's own rounding:
+//       Euclidean (d + 2) / 2 + 1, Manhattan d.  Equal rows give t = 0 in every term: the distance is exactly 0.
+//
+// Shape of the work: a register-tiled all-pairs pass on the float32 VALU (no MFMA: the distance is not a product).
+// A workgroup of 256 threads owns 16 * TM rows i and walks 64-row column tiles j; both row sets are staged in LDS in
+// chunks of 32 features ([row][36] floats: the 16 rows a wave reads with one ds_read_b128 start 36 dwords apart, on
+// 16 distinct 4-bank slots); thread (ty, tx) accumulates the TM x 4 pairs (ty + 16 r, tx + 16 c).  The next chunk is
+// fetched into registers while the current one is consumed.  Per column tile the mode's epilogue runs:
+//   core      distances -> LDS tile; one owner thread per row inserts those below its current k-th into the row's
+//             sorted k-list (LDS; after the first tiles an insertion is rare);
+//   min edge  every thread keeps the best (w, j) of its TM rows in registers; one LDS reduction at the end;
+//   sums      distances -> LDS tile; the row's owner adds them in column order, in double, and flushes the running sum
+//             to out[i][label] whenever the label changes (rows sorted by label: once per cluster).
+// Core and min edge split the columns into slices (grid.y) whose partial results a second small kernel combines in a
+// fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
+// atomics anywhere: two calls give the same bits.
+// Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
+// ((16 TM + 64) rows per 16 TM x 64 pairs).
+#include "common.h"
+
+namespace {
+
+constexpr int CL_THREADS = 256;
+constexpr int CL_COLS = 64;          // rows j per column tile
+constexpr int CL_KC = 32;            // features per staged chunk
+constexpr int CL_LDK = CL_KC + 4;    // LDS row pitch of a staged chunk (floats)
+constexpr int CL_LDD = CL_COLS + 1;  // LDS row pitch of a distance tile (floats)
+constexpr int CL_MAXK = 64;
+constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2;
+
+template <int METRIC>
+__device__ __forceinline__ float cl_accum(float a, float b, float acc) {
+  const float t = a - b;
+  if constexpr (METRIC == 0) return fmaf(t, t, acc);
+  return acc + fabsf(t);
+}
+template <int METRIC>
+__device__ __forceinline__ float cl_finish(float acc) {
+  if constexpr (METRIC == 0) return sqrtf(acc);  // (the correctly rounded root; __fsqrt_rn is the ~1 ulp native one here)
+  return acc;
+}
+
+struct ClArgs {
+  const float* x;
+  int n, d, tiles_per_slice, col_tiles;
+  // core
+  int k, kl;
+  float* part_lists;  // [slices][n][k]
+  // min edge
+  const float* core;
+  const int* comp;
+  float inv_alpha;
+  float* part_w;  // [slices][n]
+  int* part_j;
+  // sums
+  const int* labels;
+  int n_clusters;
+  double* out;  // [n][n_clusters]
+};
+
+template <int MODE, int TM>
+constexpr size_t cl_lds_bytes(int kl) {
+  size_t f = (size_t)(16 * TM + CL_COLS) * CL_LDK;
+  if (MODE != CL_MINEDGE) f += (size_t)16 * TM * CL_LDD;
+  if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
+  if (MODE == CL_SUMS) f += CL_COLS;
+  return f * sizeof(float);
+}
+
+template <int MODE, int METRIC, int TM>
+__global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float cl_smem[];
+  constexpr int ROWS = 16 * TM;
+  constexpr int APASS = ROWS / 32, BPASS = CL_COLS / 32;
+  float* As = cl_smem;
+  float* Bs = As + ROWS * CL_LDK;
+  [[maybe_unused]] float* Dt = Bs + CL_COLS * CL_LDK;  // (core, sums) the tile's distances [ROWS][CL_LDD]
+  [[maybe_unused]] float* extra = Dt + ROWS * CL_LDD;  // core: the k-lists [ROWS][kl]; sums: the tile's labels [64]
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int lq = (t & 7) * 4, lr = t >> 3;  // staging: float4 at feature lq of row lr (+ 32 per pass)
+  const int n = p.n, d = p.d;
+  const int i0 = blockIdx.x * ROWS;
+  const int tile0 = blockIdx.y * p.tiles_per_slice;
+  const int tile1 = min(tile0 + p.tiles_per_slice, p.col_tiles);
+  const int nchunks = (d + CL_KC - 1) / CL_KC;
+
+  // ---- per-mode state
+  float ci[TM], bw[TM];
+  int cpi[TM], bj[TM];
+  int cur = -1;
+  double run = 0.0;
+  if constexpr (MODE == CL_MINEDGE) {
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      const int i = i0 + ty + 16 * r;
+      ci[r] = i < n ? p.core[i] : 0.f;
+      cpi[r] = i < n ? p.comp[i] : 0;
+      bw[r] = INFINITY;
+      bj[r] = -1;
+    }
+  }
+  if constexpr (MODE == CL_CORE) {
+    for (int q = t; q < ROWS * p.kl; q += CL_THREADS) extra[q] = INFINITY;  // (ordered by the chunk loop's barriers)
+  }
+
+  for (int tile = tile0; tile < tile1; ++tile) {
+    const int j0 = tile * CL_COLS;
+    float acc[TM][4];
+#pragma unroll
+    for (int r = 0; r < TM; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
+    float4 ra[APASS], rb[BPASS];
+    auto fetch = [&](int ch) {
+      const int kq = ch * CL_KC + lq;
+#pragma unroll
+      for (int s = 0; s < APASS; ++s) {
+        const int row = i0 + lr + 32 * s;
+        ra[s] = (row < n && kq < d) ? *reinterpret_cast<const float4*>(p.x + (size_t)row * d + kq)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int s = 0; s < BPASS; ++s) {
+        const int row = j0 + lr + 32 * s;
+        rb[s] = (row < n && kq < d) ? *reinterpret_cast<const float4*>(p.x + (size_t)row * d + kq)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    };
+    fetch(0);
+    for (int ch = 0; ch < nchunks; ++ch) {
+      __syncthreads();  // the previous chunk (or the previous tile's epilogue) is done with the staging buffers
+#pragma unroll
+      for (int s = 0; s < APASS; ++s) *reinterpret_cast<float4*>(As + (lr + 32 * s) * CL_LDK + lq) = ra[s];
+#pragma unroll
+      for (int s = 0; s < BPASS; ++s) *reinterpret_cast<float4*>(Bs + (lr + 32 * s) * CL_LDK + lq) = rb[s];
+      __syncthreads();
+      if (ch + 1 < nchunks) fetch(ch + 1);
+#pragma unroll 2
+      for (int kk = 0; kk < CL_KC; kk += 4) {
+        float4 a[TM], b[4];
+#pragma unroll
+        for (int r = 0; r < TM; ++r) a[r] = *reinterpret_cast<const float4*>(As + (ty + 16 * r) * CL_LDK + kk);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) b[c] = *reinterpret_cast<const float4*>(Bs + (tx + 16 * c) * CL_LDK + kk);
+        // index order within every pair: x, y, z, w of this float4 follow the earlier features
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[r][c] = cl_accum<METRIC>(a[r].x, b[c].x, acc[r][c]);
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[r][c] = cl_accum<METRIC>(a[r].y, b[c].y, acc[r][c]);
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[r][c] = cl_accum<METRIC>(a[r].z, b[c].z, acc[r][c]);
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[r][c] = cl_accum<METRIC>(a[r].w, b[c].w, acc[r][c]);
+      }
+    }
+
+    // ---- the tile's epilogue
+    if constexpr (MODE == CL_MINEDGE) {
+      float cj[4];
+      int cpj[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = j0 + tx + 16 * c;
+        cj[c] = j < n ? p.core[j] : 0.f;
+        cpj[c] = j < n ? p.comp[j] : 0;
+      }
+#pragma unroll
+      for (int r = 0; r < TM; ++r) {
+        const bool iv = i0 + ty + 16 * r < n;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int j = j0 + tx + 16 * c;
+          const float w = fmaxf(fmaxf(ci[r], cj[c]), cl_finish<METRIC>(acc[r][c]) * p.inv_alpha);
+          if (iv && j < n && cpj[c] != cpi[r] && (w < bw[r] || (w == bw[r] && j < bj[r]))) {
+            bw[r] = w;
+            bj[r] = j;
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < TM; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          Dt[(ty + 16 * r) * CL_LDD + tx + 16 * c] = j0 + tx + 16 * c < n ? cl_finish<METRIC>(acc[r][c]) : INFINITY;
+      if constexpr (MODE == CL_SUMS) {
+        if (t < CL_COLS) reinterpret_cast<int*>(extra)[t] = j0 + t < n ? p.labels[j0 + t] : -1;
+      }
+      __syncthreads();
+      // (the next write of Dt / the labels lies behind the next tile's chunk barriers, which the owners reach only
+      // after this scan)
+      if (t < ROWS && i0 + t < n) {
+        const float* row = Dt + t * CL_LDD;
+        if constexpr (MODE == CL_CORE) {
+          float* L = extra + t * p.kl;
+          const int k = p.k;
+          float kth = L[k - 1];
+          for (int c = 0; c < CL_COLS; ++c) {
+            const float v = row[c];
+            if (v < kth) {
+              int pos = k - 1;
+              while (pos > 0 && L[pos - 1] > v) {
+                L[pos] = L[pos - 1];
+                --pos;
+              }
+              L[pos] = v;
+              kth = L[k - 1];
+            }
+          }
+        } else {
+          const int* lab = reinterpret_cast<const int*>(extra);
+          double* orow = p.out + (size_t)(i0 + t) * p.n_clusters;
+          for (int c = 0; c < CL_COLS; ++c) {
+            const int l = lab[c];
+            if (l < 0 || l >= p.n_clusters) continue;
+            if (l != cur) {
+              if (cur >= 0) orow[cur] += run;
+              cur = l;
+              run = 0.0;
+            }
+            run += (double)row[c];
+          }
+        }
+      }
+    }
+  }
+
+  // ---- the slice's result
+  if constexpr (MODE == CL_SUMS) {
+    if (t < ROWS && i0 + t < n && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
+  }
+  if constexpr (MODE == CL_CORE) {
+    if (t < ROWS && i0 + t < n) {
+      const float* L = extra + t * p.kl;
+      float* o = p.part_lists + ((size_t)blockIdx.y * n + i0 + t) * p.k;
+      for (int q = 0; q < p.k; ++q) o[q] = L[q];
+    }
+  }
+  if constexpr (MODE == CL_MINEDGE) {
+    __syncthreads();  // the staging buffers become the reduction scratch: [ROWS][17] weights, then indices
+    float* rw = cl_smem;
+    int* rj = reinterpret_cast<int*>(cl_smem + ROWS * 17);
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      rw[(ty + 16 * r) * 17 + tx] = bw[r];
+      rj[(ty + 16 * r) * 17 + tx] = bj[r];
+    }
+    __syncthreads();
+    if (t < ROWS && i0 + t < n) {
+      float w = rw[t * 17];
+      int j = rj[t * 17];
+      for (int q = 1; q < 16; ++q) {
+        const float wq = rw[t * 17 + q];
+        const int jq = rj[t * 17 + q];
+        if (jq >= 0 && (j < 0 || wq < w || (wq == w && jq < j))) {
+          w = wq;
+          j = jq;
+        }
+      }
+      p.part_w[(size_t)blockIdx.y * n + i0 + t] = w;
+      p.part_j[(size_t)blockIdx.y * n + i0 + t] = j;
+    }
+  }
+}
+
+// k-th smallest of the slices' k-lists of a row, by rank counting (ties ordered by position, so exactly one candidate
+// has rank k - 1): one wave per row.
+__global__ __launch_bounds__(CL_THREADS) void cl_core_merge(const float* __restrict__ parts, int slices, int n, int k,
+                                                            float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (CL_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (row >= n) return;
+  const int m = slices * k;
+  for (int q = lane; q < m; q += 64) {
+    const float v = parts[((size_t)(q / k) * n + row) * k + q % k];
+    int rank = 0;
+    for (int s = 0; s < slices; ++s) {
+      const float* l = parts + ((size_t)s * n + row) * k;
+      for (int e = 0; e < k; ++e) {
+        const float u = l[e];
+        rank += (u < v || (u == v && s * k + e < q)) ? 1 : 0;
+      }
+    }
+    if (rank == k - 1) out[row] = v;
+  }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void cl_minedge_merge(const float* __restrict__ pw, const int* __restrict__ pj,
+                                                               int slices, int n, float* __restrict__ out_w,
+                                                               int* __restrict__ out_j) {
+  const int i = blockIdx.x * CL_THREADS + threadIdx.x;
+  if (i >= n) return;
+  float w = INFINITY;
+  int j = -1;
+  for (int s = 0; s < slices; ++s) {
+    const float ws = pw[(size_t)s * n + i];
+    const int js = pj[(size_t)s * n + i];
+    if (js >= 0 && (j < 0 || ws < w || (ws == w && js < j))) {
+      w = ws;
+      j = js;
+    }
+  }
+  out_w[i] = j < 0 ? INFINITY : w;
+  out_j[i] = j;
+}
+
+struct ClGrid {
+  int row_tiles, col_tiles, slices, tiles_per_slice;
+};
+// Column slices so that about a thousand workgroups exist (four per CU); every slice holds at least one tile.
+inline ClGrid cl_grid(int n, int rows, bool sliced) {
+  ClGrid g;
+  g.row_tiles = wm_cdiv(n, rows);
+  g.col_tiles = wm_cdiv(n, CL_COLS);
+  int want = sliced ? wm_cdiv(1024, g.row_tiles) : 1;
+  if (want > g.col_tiles) want = g.col_tiles;
+  g.tiles_per_slice = wm_cdiv(g.col_tiles, want);
+  g.slices = wm_cdiv(g.col_tiles, g.tiles_per_slice);
+  return g;
+}
+
+template <int MODE, int TM>
+int cl_launch(const ClArgs& a, const ClGrid& g, int metric, hipStream_t st) {
+  const size_t lds = cl_lds_bytes<MODE, TM>(a.kl);
+  constexpr size_t lds_max = cl_lds_bytes<MODE, TM>(CL_MAXK | 1);  // the mode's largest request, allowed once
+  static bool attr_set[2] = {false, false};  // per metric; idempotent; a race only repeats the call
+  if (lds_max > 64 * 1024 && !attr_set[metric]) {
+    const void* fn = metric == 0 ? reinterpret_cast<const void*>(&cl_pairs<MODE, 0, TM>)
+                                 : reinterpret_cast<const void*>(&cl_pairs<MODE, 1, TM>);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    if (e != hipSuccess) return (int)e;
+    attr_set[metric] = true;
+  }
+  const dim3 grid(g.row_tiles, g.slices);
+  if (metric == 0)
+    cl_pairs<MODE, 0, TM><<<grid, CL_THREADS, lds, st>>>(a);
+  else
+    cl_pairs<MODE, 1, TM><<<grid, CL_THREADS, lds, st>>>(a);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+inline bool cl_shape_ok(int d, int metric) { return d % 4 == 0 && d <= 1024 && (metric == 0 || metric == 1); }
+constexpr int CL_MAX_N = 1 << 24;  // (row * d and slice * n + row stay far inside size_t; tile indices inside int)
+
+}  // namespace
+
+extern "C" size_t wm_core_distance_workspace_bytes(int n, int d, int k) {
+  if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
+  return (size_t)cl_grid(n, 128, true).slices * n * k * sizeof(float) + 256;
+}
+
+extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(x && out && workspace, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
+  const ClGrid g = cl_grid(n, 128, true);
+  WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * k * sizeof(float), WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.k = k;
+  a.kl = k | 1;  // odd pitch: the owners' list accesses fall on distinct banks
+  a.part_lists = static_cast<float*>(workspace);
+  const int rc = cl_launch<CL_CORE, 8>(a, g, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_core_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, g.slices, n, k, out);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_mreach_min_edge_workspace_bytes(int n, int d) {
+  if (n <= 0 || n > CL_MAX_N || d <= 0) return 0;
+  return (size_t)cl_grid(n, 128, true).slices * n * 8 + 256;
+}
+
+extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32_t* comp, int n, int d, int metric,
+                                  float inv_alpha, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  WM_REQUIRE(x && core && comp && out_w && out_j && workspace, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && inv_alpha > 0.f, WM_EINVAL);
+  WM_REQUIRE(n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
+  const ClGrid g = cl_grid(n, 128, true);
+  WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.core = core;
+  a.comp = comp;
+  a.inv_alpha = inv_alpha;
+  a.part_w = static_cast<float*>(workspace);
+  a.part_j = reinterpret_cast<int*>(a.part_w + (size_t)g.slices * n);
+  const int rc = cl_launch<CL_MINEDGE, 8>(a, g, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, g.slices, n, out_w, out_j);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, int metric, int n_clusters,
+                                    double* out, void* stream) {
+  WM_REQUIRE(x && labels && out, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && n_clusters >= 2 && n_clusters <= n, WM_EINVAL);
+  WM_REQUIRE(n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0, WM_EALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t e = wm_zero_async(out, (size_t)n * n_clusters * sizeof(double), st);
+  if (e != hipSuccess) return (int)e;
+  const ClGrid g = cl_grid(n, 64, false);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.labels = labels;
+  a.n_clusters = n_clusters;
+  a.out = out;
+  return cl_launch<CL_SUMS, 4>(a, g, metric, st);
+}
