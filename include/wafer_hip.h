@@ -771,6 +771,33 @@ int wm_mreach_min_edge(const float* x, const float* core, const int32_t* comp, i
 int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, int metric, int n_clusters, double* out,
                          void* stream);
 
+/* The exact k-nearest-neighbour graph under the same distance function: dist float32 [n][k] and idx int32 [n][k], every
+ * row ordered by (distance, index) ascending with the row itself among its own candidates (so dist[i][0] = 0).
+ * 1 <= k <= 64, k <= n (k > n: WM_EINVAL). */
+size_t wm_knn_graph_workspace_bytes(int n, int d, int k);
+int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas
+ * are stated in full in csrc/umap.hip.
+ *
+ * wm_umap_smooth_knn: per row of dist / idx [n][k] (as wm_knn_graph returns them) rho[i] = the first positive distance
+ * (0 if none), sigma[i] by at most 64 bisection steps so that sum_{j >= 1} exp(-max(d_j - rho, 0) / sigma) = log2(k) to
+ * 1e-5, floored at 1e-3 * the row's mean distance (rho > 0) or 1e-3 * *mean_dist (rho = 0; mean_dist: device pointer to
+ * the mean of all n * k distances), and weights[i][j] = exp(-max(d_j - rho, 0) / sigma), 0 where idx[i][j] = i
+ * (umap-learn with local_connectivity = 1).  Double precision inside; rho, sigma [n], weights [n][k] float32. */
+int wm_umap_smooth_knn(const float* dist, const int32_t* idx, int n, int k, const double* mean_dist, float* rho, float* sigma,
+                       float* weights, void* stream);
+/* Layout epochs [epoch_begin, epoch_end) of n_epochs over the symmetric graph in CSR form (indptr int32 [n + 1], indices
+ * int32 [nnz] in [0, n), q uint32 [nnz] = rint(65536 * weight / max weight)), one launch per epoch, reading one of
+ * y_a / y_b float32 [n][dim] and writing the other, starting from y_a; *result_buffer (host) = 0 when the result is in
+ * y_a, 1 when in y_b.  Deterministic gather, no atomics: splitting the epoch range over several calls, or calling
+ * twice, gives the same bits.  1 <= dim <= 64, 0 <= neg_rate <= 64; a, b > 0.  No allocation, no synchronisation. */
+int wm_umap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n, int dim,
+                   double a, double b, double gamma, double learning_rate, uint32_t seed, int epoch_begin, int epoch_end,
+                   int n_epochs, int neg_rate, int* result_buffer, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -22,8 +22,8 @@ What the notebooks do, and where it is here:
                                                              down; and, beyond the notebooks' four scores,
                                                              n_noise down)
   nearest wafers of a member of each cluster              -> retrieval.nearest_neighbors (5 neighbours, L2)
-UMAP / DensMAP only draw the notebooks' 2-D pictures and are not part of this script; pass a reduced matrix as
---embeddings to cluster one.  `min_samples` counts the point itself (sklearn's convention; the `hdbscan` package's
+UMAP is a script of its own: scripts/embedding_umap_amd.py writes a reduced.npz that --embeddings reads (add --no-scale),
+which is notebook 3.2's reduce-then-cluster flow in two commands.  `min_samples` counts the point itself (sklearn's convention; the `hdbscan` package's
 generic path counts one neighbour more).  The canberra and braycurtis metrics of the notebook's search space have
 no kernel and are refused.
 

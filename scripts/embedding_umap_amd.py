@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""UMAP of dumped embeddings on MI355X: the `umap.UMAP(...).fit_transform(data)` step of the reference's notebooks
+(3.0-Embeddings-inference, 3.1-Embeddings-clustering, 3.2-Embeddings-SSL-categories, 2.0-Figures-MixedWM38) on the HIP
+path (ssl_wafermap_amd.manifold).
+
+    python scripts/embedding_umap_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
+                                         [--neighbors 15] [--components 2] [--min-dist 0.1] [--epochs N]
+                                         [--init spectral|pca|random] [--seed 0] [--no-scale] [--rows N] [--out DIR]
+
+What the notebooks do, and where it is here:
+  StandardScaler().fit_transform(embeddings)        -> retrieval.StandardScaler (skipped with --no-scale)
+  umap.UMAP(n_neighbors, n_components, min_dist, ...).fit_transform(data)
+                                                     -> manifold.UMAP: exact kNN graph, fuzzy simplicial set and the
+                                                        layout optimisation as HIP kernels
+  the 2-D scatter coloured by failure code          -> umap.png (when --components 2)
+  3.2: HDBSCAN on UMAP(n_neighbors=30, min_dist=0, n_components=50).fit_transform(data)
+                                                     -> --neighbors 30 --min-dist 0 --components 50, then
+                                                        scripts/embedding_clustering_amd.py --embeddings DIR/reduced.npz
+                                                        --no-scale (the notebook's densmap=True density term is not
+                                                        built: the reduction is plain UMAP)
+
+Outputs under --out: reduced.npz (`embeddings` float32 [n, components], `labels`: the format --embeddings reads),
+umap.png for two components, summary.json (seconds per stage; sklearn trustworthiness on at most 5 000 seeded rows).
+"""
+from __future__ import annotations
+
+import argparse
+import importlib.util
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+
+def load_embeddings(path):
+    """scripts/embedding_clustering_amd.py's loader (.npz or a reference *_preds_*.pkl.xz)."""
+    spec = importlib.util.spec_from_file_location("embedding_clustering_amd", Path(__file__).with_name("embedding_clustering_amd.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.load_embeddings(path)
+
+
+def main(argv=None) -> dict:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--embeddings", required=True)
+    ap.add_argument("--neighbors", type=int, default=15)
+    ap.add_argument("--components", type=int, default=2)
+    ap.add_argument("--min-dist", type=float, default=0.1)
+    ap.add_argument("--epochs", type=int, default=0, help="0: 500 for at most 10 000 rows, 200 above")
+    ap.add_argument("--init", choices=["spectral", "pca", "random"], default="spectral")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--rows", type=int, default=0, help="use the first N rows only")
+    ap.add_argument("--no-scale", action="store_true")
+    ap.add_argument("--out", default="umap_out")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+
+    import torch
+
+    from ssl_wafermap_amd import manifold
+    from ssl_wafermap_amd.retrieval import StandardScaler
+
+    model = manifold.UMAP(n_neighbors=a.neighbors, n_components=a.components, min_dist=a.min_dist, n_epochs=a.epochs or None,
+                          init=a.init, random_state=a.seed)
+    emb, truth = load_embeddings(a.embeddings)
+    if a.rows:
+        emb, truth = emb[:a.rows], truth[:a.rows]
+    x = torch.from_numpy(emb).to(a.device)
+    if not a.no_scale:
+        x = StandardScaler().fit_transform(x)
+    out = Path(a.out)
+    out.mkdir(parents=True, exist_ok=True)
+    n = int(x.shape[0])
+
+    # the stages of UMAP.fit, timed one by one (a synchronise closes each)
+    seconds = {}
+
+    def timed(name, fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        seconds[name] = time.perf_counter() - t0
+        return res
+
+    k = min(model.n_neighbors, n)
+    dist, idx = timed("knn_graph", lambda: manifold.knn_graph(x, k, model.metric))
+    graph = timed("fuzzy_set", lambda: manifold.fuzzy_union(idx, manifold.smooth_knn(dist, idx)[2]))
+    y0 = timed("init", lambda: model._initial(manifold._prep(x), graph))
+    n_epochs = model.n_epochs if model.n_epochs is not None else (500 if n <= 10000 else 200)
+    y = timed("layout", lambda: manifold.optimize_layout(
+        y0, graph.indptr, graph.indices, manifold.sample_rates(graph.data), model.a_, model.b_, n_epochs,
+        gamma=model.repulsion_strength, learning_rate=model.learning_rate, seed=model.random_state,
+        negative_sample_rate=model.negative_sample_rate))
+    reduced = y.cpu().numpy()
+    np.savez(out / "reduced.npz", embeddings=reduced, labels=truth)
+
+    from sklearn.manifold import trustworthiness
+
+    pick = np.sort(np.random.default_rng(a.seed).permutation(n)[:5000])
+    xs = x[torch.from_numpy(pick).to(x.device)].cpu().numpy()
+    score = float(trustworthiness(xs, reduced[pick], n_neighbors=min(15, max(1, (pick.size - 1) // 2 - 1))))
+    if a.components == 2:
+        import matplotlib
+
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+
+        fig, ax = plt.subplots(figsize=(7, 7))
+        sc = ax.scatter(reduced[:, 0], reduced[:, 1], c=truth, cmap="tab10", s=4)
+        ax.legend(*sc.legend_elements(), title="failure code", loc="best", fontsize=7)
+        ax.set_title(f"UMAP of {n} embeddings (n_neighbors={k}, min_dist={a.min_dist})")
+        fig.savefig(out / "umap.png", dpi=120)
+        plt.close(fig)
+    summary = {"n": n, "d": int(x.shape[1]), "n_neighbors": k, "n_components": a.components, "min_dist": a.min_dist,
+               "n_epochs": n_epochs, "init": a.init, "a": model.a_, "b": model.b_, "graph_entries": int(graph.indices.numel()),
+               "seconds": seconds, "trustworthiness": score, "trustworthiness_rows": int(pick.size)}
+    (out / "summary.json").write_text(json.dumps(summary, indent=1))
+    print(f"UMAP of {n} x {x.shape[1]} -> {a.components}-D in {sum(seconds.values()):.2f} s "
+          f"({', '.join(f'{s} {v:.3f}' for s, v in seconds.items())}); trustworthiness {score:.4f} -> {out}")
+    return summary
+
+
+if __name__ == "__main__":
+    main()

@@ -287,6 +287,12 @@ SIGNATURES = {
     "wm_mreach_min_edge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                    c_size_t, c_void_p]),
     "wm_cluster_dist_sums": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wm_knn_graph_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_knn_graph": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- UMAP
+    "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
+                               c_double, c_uint32, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -3,9 +3,11 @@
 //   wm_core_distance      k-th smallest distance of every row (the HDBSCAN core distance, self included);
 //   wm_mreach_min_edge    one Boruvka round on the mutual-reachability graph: per row the lightest edge that
 //                         leaves the row's component;
-//   wm_cluster_dist_sums  per row the sum of its distances to the members of every cluster (silhouette).
+//   wm_cluster_dist_sums  per row the sum of its distances to the members of every cluster (silhouette);
+//   wm_knn_graph          the k nearest rows of every row with their indices, ordered by (distance, index), the row
+//                         itself among its candidates (the exact kNN graph that manifold.UMAP starts from).
 //
-// ONE distance function serves all three (cl_accum / cl_finish below): the float32 differences a_k - b_k are
+// ONE distance function serves all four (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
 // correctly rounded square root; Manhattan: acc + |t|).  Not ||a||^2 + ||b||^2 - 2ab: wafer embeddings contain
 // near-duplicates, whose distance that form cancels away.  Two properties the host code and the tests rely on:
@@ -24,10 +26,12 @@
 // fetched into registers while the current one is consumed.  Per column tile the mode's epilogue runs:
 //   core      distances -> LDS tile; one owner thread per row inserts those below its current k-th into the row's
 //             sorted k-list (LDS; after the first tiles an insertion is rare);
+//   knn       the same with the column index carried next to the distance; a slice scans its columns in ascending
+//             order and a candidate goes behind its equals, so a list is ordered by (distance, index);
 //   min edge  every thread keeps the best (w, j) of its TM rows in registers; one LDS reduction at the end;
 //   sums      distances -> LDS tile; the row's owner adds them in column order, in double, and flushes the running sum
 //             to out[i][label] whenever the label changes (rows sorted by label: once per cluster).
-// Core and min edge split the columns into slices (grid.y) whose partial results a second small kernel combines in a
+// Core, knn and min edge split the columns into slices (grid.y) whose partial results a second small kernel combines in a
 // fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
 // atomics anywhere: two calls give the same bits.
 // Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
@@ -42,7 +46,7 @@ constexpr int CL_KC = 32;            // features per staged chunk
 constexpr int CL_LDK = CL_KC + 4;    // LDS row pitch of a staged chunk (floats)
 constexpr int CL_LDD = CL_COLS + 1;  // LDS row pitch of a distance tile (floats)
 constexpr int CL_MAXK = 64;
-constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2;
+constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3;
 
 template <int METRIC>
 __device__ __forceinline__ float cl_accum(float a, float b, float acc) {
@@ -62,6 +66,7 @@ struct ClArgs {
   // core
   int k, kl;
   float* part_lists;  // [slices][n][k]
+  int* part_idx;      // knn: the lists' column indices, same shape (-1 pads a slice with fewer than k columns)
   // min edge
   const float* core;
   const int* comp;
@@ -79,6 +84,7 @@ constexpr size_t cl_lds_bytes(int kl) {
   size_t f = (size_t)(16 * TM + CL_COLS) * CL_LDK;
   if (MODE != CL_MINEDGE) f += (size_t)16 * TM * CL_LDD;
   if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
+  if (MODE == CL_KNN) f += (size_t)2 * 16 * TM * kl;
   if (MODE == CL_SUMS) f += CL_COLS;
   return f * sizeof(float);
 }
@@ -91,7 +97,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   float* As = cl_smem;
   float* Bs = As + ROWS * CL_LDK;
   [[maybe_unused]] float* Dt = Bs + CL_COLS * CL_LDK;  // (core, sums) the tile's distances [ROWS][CL_LDD]
-  [[maybe_unused]] float* extra = Dt + ROWS * CL_LDD;  // core: the k-lists [ROWS][kl]; sums: the tile's labels [64]
+  [[maybe_unused]] float* extra = Dt + ROWS * CL_LDD;  // core, knn: the k-lists [ROWS][kl]; sums: the tile's labels [64]
+  [[maybe_unused]] int* extra_j = reinterpret_cast<int*>(extra) + ROWS * p.kl;  // knn: the lists' indices [ROWS][kl]
   const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
   const int lq = (t & 7) * 4, lr = t >> 3;  // staging: float4 at feature lq of row lr (+ 32 per pass)
   const int n = p.n, d = p.d;
@@ -115,8 +122,11 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       bj[r] = -1;
     }
   }
-  if constexpr (MODE == CL_CORE) {
+  if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
     for (int q = t; q < ROWS * p.kl; q += CL_THREADS) extra[q] = INFINITY;  // (ordered by the chunk loop's barriers)
+  }
+  if constexpr (MODE == CL_KNN) {
+    for (int q = t; q < ROWS * p.kl; q += CL_THREADS) extra_j[q] = -1;
   }
 
   for (int tile = tile0; tile < tile1; ++tile) {
@@ -215,8 +225,9 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       // after this scan)
       if (t < ROWS && i0 + t < n) {
         const float* row = Dt + t * CL_LDD;
-        if constexpr (MODE == CL_CORE) {
+        if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
           float* L = extra + t * p.kl;
+          [[maybe_unused]] int* J = extra_j + t * p.kl;
           const int k = p.k;
           float kth = L[k - 1];
           for (int c = 0; c < CL_COLS; ++c) {
@@ -225,9 +236,11 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
               int pos = k - 1;
               while (pos > 0 && L[pos - 1] > v) {
                 L[pos] = L[pos - 1];
+                if constexpr (MODE == CL_KNN) J[pos] = J[pos - 1];
                 --pos;
               }
               L[pos] = v;
+              if constexpr (MODE == CL_KNN) J[pos] = j0 + c;
               kth = L[k - 1];
             }
           }
@@ -253,11 +266,16 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   if constexpr (MODE == CL_SUMS) {
     if (t < ROWS && i0 + t < n && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
   }
-  if constexpr (MODE == CL_CORE) {
+  if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
     if (t < ROWS && i0 + t < n) {
       const float* L = extra + t * p.kl;
       float* o = p.part_lists + ((size_t)blockIdx.y * n + i0 + t) * p.k;
       for (int q = 0; q < p.k; ++q) o[q] = L[q];
+      if constexpr (MODE == CL_KNN) {
+        const int* J = extra_j + t * p.kl;
+        int* oj = p.part_idx + ((size_t)blockIdx.y * n + i0 + t) * p.k;
+        for (int q = 0; q < p.k; ++q) oj[q] = J[q];
+      }
     }
   }
   if constexpr (MODE == CL_MINEDGE) {
@@ -306,6 +324,43 @@ __global__ __launch_bounds__(CL_THREADS) void cl_core_merge(const float* __restr
       }
     }
     if (rank == k - 1) out[row] = v;
+  }
+}
+
+// The k smallest of the slices' k-lists of a row under (distance, index), in that order: one wave per row, a lane per
+// candidate.  Every list is sorted by (distance, index), so a candidate's rank is the sum over the lists of the number
+// of entries before it (a binary search each); the -1 pads of a short slice sit at +inf behind every row index and are
+// told apart by their position.  The n >= k real candidates fill the ranks 0 .. k-1, each exactly once.
+__global__ __launch_bounds__(CL_THREADS) void cl_knn_merge(const float* __restrict__ pd, const int* __restrict__ pj,
+                                                           int slices, int n, int k, float* __restrict__ out_d,
+                                                           int* __restrict__ out_j) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (CL_THREADS / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (row >= n) return;
+  const int m = slices * k;
+  for (int q = lane; q < m; q += 64) {
+    const int sq = q / k;
+    const size_t at = ((size_t)sq * n + row) * k + q % k;
+    const float v = pd[at];
+    const int j = pj[at];
+    if (j < 0) continue;
+    int rank = 0;
+    for (int s = 0; s < slices && rank < k; ++s) {
+      const float* ld = pd + ((size_t)s * n + row) * k;
+      const int* lj = pj + ((size_t)s * n + row) * k;
+      int lo = 0, hi = k;  // first entry of list s that is not before (v, j)
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float u = ld[mid];
+        const int ju = lj[mid];
+        if (ju >= 0 && (u < v || (u == v && ju < j))) lo = mid + 1; else hi = mid;
+      }
+      rank += lo;
+    }
+    if (rank < k) {
+      out_d[(size_t)row * k + rank] = v;
+      out_j[(size_t)row * k + rank] = j;
+    }
   }
 }
 
@@ -395,6 +450,38 @@ extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k,
   const int rc = cl_launch<CL_CORE, 8>(a, g, metric, st);
   if (rc != WM_OK) return rc;
   cl_core_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, g.slices, n, k, out);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_knn_graph_workspace_bytes(int n, int d, int k) {
+  if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
+  return (size_t)cl_grid(n, 128, true).slices * n * k * 8 + 256;
+}
+
+extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(x && dist && idx && workspace, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
+  const ClGrid g = cl_grid(n, 128, true);
+  const size_t entries = (size_t)g.slices * n * k;
+  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.k = k;
+  a.kl = k | 1;
+  a.part_lists = static_cast<float*>(workspace);
+  a.part_idx = reinterpret_cast<int*>(a.part_lists + entries);
+  const int rc = cl_launch<CL_KNN, 8>(a, g, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_knn_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, g.slices, n, k, dist, idx);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

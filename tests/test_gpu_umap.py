@@ -1,0 +1,423 @@
+"""GPU checks of the UMAP kernels (csrc/cluster.hip: wm_knn_graph; csrc/umap.hip) and their Python layer
+(manifold.py, scripts/embedding_umap_amd.py) against the float64 reference of tests/test_umap_cpu.py.
+
+Bounds are derived, not tuned; u = 2^-24.
+  kNN graph      the distance function is cluster.hip's: relative error at most eps(d) = (d + 3) u, duplicates at exactly 0.
+  sigma          the kernel stops its double-precision bisection at |S(sigma) - log2 k| < 1e-5 and then rounds sigma to
+                 float32.  dS/dsigma * sigma = sum_j x_j exp(-x_j) with x_j = (d_j - rho) / sigma, at most (k - 1) / e, so
+                 the rounding moves S by at most (k - 1) u / e; the kernel's exp and numpy's differ by an ulp of double
+                 per term, (k - 1) 2^-50 covers that.  Rows whose bisection ends below the floor carry the floor instead:
+                 float32(1e-3 * mean), whose double-precision mean may differ from numpy's in the last bit, so one
+                 float32 ulp (2 u relative) is allowed there.
+  weights        exp in double at the returned (rho, sigma) -- the argument is exact up to one double rounding of the
+                 quotient, at most 2^-53 * 1000 relative in the result -- rounded once to float32: u (1 + 2^-10) relative,
+                 plus 2^-150 absolute where the result is subnormal.
+  union          the entry is formed in double and rounded once: u relative (the issue allows 3 u).
+  layout         see `layout_bound`.
+"""
+import importlib.util
+import json
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+from parity_log import parity
+
+from test_cluster_cpu import lattice_points, pairwise64
+from test_umap_cpu import ref_alpha, ref_fit, ref_layout_epoch, ref_rates, ref_smooth_knn, ref_union, ref_weights
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+ROOT = Path(__file__).resolve().parent.parent
+GOLDEN = ROOT / "tests" / "golden"
+U = 2.0 ** -24
+METRICS = ["euclidean", "manhattan"]
+KS = (1, 2, 15, 16, 30, 64)
+
+
+def eps(d):
+    return (d + 3) * U
+
+
+def rows(n, d, seed):
+    """float32 rows with exact duplicates among them (rows 3, 5, 7 and the last equal row 0 when they exist)."""
+    x = np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
+    for i in (3, 5, 7, n - 1):
+        if 0 < i < n:
+            x[i] = x[0]
+    return x
+
+
+_CACHE = {}
+
+
+def reference(n, d, metric):
+    """(x float32, float64 distance matrix), computed once per shape and shared."""
+    key = (n, d, metric)
+    if key not in _CACHE:
+        x = rows(n, d, 1000 * n + d)
+        _CACHE[key] = (x, pairwise64(x, metric))
+    return _CACHE[key]
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def max_rel(got, want):
+    """Largest relative error where the reference is positive; where it is exactly 0 so must the result be."""
+    got, want = np.asarray(got, dtype=np.float64).ravel(), np.asarray(want, dtype=np.float64).ravel()
+    zero = want == 0
+    assert (got[zero] == 0).all(), "an exactly zero reference needs an exactly zero result"
+    return float(np.max(np.abs(got - want)[~zero] / want[~zero])) if (~zero).any() else 0.0
+
+
+def bits(t):
+    return t.cpu().numpy().view(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ kNN graph
+
+
+@pytest.mark.parametrize("d", [4, 52, 512])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_knn_graph_against_float64(n, d):
+    from ssl_wafermap_amd import _lib, cluster, manifold
+
+    for metric in METRICS:
+        x, dist = reference(n, d, metric)
+        ordered = np.sort(dist, axis=1)
+        xd = dev(x)
+        for k in [k for k in KS if k <= n]:
+            got_d, got_i = manifold.knn_graph(xd, k, metric)
+            assert got_d.shape == got_i.shape == (n, k) and got_d.dtype == torch.float32 and got_i.dtype == torch.int32
+            gd, gi = got_d.cpu().numpy().astype(np.float64), got_i.cpu().numpy().astype(np.int64)
+            assert gi.min() >= 0 and gi.max() < n
+            assert all(np.unique(r).size == k for r in gi), "a row names a neighbour twice"
+            assert (np.diff(gd, axis=1) >= 0).all()
+            tie = np.diff(gd, axis=1) == 0
+            assert (np.diff(gi, axis=1)[tie] > 0).all(), "equal distances must be ordered by index"
+            assert (gd[:, 0] == 0).all()  # the row itself (or an equal row before it) leads
+            parity(f"knn_graph dist {metric} n={n} d={d} k={k} rel", max_rel(gd, ordered[:, :k]), eps(d))
+            # near-ties may swap, nothing else: the true distance of the index at a rank against the true rank statistic
+            parity(f"knn_graph index {metric} n={n} d={d} k={k} rel",
+                   max_rel(np.take_along_axis(dist, gi, axis=1), ordered[:, :k]), eps(d))
+            again_d, again_i = manifold.knn_graph(xd, k, metric)
+            assert np.array_equal(bits(got_d), bits(again_d)) and np.array_equal(bits(got_i), bits(again_i))
+        # k = n + 1: the argument error code, from the entry point itself
+        lib = _lib.load()
+        ws = torch.empty(max(lib.wm_knn_graph_workspace_bytes(n, d, 1), 16), dtype=torch.uint8, device=DEV)
+        od = torch.empty((n, n + 1), dtype=torch.float32, device=DEV)
+        oi = torch.empty((n, n + 1), dtype=torch.int32, device=DEV)
+        rc = lib.wm_knn_graph(xd.data_ptr(), n, d, cluster.METRICS[metric], n + 1, od.data_ptr(), oi.data_ptr(),
+                              ws.data_ptr(), ws.numel(), 0)
+        assert rc == -1
+        with pytest.raises(ValueError):
+            manifold.knn_graph(xd, n + 1, metric)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_knn_graph_exact_on_a_lattice(metric):
+    """Every distance on the integer lattice is exact in float32 (the Euclidean root rounded correctly by numpy as by
+    the kernel's sqrtf), so indices and distances equal the float32 brute force under the (distance, index) order."""
+    from ssl_wafermap_amd import manifold
+
+    x = lattice_points().astype(np.float32)
+    n = x.shape[0]
+    diff = x[:, None, :] - x[None, :, :]
+    dist = np.sqrt((diff * diff).sum(-1, dtype=np.float32)) if metric == "euclidean" else np.abs(diff).sum(-1, dtype=np.float32)
+    order = np.stack([np.lexsort((np.arange(n), dist[i])) for i in range(n)])
+    for k in KS:
+        got_d, got_i = manifold.knn_graph(dev(x), k, metric)
+        assert np.array_equal(got_i.cpu().numpy(), order[:, :k])
+        assert np.array_equal(got_d.cpu().numpy(), np.take_along_axis(dist, order[:, :k], axis=1))
+
+
+# ------------------------------------------------------------------------------------------------ rho, sigma, weights
+
+
+def clumped(n, d, clump, seed):
+    """Rows of which the first `clump` are one and the same point (all their neighbours are duplicates when
+    k <= clump: rho = 0)."""
+    x = rows(n, d, seed)
+    x[:clump] = x[0]
+    return x
+
+
+@pytest.mark.parametrize("n,d,k,clump", [(257, 52, 15, 0), (65, 4, 30, 0), (300, 52, 15, 20), (65, 512, 2, 0), (63, 4, 2, 5),
+                                         (64, 4, 64, 0)])
+def test_smooth_knn_against_float64(n, d, k, clump):
+    """rho exactly; S(sigma) within 1e-5 + (k - 1) (u / e + 2^-50) of log2 k, or sigma at its floor within one float32
+    ulp; weights within u (1 + 2^-10) relative + 2^-150 of the float64 formula at the kernel's (rho, sigma)."""
+    from ssl_wafermap_amd import manifold
+
+    x = clumped(n, d, clump, n + d + k) if clump else rows(n, d, n + d + k)
+    dist_t, idx_t = manifold.knn_graph(dev(x), k)
+    rho_t, sigma_t, w_t = manifold.smooth_knn(dist_t, idx_t)
+    dist, idx = dist_t.cpu().numpy().astype(np.float64), idx_t.cpu().numpy()
+    rho, sigma, w = rho_t.cpu().numpy(), sigma_t.cpu().numpy(), w_t.cpu().numpy()
+    assert rho.dtype == sigma.dtype == w.dtype == np.float32
+    first_pos = np.array([r[r > 0][0] if (r > 0).any() else 0.0 for r in dist])
+    assert np.array_equal(rho.astype(np.float64), first_pos)
+    if clump >= k:
+        assert (rho[:clump] == 0).all()
+    floor = np.where(first_pos > 0, 1e-3 * dist.mean(axis=1), 1e-3 * dist.mean())
+    floor32 = floor.astype(np.float32).astype(np.float64)
+    s64 = sigma.astype(np.float64)
+    assert (s64 > 0).all() and (s64 >= floor32 * (1 - 2 * U)).all()
+    pinned = s64 <= floor32 * (1 + 2 * U)
+    d_rel = dist[:, 1:] - first_pos[:, None]
+    sums = np.where(d_rel > 0, np.exp(-np.maximum(d_rel, 0) / s64[:, None]), 1.0).sum(axis=1)
+    free = ~pinned
+    if free.any():
+        parity(f"smooth_knn sum n={n} d={d} k={k} abs", np.abs(sums[free] - np.log2(k)).max(),
+               1e-5 + (k - 1) * (U / np.e + 2.0 ** -50))
+    if clump >= k and k > 2:
+        assert pinned[:clump].all(), "rows whose neighbours are all duplicates cannot reach log2 k: the floor holds"
+    want = ref_weights(dist, idx, first_pos, s64)
+    bound = U * (1 + 2.0 ** -10) * want + 2.0 ** -150
+    assert (w[want == 0] == 0).all() and (w[idx == np.arange(n)[:, None]] == 0).all()
+    parity(f"smooth_knn weights n={n} d={d} k={k} (fraction of the bound)", (np.abs(w - want) / bound).max(), 1.0)
+    assert np.array_equal(ref_smooth_knn(dist, idx)[0], first_pos)  # (the reference's own rho)
+    again = manifold.smooth_knn(dist_t, idx_t)
+    assert all(np.array_equal(bits(p), bits(q)) for p, q in zip((rho_t, sigma_t, w_t), again))
+
+
+# ------------------------------------------------------------------------------------------------ union
+
+
+@pytest.mark.parametrize("n,d,k", [(65, 4, 15), (300, 52, 15), (257, 52, 30), (63, 4, 2)])
+def test_union_against_scipy(n, d, k):
+    from ssl_wafermap_amd import manifold
+
+    x = rows(n, d, 5 * n + k)
+    dist_t, idx_t = manifold.knn_graph(dev(x), k)
+    _, _, w_t = manifold.smooth_knn(dist_t, idx_t)
+    g = manifold.fuzzy_union(idx_t, w_t)
+    assert g.indptr.dtype == g.indices.dtype == torch.int32 and g.data.dtype == torch.float32 and g.data.is_cuda
+    ref = ref_union(idx_t.cpu().numpy(), w_t.cpu().numpy())
+    indptr, indices, data = g.indptr.cpu().numpy(), g.indices.cpu().numpy(), g.data.cpu().numpy()
+    assert np.array_equal(indptr, ref.indptr) and np.array_equal(indices, ref.indices)
+    for i in range(n):
+        assert (np.diff(indices[indptr[i]:indptr[i + 1]]) > 0).all(), "columns must be sorted within a row"
+    parity(f"union n={n} k={k} rel", max_rel(data, ref.data), 3 * U)
+    dense = g.to_scipy().toarray()
+    assert np.array_equal(dense.view(np.int32), dense.T.copy().view(np.int32)), "G must be symmetric in bits"
+    same = manifold.fuzzy_simplicial_set(dev(x), k)
+    assert np.array_equal(bits(same.data), bits(g.data)) and np.array_equal(same.indices.cpu().numpy(), indices)
+    q = manifold.sample_rates(g.data).cpu().numpy()
+    assert np.array_equal(q, ref_rates(data)) and q.max() == 65536 and q.min() >= 0
+
+
+# ------------------------------------------------------------------------------------------------ layout
+
+
+def layout_case(n, dim, seed):
+    """A symmetric graph with skewed degrees, an isolated last vertex and rates from {65536, 32768, 21845, 1} and
+    random ones; positions with a coincident pair (0, 1), a tight clump (a fifth of the vertices within 0.03 of
+    each other, so that sampled negatives repel hard enough to clip) and a far vertex."""
+    rng = np.random.default_rng(seed)
+    pairs = {(0, 1)}
+    if n > 2:
+        for i in range(n - 1):
+            for j in rng.choice(n - 1, size=int(rng.integers(1, 4 if i % 7 else 40)), replace=False):
+                if i != j:
+                    pairs.add((min(i, int(j)), max(i, int(j))))
+    pairs = sorted(pairs)
+    special = [65536, 32768, 21845, 1]
+    rate = {p: special[t] if t < 4 else int(rng.choice(special + [int(rng.integers(0, 65537))])) for t, p in enumerate(pairs)}
+    adj = [[] for _ in range(n)]
+    for (i, j) in pairs:
+        adj[i].append((j, rate[(i, j)]))
+        adj[j].append((i, rate[(i, j)]))
+    indptr = np.zeros(n + 1, dtype=np.int32)
+    indices, q = [], []
+    for i in range(n):
+        for j, r in sorted(adj[i]):
+            indices.append(j)
+            q.append(r)
+        indptr[i + 1] = len(indices)
+    y = (3.0 * rng.standard_normal((n, dim))).astype(np.float32)
+    if n == 2:
+        y[1] = y[0]
+        y[1, 0] += np.float32(0.02)  # (two vertices: the close pair whose repulsion clips)
+    else:
+        y[1] = y[0]
+        clump = np.arange(8, 8 + n // 5)
+        y[clump] = y[8] + (0.03 / np.sqrt(dim) * rng.uniform(-1, 1, (clump.size, dim))).astype(np.float32)
+        y[4] = y[2] + np.float32(1000.0)
+    return indptr, np.asarray(indices, dtype=np.int32), np.asarray(q, dtype=np.int32), y
+
+
+def layout_bound(y_ref, mag, alpha, deg, dim, b, rate):
+    """Bound on |kernel - float64 reference| of one epoch, per vertex and component, with a and b exactly representable
+    in float32 (the test rounds them first).  Roundings of one term, in units of u = 2^-24 relative to the unclipped
+    term, with L = log2 of the padded dimension DP:
+      d_c = y_i[c] - y_j[c]: 1;   r: the squares carry 2 from d_c, 1 from the product, L from the butterfly: e_r = 3 + L;
+      p = powf(r, b): b e_r from r plus P = 4 for powf itself (the HIP documentation lists 1 ulp = 2 u; twice that);
+      attraction (c_att p) / (r (a p + 1)) d_c: c_att 1, product 1, p; a p + 1: p and 2; times r: e_r and 1; quotient 1;
+        times d_c: 1 and 1 -- (2b + 1) e_r + 2 P + 8;
+      repulsion c_rep / ((0.001f + r)(a p + 1)) d_c: c_rep 1; 0.001f + r: e_r and 2; a p + 1: p and 2; product 1;
+        quotient 1; times d_c: 1 and 1 -- (b + 1) e_r + P + 9.
+    E = (2b + 1) e_r + 2 P + 10 covers both.  clip is 1-Lipschitz and the doubling is exact, so a term is off by at most
+    E u |term|.  The terms are added one at a time: a lane adds 1 + R terms per pass over ceil(deg / EPP) passes
+    (EPP = 64 / DP entries per pass), then EPP lanes are added: N = ceil(deg / EPP)(1 + R) + EPP additions, each off by
+    at most u times the sum of |terms|.  alpha * sum: 1.  The final y + alpha sum: u |y'|.  Second-order terms: 1 %.
+      |error| <= 1.01 u [(E + N + 1) alpha sum|terms| + |y'|]"""
+    dp = 1 << int(np.ceil(np.log2(dim)))
+    e_r = 3 + np.log2(dp)
+    big_e = (2 * b + 1) * e_r + 2 * 4 + 10
+    epp = 64 // dp
+    adds = np.ceil(deg / epp) * (1 + rate) + epp
+    return 1.01 * U * ((big_e + adds[:, None] + 1) * alpha * mag + np.abs(y_ref))
+
+
+AB = [(float(np.float32(1.57694)), float(np.float32(0.89506))), (float(np.float32(1.93281)), float(np.float32(0.79049)))]
+
+
+@pytest.mark.parametrize("dim", [1, 2, 3, 50, 64])
+@pytest.mark.parametrize("n", [2, 65, 300])
+def test_layout_teacher_forced_against_float64(n, dim):
+    """20 epochs, one call each; after every epoch the kernel's positions against one float64 reference epoch started
+    from the kernel's own previous positions (so no chaos enters the bound, and a missed or extra sample is an O(1)
+    error).  Then: one call over [0, 20) = calls over [0, 7) + [7, 20) = a second run, in bits; the isolated vertex
+    never moves."""
+    from ssl_wafermap_amd import manifold
+
+    a, b = AB[(n + dim) % 2]
+    gamma, lr, seed, rate, epochs = 1.0, 1.0, 1234 + n, 5, 20
+    indptr, indices, q, y0 = layout_case(n, dim, 17 * n + dim)
+    assert {65536, 32768, 21845, 1} <= set(q.tolist()) or n == 2
+    ip, ix, qd = dev(indptr), dev(indices), dev(q)
+    deg = np.diff(indptr).astype(np.float64)
+    kw = dict(gamma=gamma, learning_rate=lr, seed=seed, negative_sample_rate=rate)
+    y = dev(y0)
+    worst, clipped, hits = 0.0, 0, 0
+    for ep in range(epochs):
+        nxt = manifold.optimize_layout(y, ip, ix, qd, a, b, epochs, ep, ep + 1, **kw)
+        prev = y.cpu().numpy()
+        ref, mag, hit, clip = ref_layout_epoch(prev, indptr, indices, q, a, b, gamma, ref_alpha(lr, ep, epochs), seed, ep, rate)
+        got = nxt.cpu().numpy()
+        assert np.isfinite(got).all()
+        bound = layout_bound(ref, mag, ref_alpha(lr, ep, epochs), deg, dim, b, rate)
+        worst = max(worst, float((np.abs(got - ref) / bound).max()))
+        clipped += clip
+        hits += int(hit.sum())
+        y = nxt
+    assert hits > 0 and clipped > 0, "the case must sample entries and clip gradients"
+    parity(f"layout n={n} dim={dim} (fraction of the bound)", worst, 1.0)
+    whole = manifold.optimize_layout(dev(y0), ip, ix, qd, a, b, epochs, 0, epochs, **kw)
+    part = manifold.optimize_layout(dev(y0), ip, ix, qd, a, b, epochs, 0, 7, **kw)
+    part = manifold.optimize_layout(part, ip, ix, qd, a, b, epochs, 7, epochs, **kw)
+    assert np.array_equal(bits(whole), bits(part)) and np.array_equal(bits(whole), bits(y))
+    assert np.array_equal(bits(whole), bits(manifold.optimize_layout(dev(y0), ip, ix, qd, a, b, epochs, **kw)))
+    if n > 2:
+        assert deg[n - 1] == 0 and np.array_equal(bits(whole)[n - 1], y0.view(np.int32)[n - 1])
+
+
+def test_layout_rejects_a_graph_that_points_outside():
+    from ssl_wafermap_amd import manifold
+
+    y = dev(np.zeros((4, 2), dtype=np.float32))
+    ip = dev(np.array([0, 1, 1, 1, 1], dtype=np.int32))
+    one = dev(np.array([65536], dtype=np.int32))
+    with pytest.raises(ValueError):
+        manifold.optimize_layout(y, ip, dev(np.array([4], dtype=np.int32)), one, 1.5, 0.9, 10)
+    with pytest.raises(ValueError):
+        manifold.optimize_layout(y, ip, dev(np.array([-1], dtype=np.int32)), one, 1.5, 0.9, 10)
+    with pytest.raises(ValueError):
+        manifold.optimize_layout(dev(np.zeros((4, 65), dtype=np.float32)), ip, dev(np.array([1], dtype=np.int32)), one, 1.5, 0.9, 10)
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+
+
+@pytest.fixture(scope="module")
+def wafer_rows():
+    """1 500 rows of the golden embeddings by default_rng(0).permutation, standardised (float32), and their labels."""
+    z = np.load(GOLDEN / "simsiam_preds_subset.npz")
+    emb = z["embeddings"].astype(np.float64)
+    sel = np.random.default_rng(0).permutation(emb.shape[0])[:1500]
+    x = emb[sel]
+    std = x.std(axis=0)
+    return ((x - x.mean(axis=0)) / np.where(std > 0, std, 1.0)).astype(np.float32), np.asarray(z["labels"])[sel]
+
+
+def test_fit_transform_keeps_neighbourhoods_like_the_float64_reference(wafer_rows):
+    """k = 15, 2-D, init="random", 200 epochs on 1 500 standardised golden rows: sklearn trustworthiness(15) of the GPU
+    embedding must reach that of the float64 reference run with the same seed minus 0.005.  The layout is chaotic, so the
+    two runs diverge at rounding level and differ like two seeds do: the reference scored 0.9880, 0.9877 and 0.9880
+    for seeds 0, 1 and 2 on these rows (spread 0.0003; the issue's prototype: 0.9870-0.9881 over six seeds), PCA to 2-D
+    scores 0.9602 and a random layout about 0.5; 0.005 is more than four times the spread and five times below the
+    gap to PCA.  Measured on the MI355X: 0.9890 against the reference's 0.9880 at seed 0."""
+    from sklearn.manifold import trustworthiness
+
+    from ssl_wafermap_amd import manifold
+
+    x, _ = wafer_rows
+    model = manifold.UMAP(n_neighbors=15, n_components=2, init="random", n_epochs=200, random_state=0)
+    got = model.fit_transform(dev(x))
+    assert got.shape == (1500, 2) and got.dtype == torch.float32 and got.is_cuda and model.embedding_ is got
+    assert model.graph_.shape == (1500, 1500)
+    ref = ref_fit(x, 15, 2, model.a_, model.b_, 200, 0)
+    t_ref = trustworthiness(x, ref, n_neighbors=15)
+    t_got = trustworthiness(x, got.cpu().numpy(), n_neighbors=15)
+    parity("umap trustworthiness(15), 1500 golden rows (bound: float64 reference - 0.005)", t_got, t_ref - 0.005, higher=True,
+           note=f"float64 reference {t_ref:.4f}")
+    again = manifold.UMAP(n_neighbors=15, n_components=2, init="random", n_epochs=200, random_state=0).fit_transform(dev(x))
+    assert np.array_equal(bits(got), bits(again)), "two fits must give the same bits"
+
+
+@pytest.mark.parametrize("init", ["spectral", "pca"])
+def test_initialisations_end_no_worse_than_pca(wafer_rows, init):
+    """The initial layout fills [0, 10] in every dimension, and 200 epochs from it keep neighbourhoods at least as
+    well as the 2-D PCA projection does (0.9602 on these rows against the reference's 0.988: a wide margin)."""
+    from sklearn.manifold import trustworthiness
+
+    from ssl_wafermap_amd import manifold
+
+    x = wafer_rows[0]
+    xd = dev(x)
+    model = manifold.UMAP(n_neighbors=15, init=init, n_epochs=200)
+    start = model._initial(xd, manifold.fuzzy_simplicial_set(xd, 15)).cpu().numpy()
+    assert start.shape == (1500, 2) and start.dtype == np.float32
+    assert (start.min(axis=0) == 0).all() and (start.max(axis=0) == 10).all()
+    got = model.fit_transform(xd).cpu().numpy()
+    assert np.isfinite(got).all() and got.shape == (1500, 2)
+    xc = x.astype(np.float64) - x.astype(np.float64).mean(axis=0)
+    u, sv, _ = np.linalg.svd(xc, full_matrices=False)
+    parity(f"umap init={init} trustworthiness(15), 1500 rows (bound: PCA to 2-D)", trustworthiness(x, got, n_neighbors=15),
+           trustworthiness(x, u[:, :2] * sv[:2], n_neighbors=15), higher=True)
+
+
+def test_reduction_hands_over_to_hdbscan(wafer_rows):
+    """Notebook 3.2's reduce-then-cluster flow: UMAP(n_neighbors=30, n_components=50, min_dist=0) -> HDBSCAN."""
+    from ssl_wafermap_amd import cluster, manifold
+
+    x = wafer_rows[0][:600]
+    reduced = manifold.UMAP(n_neighbors=30, n_components=50, min_dist=0.0).fit_transform(dev(x))
+    assert reduced.shape == (600, 50) and bool(torch.isfinite(reduced).all())
+    labels = cluster.HDBSCAN(min_cluster_size=15).fit_predict(reduced)
+    assert labels.shape == (600,) and labels.max() + 1 >= 2
+
+
+def test_umap_script_on_wafer_embeddings(tmp_path):
+    spec = importlib.util.spec_from_file_location("embedding_umap_amd", ROOT / "scripts" / "embedding_umap_amd.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    summary = mod.main(["--embeddings", str(GOLDEN / "simsiam_preds_subset.npz"), "--rows", "600", "--epochs", "100",
+                        "--out", str(tmp_path)])
+    z = np.load(tmp_path / "reduced.npz")
+    assert z["embeddings"].shape == (600, 2) and z["embeddings"].dtype == np.float32 and z["labels"].shape == (600,)
+    assert np.isfinite(z["embeddings"]).all() and (tmp_path / "umap.png").stat().st_size > 0
+    on_disk = json.loads((tmp_path / "summary.json").read_text())
+    assert on_disk["n"] == summary["n"] == 600 and 0.9 <= on_disk["trustworthiness"] <= 1.0
+    assert {"knn_graph", "fuzzy_set", "init", "layout"} <= set(on_disk["seconds"])
+    # the reduced matrix is what the clustering script reads
+    cl = importlib.util.spec_from_file_location("embedding_clustering_amd", ROOT / "scripts" / "embedding_clustering_amd.py")
+    cmod = importlib.util.module_from_spec(cl)
+    cl.loader.exec_module(cmod)
+    emb, lab = cmod.load_embeddings(tmp_path / "reduced.npz")
+    assert emb.shape == (600, 2) and lab.shape == (600,)

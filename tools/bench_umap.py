@@ -1,0 +1,151 @@
+"""UMAP micro-benchmark (manifold.py; csrc/cluster.hip wm_knn_graph, csrc/umap.hip): the kNN graph, the fuzzy
+simplicial set and the layout epochs at the golden 12 449 x 512 embeddings and at a synthetic 172 950 x 512 matrix
+(the size of the reference's full WM-811K dump), on one MI355X.
+
+    python tools/bench_umap.py [--out profiles/umap_bench.md] [--reps 5] [--sizes golden synthetic]
+
+Device events around the Python calls, one warm-up call per shape, then --reps calls: median (min .. max).  The kNN
+pass is set next to wm_core_distance on the same rows and k: both are one all-pairs pass of 3 n^2 d float32 operations
+on the vector ALU (157.3 TF peak).  The layout is reported per epoch and as sampled edges per second (an edge
+sample = one attraction and R negative samples, i.e. 1 + R row gathers).  Worst parity figures of the UMAP tests are
+appended when the parity log of tests/parity_log.py exists (tests/test_gpu_umap.py writes into it)."""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from ssl_wafermap_amd import cluster, manifold  # noqa: E402
+from ssl_wafermap_amd.retrieval import StandardScaler  # noqa: E402
+
+PEAK_F32_VALU = 157.3e12
+DEV = torch.device("cuda:0")
+
+
+def timed(fn, reps):
+    """(median, min, max) milliseconds of fn() by device events after one warm-up call; and fn's last result."""
+    out = fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return (statistics.median(ms), min(ms), max(ms)), out
+
+
+def fmt(t):
+    return f"{t[0]:.2f} ms ({t[1]:.2f} .. {t[2]:.2f})"
+
+
+def synthetic(n, d, seed):
+    """Seeded mixture of 38 Gaussians (the MixedWM38 class count), float32 on the device."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    centers = 4.0 * torch.randn(38, d, generator=g, device=DEV)
+    which = torch.randint(0, 38, (n,), generator=g, device=DEV)
+    return (centers[which] + torch.randn(n, d, generator=g, device=DEV)).contiguous()
+
+
+def bench_shape(name, x, k, reps, lines):
+    n, d = x.shape
+    flop = 3.0 * n * n * d
+    t_knn, (dist, idx) = timed(lambda: manifold.knn_graph(x, k), reps)
+    t_core, _ = timed(lambda: cluster.core_distances(x, k), reps)
+    t_w, w = timed(lambda: manifold.smooth_knn(dist, idx)[2], reps)
+    t_u, graph = timed(lambda: manifold.fuzzy_union(idx, w), reps)
+    nnz = int(graph.indices.numel())
+    deg = torch.diff(graph.indptr.long())
+    q = manifold.sample_rates(graph.data)
+    lines += [f"## {name}: {n} x {d}, k = {k}", "",
+              f"Graph: {nnz} entries, degree {int(deg.min())} .. {int(deg.max())} (median {int(deg.median())}).", "",
+              "| step | time | TF | share of 157.3 TF |", "|---|---|---|---|",
+              f"| kNN graph with indices (`wm_knn_graph`) | {fmt(t_knn)} | {flop / t_knn[0] / 1e9:.1f} | {flop / PEAK_F32_VALU * 1e3 / t_knn[0]:.2f} |",
+              f"| core distance, same rows and k (`wm_core_distance`) | {fmt(t_core)} | {flop / t_core[0] / 1e9:.1f} | {flop / PEAK_F32_VALU * 1e3 / t_core[0]:.2f} |",
+              f"| rho, sigma, weights (`wm_umap_smooth_knn`) | {fmt(t_w)} | | |",
+              f"| union to CSR (torch sort / unique / searchsorted) | {fmt(t_u)} | | |", "",
+              f"kNN graph / core distance: {t_knn[0] / t_core[0]:.2f} x.", ""]
+    rec = {"shape": name, "n": n, "d": d, "k": k, "nnz": nnz, "knn_ms": t_knn[0], "core_ms": t_core[0], "weights_ms": t_w[0],
+           "union_ms": t_u[0], "layout": []}
+    n_epochs = 500 if n <= 10000 else 200
+    a, b = manifold.find_ab_params(1.0, 0.1)
+    lines += ["| layout | epochs | time | per epoch | sampled edges | edge samples / s |", "|---|---|---|---|---|---|"]
+    samples = int(((n_epochs * q.long()) >> 16).sum())
+    for dim in (2, 50):
+        g = torch.Generator(device="cuda").manual_seed(dim)
+        y0 = (10.0 * torch.rand(n, dim, generator=g, device=DEV)).contiguous()
+        t_l, _ = timed(lambda: manifold.optimize_layout(y0, graph.indptr, graph.indices, q, a, b, n_epochs), max(2, reps // 2))
+        lines.append(f"| {dim}-D (`wm_umap_layout`) | {n_epochs} | {fmt(t_l)} | {t_l[0] / n_epochs * 1e3:.1f} us | {samples} | "
+                     f"{samples / t_l[0] * 1e3:.3g} |")
+        rec["layout"].append({"dim": dim, "epochs": n_epochs, "ms": t_l[0], "edge_samples": samples,
+                              "edge_samples_per_s": samples / t_l[0] * 1e3})
+    lines.append("")
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def parity_section(lines):
+    sys.path.insert(0, str(ROOT / "tests"))
+    from parity_log import _PATH  # (relative to the directory the tests ran from: the repository root)
+
+    path = ROOT / _PATH
+    if not path.exists():
+        return
+    worst = {}
+    for ln in path.read_text().splitlines():
+        r = json.loads(ln)
+        if "test_gpu_umap" not in r.get("test", "") or r.get("generic"):
+            continue
+        key = r["name"].split(" n=")[0].split(" init=")[0]
+        frac = (r["bound"] / r["measured"] if r["higher"] else r["measured"] / r["bound"]) if r["bound"] and r["measured"] else 0.0
+        cur = worst.setdefault(key, {"count": 0, "frac": 0.0, "measured": None, "bound": None})
+        cur["count"] += 1
+        if frac >= cur["frac"]:
+            cur.update(frac=frac, measured=r["measured"], bound=r["bound"])
+    if worst:
+        lines += ["## Parity (tests/test_gpu_umap.py, this run)", "",
+                  "Worst comparison per check; the bounds are derived in the test module.", "",
+                  "| check | comparisons | worst measured | its bound | fraction of the bound |", "|---|---|---|---|---|"]
+        for key, c in worst.items():
+            lines.append(f"| {key} | {c['count']} | {c['measured']:.6g} | {c['bound']:.6g} | {c['frac']:.3f} |")
+        lines.append("")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "umap_bench.md"))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", nargs="+", default=["golden", "synthetic"], choices=["golden", "synthetic"])
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_umap.py needs the GPU: nothing is measured without one")
+    lines = ["# UMAP: kNN graph, fuzzy simplicial set, layout", "",
+             "Scope: `csrc/cluster.hip` (`wm_knn_graph`), `csrc/umap.hip` (`wm_umap_smooth_knn`, `wm_umap_layout`), `manifold.py`.",
+             "One MI355X.  Written by `tools/bench_umap.py`: device events around the Python call (output allocation and the",
+             "small merge kernel included), one warm-up call, then the median (min .. max) of the repeats.  One all-pairs",
+             "pass is 3 n^2 d float32 operations; the share of peak is against the 157.3 TF vector rate.  Per-kernel times",
+             "from a profiler trace: not measured.", ""]
+    recs = []
+    if "golden" in a.sizes:
+        emb = np.load(ROOT / "tests" / "golden" / "simsiam_preds_subset.npz")["embeddings"].astype(np.float32)
+        x = StandardScaler().fit_transform(torch.from_numpy(emb).to(DEV))
+        recs.append(bench_shape("golden SimSiam embeddings, standardised", x, 15, a.reps, lines))
+    if "synthetic" in a.sizes:
+        recs.append(bench_shape("synthetic mixture of 38 Gaussians", synthetic(172950, 512, 0), 15, max(2, a.reps // 2), lines))
+    parity_section(lines)
+    out = Path(a.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+    print(f"wrote {out}")
+    return recs
+
+
+if __name__ == "__main__":
+    main()
