@@ -798,6 +798,33 @@ int wm_umap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t*
                    double a, double b, double gamma, double learning_rate, uint32_t seed, int epoch_begin, int epoch_end,
                    int n_epochs, int neg_rate, int* result_buffer, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DensMAP (umap.UMAP(densmap=True, ...): the density-preserving term added to the last dens_frac of the layout epochs);
+ * formulas, the live rule and the workspace layout are stated in csrc/umap.hip.
+ *
+ * wm_densmap_graph_radii: ro[i] = log(1e-8 + sum w_e dist_e^2 / sum w_e) over the live entries of row i of the graph
+ * (data = w, dists = max(d_ij, d_ji), both float32 [nnz]; live: (uint64)q_e * n_epochs >= 65536), log 1e-8 for a row
+ * without live entries.  Double inside, float32 [n] out. */
+int wm_densmap_graph_radii(const int32_t* indptr, const float* data, const float* dists, const uint32_t* q, int n, int n_epochs,
+                           float* ro, void* stream);
+/* The embedding's radii at the positions y float32 [n][dim]: d[i] = D_i = 2 sum_live 1 / (1 + a r^b) and
+ * re[i] = log(1e-8 + N_i / D_i), N_i = 2 sum_live r / (1 + a r^b), r = |y_i - y_j|^2 (log 1e-8 when D_i = 0).  One wave
+ * per vertex, double inside in a fixed order, float32 [n] out. */
+int wm_densmap_embedding_radii(const float* y, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n, int dim,
+                               double a, double b, int n_epochs, float* re, float* d, void* stream);
+/* wm_umap_layout with the density term: epochs ep of [epoch_begin, epoch_end) with dens_lambda > 0 and
+ * (ep + 1) / n_epochs > 1 - dens_frac first compute the embedding's radii, their mean, variance and covariance with
+ * rad (the standardised graph radii, float32 [n]) and the per-vertex terms into the workspace -- further launches on the
+ * stream, no atomics, no synchronisation -- and then run the layout kernel with the density term; every other epoch is
+ * wm_umap_layout's, bit for bit.  data float32 [nnz] > 0: the graph's weights; n >= 2; workspace: 16-byte aligned,
+ * wm_densmap_layout_workspace_bytes(n) bytes (0: unsupported n), owned by the caller; after a call that ran a phase
+ * epoch it holds the values the last phase epoch used. */
+size_t wm_densmap_layout_workspace_bytes(int n);
+int wm_densmap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q, const float* data,
+                      const float* rad, int n, int nnz, int dim, double a, double b, double gamma, double learning_rate,
+                      double dens_lambda, double dens_frac, double dens_var_shift, uint32_t seed, int epoch_begin, int epoch_end,
+                      int n_epochs, int neg_rate, void* workspace, size_t workspace_bytes, int* result_buffer, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -6,6 +6,7 @@ path (ssl_wafermap_amd.manifold).
     python scripts/embedding_umap_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
                                          [--neighbors 15] [--components 2] [--min-dist 0.1] [--epochs N]
                                          [--init spectral|pca|random] [--seed 0] [--no-scale] [--rows N] [--out DIR]
+                                         [--densmap [--dens-lambda 2.0] [--dens-frac 0.3] [--dens-var-shift 0.1]]
 
 What the notebooks do, and where it is here:
   StandardScaler().fit_transform(embeddings)        -> retrieval.StandardScaler (skipped with --no-scale)
@@ -13,14 +14,17 @@ What the notebooks do, and where it is here:
                                                      -> manifold.UMAP: exact kNN graph, fuzzy simplicial set and the
                                                         layout optimisation as HIP kernels
   the 2-D scatter coloured by failure code          -> umap.png (when --components 2)
-  3.2: HDBSCAN on UMAP(n_neighbors=30, min_dist=0, n_components=50).fit_transform(data)
-                                                     -> --neighbors 30 --min-dist 0 --components 50, then
-                                                        scripts/embedding_clustering_amd.py --embeddings DIR/reduced.npz
-                                                        --no-scale (the notebook's densmap=True density term is not
-                                                        built: the reduction is plain UMAP)
+  umap.UMAP(..., densmap=True, dens_lambda=L)        -> --densmap --dens-lambda L: manifold.DensMAP (the density term in
+                                                        the last --dens-frac of the epochs)
+  3.2: HDBSCAN on UMAP(n_neighbors=30, min_dist=0, n_components=50, densmap=True, dens_lambda=0.1).fit_transform(data)
+                                                     -> --neighbors 30 --min-dist 0 --components 50 --densmap
+                                                        --dens-lambda 0.1, then scripts/embedding_clustering_amd.py
+                                                        --embeddings DIR/reduced.npz --no-scale
 
-Outputs under --out: reduced.npz (`embeddings` float32 [n, components], `labels`: the format --embeddings reads),
-umap.png for two components, summary.json (seconds per stage; sklearn trustworthiness on at most 5 000 seeded rows).
+Outputs under --out: reduced.npz (`embeddings` float32 [n, components], `labels`: the format --embeddings reads; with
+--densmap also `rad_orig` and `rad_emb`, the log-radii of the data and of the embedding), umap.png for two components,
+summary.json (seconds per stage; sklearn trustworthiness on at most 5 000 seeded rows; with --densmap the Pearson
+correlation of the two radii as `radii_correlation`).
 """
 from __future__ import annotations
 
@@ -52,7 +56,11 @@ def main(argv=None) -> dict:
     ap.add_argument("--neighbors", type=int, default=15)
     ap.add_argument("--components", type=int, default=2)
     ap.add_argument("--min-dist", type=float, default=0.1)
-    ap.add_argument("--epochs", type=int, default=0, help="0: 500 for at most 10 000 rows, 200 above")
+    ap.add_argument("--epochs", type=int, default=0, help="0: 500 for at most 10 000 rows, 200 above (--densmap: 200 more)")
+    ap.add_argument("--densmap", action="store_true", help="DensMAP: add the density-preserving term")
+    ap.add_argument("--dens-lambda", type=float, default=2.0)
+    ap.add_argument("--dens-frac", type=float, default=0.3)
+    ap.add_argument("--dens-var-shift", type=float, default=0.1)
     ap.add_argument("--init", choices=["spectral", "pca", "random"], default="spectral")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rows", type=int, default=0, help="use the first N rows only")
@@ -66,8 +74,12 @@ def main(argv=None) -> dict:
     from ssl_wafermap_amd import manifold
     from ssl_wafermap_amd.retrieval import StandardScaler
 
-    model = manifold.UMAP(n_neighbors=a.neighbors, n_components=a.components, min_dist=a.min_dist, n_epochs=a.epochs or None,
-                          init=a.init, random_state=a.seed)
+    common = dict(n_neighbors=a.neighbors, n_components=a.components, min_dist=a.min_dist, n_epochs=a.epochs or None,
+                  init=a.init, random_state=a.seed)
+    if a.densmap:
+        model = manifold.DensMAP(dens_lambda=a.dens_lambda, dens_frac=a.dens_frac, dens_var_shift=a.dens_var_shift, **common)
+    else:
+        model = manifold.UMAP(**common)
     emb, truth = load_embeddings(a.embeddings)
     if a.rows:
         emb, truth = emb[:a.rows], truth[:a.rows]
@@ -91,15 +103,28 @@ def main(argv=None) -> dict:
 
     k = min(model.n_neighbors, n)
     dist, idx = timed("knn_graph", lambda: manifold.knn_graph(x, k, model.metric))
-    graph = timed("fuzzy_set", lambda: manifold.fuzzy_union(idx, manifold.smooth_knn(dist, idx)[2]))
+    graph = timed("fuzzy_set", lambda: manifold.fuzzy_union(idx, manifold.smooth_knn(dist, idx)[2], dist if a.densmap else None))
+    if a.densmap:
+        graph, dists = graph
     y0 = timed("init", lambda: model._initial(manifold._prep(x), graph))
-    n_epochs = model.n_epochs if model.n_epochs is not None else (500 if n <= 10000 else 200)
-    y = timed("layout", lambda: manifold.optimize_layout(
-        y0, graph.indptr, graph.indices, manifold.sample_rates(graph.data), model.a_, model.b_, n_epochs,
-        gamma=model.repulsion_strength, learning_rate=model.learning_rate, seed=model.random_state,
-        negative_sample_rate=model.negative_sample_rate))
+    q = manifold.sample_rates(graph.data)
+    layout_args = dict(gamma=model.repulsion_strength, learning_rate=model.learning_rate, seed=model.random_state,
+                       negative_sample_rate=model.negative_sample_rate)
+    extra = {}
+    if a.densmap:
+        n_epochs = model.default_epochs(n)
+        rad_orig = timed("graph_radii", lambda: manifold.graph_radii(graph.indptr, graph.data, dists, q, n_epochs))
+        y = timed("layout", lambda: manifold.optimize_layout_densmap(
+            y0, graph.indptr, graph.indices, q, graph.data, manifold.standardize_radii(rad_orig), model.a_, model.b_, n_epochs,
+            dens_lambda=model.dens_lambda, dens_frac=model.dens_frac, dens_var_shift=model.dens_var_shift, **layout_args))
+        rad_emb = manifold.embedding_radii(y, graph.indptr, graph.indices, q, model.a_, model.b_, n_epochs)[0]
+        extra = {"rad_orig": rad_orig.cpu().numpy(), "rad_emb": rad_emb.cpu().numpy()}
+    else:
+        n_epochs = model.n_epochs if model.n_epochs is not None else (500 if n <= 10000 else 200)
+        y = timed("layout", lambda: manifold.optimize_layout(y0, graph.indptr, graph.indices, q, model.a_, model.b_, n_epochs,
+                                                             **layout_args))
     reduced = y.cpu().numpy()
-    np.savez(out / "reduced.npz", embeddings=reduced, labels=truth)
+    np.savez(out / "reduced.npz", embeddings=reduced, labels=truth, **extra)
 
     from sklearn.manifold import trustworthiness
 
@@ -115,12 +140,16 @@ def main(argv=None) -> dict:
         fig, ax = plt.subplots(figsize=(7, 7))
         sc = ax.scatter(reduced[:, 0], reduced[:, 1], c=truth, cmap="tab10", s=4)
         ax.legend(*sc.legend_elements(), title="failure code", loc="best", fontsize=7)
-        ax.set_title(f"UMAP of {n} embeddings (n_neighbors={k}, min_dist={a.min_dist})")
+        ax.set_title(f"{'DensMAP' if a.densmap else 'UMAP'} of {n} embeddings (n_neighbors={k}, min_dist={a.min_dist})")
         fig.savefig(out / "umap.png", dpi=120)
         plt.close(fig)
     summary = {"n": n, "d": int(x.shape[1]), "n_neighbors": k, "n_components": a.components, "min_dist": a.min_dist,
                "n_epochs": n_epochs, "init": a.init, "a": model.a_, "b": model.b_, "graph_entries": int(graph.indices.numel()),
                "seconds": seconds, "trustworthiness": score, "trustworthiness_rows": int(pick.size)}
+    if a.densmap:
+        summary.update(densmap=True, dens_lambda=model.dens_lambda, dens_frac=model.dens_frac, dens_var_shift=model.dens_var_shift,
+                       radii_correlation=float(np.corrcoef(extra["rad_orig"].astype(np.float64),
+                                                           extra["rad_emb"].astype(np.float64))[0, 1]))
     (out / "summary.json").write_text(json.dumps(summary, indent=1))
     print(f"UMAP of {n} x {x.shape[1]} -> {a.components}-D in {sum(seconds.values()):.2f} s "
           f"({', '.join(f'{s} {v:.3f}' for s, v in seconds.items())}); trustworthiness {score:.4f} -> {out}")

@@ -293,6 +293,14 @@ SIGNATURES = {
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
                                c_double, c_uint32, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # ---- DensMAP
+    "wm_densmap_graph_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "wm_densmap_embedding_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
+    "wm_densmap_layout_workspace_bytes": (c_size_t, [c_int]),
+    "wm_densmap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_uint32, c_int, c_int,
+                                  c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

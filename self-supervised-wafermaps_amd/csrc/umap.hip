@@ -45,6 +45,43 @@
 // skipped (a wave-uniform branch).  Every lane adds its terms in entry order, then the slots of a component are added
 // in slot order through LDS by the lanes of slot 0, which write y'.  y (1.4 MB at 172 950 x 2) lives in L2: the kernel
 // is bound by gather latency, which the many resident waves cover.
+//
+// ---- DensMAP (umap-learn's densmap=True: _optimize_layout_euclidean_densmap_epoch_init and the densmap branch of its
+// epoch loop, restated for the gather above; manifold.DensMAP).  With w_e the graph's float32 weight of entry e,
+// eps = 1e-8, r = |y_i - y_j|^2, p = r^b:
+//   live(e)   = uint64(q_e) * n_epochs >= 65536: the entry is sampled at least once (umap-learn prunes weights below
+//               max / n_epochs; here nothing is dropped physically, entries that are not live take part in no sum);
+//   dist_e    = max(d_ij, d_ji) over the kNN distances, a missing direction counting 0 (float32, aligned with the CSR);
+//   ro_i      = log(eps + sum_live w_e dist_e^2 / sum_live w_e), log eps for a row without live entries
+//               (wm_densmap_graph_radii, once per fit, one thread per row in double, rounded once);
+//   R         = (ro - mean) / std (population std; 0 when std = 0), formed by the caller;  mu_tot = sum_live w_e;
+//   phase(ep) = dens_lambda > 0 and (ep + 1) / n_epochs > 1 - dens_frac, in double exactly as written.
+// At the start of a phase epoch, from the positions before that epoch (phi_e = 1 / (1 + a p)):
+//   D_i = 2 sum_live phi_e,  N_i = 2 sum_live phi_e r,  re_i = log(eps + N_i / D_i), log eps when D_i = 0
+//         (densmap_radii_kernel: one wave per vertex with the slot layout of the layout kernel, everything in double;
+//         of every 64 consecutive entries each lane takes one, adds its terms in entry order, then the 64 lanes are
+//         added in lane order; r = 0 gives phi = 1 and adds to D only);
+//   mean = sum re / n,  var = sum (re - mean)^2 / n (two passes),  std = sqrt(var + dens_var_shift),
+//   cov  = sum re_i R_i / (n - 1),  W_i = R_i - cov (re_i - mean) / std^2
+//         (densmap_sum1 / sum2 / terms kernels: every thread adds its strided elements in order, a block adds its 256
+//         threads in a fixed tree and stores the partial into its slot, the next kernel adds the slots in the same way:
+//         no atomics, no host synchronisation, two runs give the same bits).
+// The terms kernel leaves per vertex the four float32 values the layout reads, each formed in double and rounded
+// once: 1 / D_i (0 when D_i = 0), 1 / (eps + N_i / D_i), W_i (R_i when std = 0), re_i; and the scalar
+// s = dens_lambda mu_tot / (std n) (0 when std = 0).  In a phase epoch every sampled entry e = (i -> j) then adds
+//   dens(i, j) = 2 clip(2 g_e (y_i - y_j)), 0 when r = 0;   g_e = s (W_i dr_i + W_j dr_j) / w_e,
+//   dr_v = (phi_e / D_v) ((1 - b (1 - phi_e)) / (eps + N_v / D_v) + a b p / (r (1 + a p)))
+// to the terms of vertex i: g_e is symmetric in (i, j), so as for the attraction the move of the head and of the tail
+// become twice the term at the head.  Outside the phase an epoch is the plain epoch above, by the same kernel.
+// Float32 arithmetic of the density term: phi = 1 / (a p + 1); 1 - b (1 - phi) as fma(b, phi, 1 - b) (two positive
+// parts, no cancellation); t2 = (float32(ab) p) / (r (a p + 1)); dr_v = (phi * invD_v) * (t1 * invden_v + t2);
+// g = (s * (W_i dr_i + W_j dr_j)) / w_e; the term is 2 clip((2 g) d_c).
+//
+// Workspace of wm_densmap_layout (16-byte aligned, wm_densmap_layout_workspace_bytes(n) = 4160 + 40 n bytes):
+//   [0, 64)        double mu_tot, mean, var, cov, std; float s at byte 40 (written in every phase epoch)
+//   [64, 4160)     double slots[4][128]: partial sums of mu_tot, re, (re - mean)^2, re R
+//   [4160, +16 n)  float32 [n][4]: 1 / D, 1 / (eps + N / D), W, re
+//   then           double re[n], D[n], N / D [n]
 #include "common.h"
 
 namespace {
@@ -111,11 +148,17 @@ struct UmLayoutArgs {
   int n, dim, neg_rate;
   uint32_t ep, ep_key;  // ep_key = mix(seed ^ ep * 0x9e3779b9)
   float a, b, c_att, c_rep, alpha;
+  // density phase only (DENS)
+  const float* data;    // w_e
+  const float4* vert;   // per vertex: 1 / D, 1 / (eps + N / D), W, re
+  const float* scale;   // s = dens_lambda mu_tot / (std n), on the device
+  float ab, omb;        // float32(a b), float32(1 - b)
 };
 
 __device__ __forceinline__ float um_clip(float v) { return fminf(4.f, fmaxf(-4.f, v)); }
 
-template <int DP>
+// DENS = false is the plain UMAP epoch; DENS = true adds the density term of a DensMAP phase epoch to every sampled entry.
+template <int DP, bool DENS>
 __global__ __launch_bounds__(UM_THREADS) void umap_layout_kernel(const UmLayoutArgs p) {
   constexpr int EPP = 64 / DP;
   __shared__ float red[UM_THREADS];
@@ -129,6 +172,12 @@ __global__ __launch_bounds__(UM_THREADS) void umap_layout_kernel(const UmLayoutA
     const float* yrow = p.y + (size_t)i * p.dim;
     yi = comp ? yrow[c] : 0.f;
     const int beg = p.indptr[i], end = p.indptr[i + 1];
+    float4 vi = {0.f, 0.f, 0.f, 0.f};
+    float scale = 0.f;
+    if constexpr (DENS) {
+      vi = p.vert[i];
+      scale = *p.scale;
+    }
     for (int e0 = beg; e0 < end; e0 += EPP) {
       const int e = e0 + es;
       const uint32_t qe = e < end ? p.q[e] : 0u;
@@ -142,6 +191,18 @@ __global__ __launch_bounds__(UM_THREADS) void umap_layout_kernel(const UmLayoutA
         const float pb = powf(r, p.b);
         const float coef = (p.c_att * pb) / (r * (p.a * pb + 1.f));
         if (hit && r > 0.f) acc += 2.f * um_clip(coef * d);
+        if constexpr (DENS) {
+          const float4 vj = hit ? p.vert[j] : vi;
+          const float we = hit ? p.data[e] : 1.f;
+          const float apb1 = p.a * pb + 1.f;
+          const float phi = 1.f / apb1;
+          const float t1 = fmaf(p.b, phi, p.omb);
+          const float t2 = (p.ab * pb) / (r * apb1);
+          const float dri = (phi * vi.x) * (t1 * vi.y + t2);
+          const float drj = (phi * vj.x) * (t1 * vj.y + t2);
+          const float g = (scale * (vi.z * dri + vj.z * drj)) / we;
+          if (hit && r > 0.f) acc += 2.f * um_clip((2.f * g) * d);
+        }
       }
       const uint32_t key = lowbias32(p.ep_key + (uint32_t)e);
       for (int t = 0; t < p.neg_rate; ++t) {
@@ -166,9 +227,227 @@ __global__ __launch_bounds__(UM_THREADS) void umap_layout_kernel(const UmLayoutA
   }
 }
 
-template <int DP>
+template <int DP, bool DENS>
 void um_launch(const UmLayoutArgs& a, hipStream_t st) {
-  umap_layout_kernel<DP><<<wm_cdiv(a.n, UM_THREADS / 64), UM_THREADS, 0, st>>>(a);
+  umap_layout_kernel<DP, DENS><<<wm_cdiv(a.n, UM_THREADS / 64), UM_THREADS, 0, st>>>(a);
+}
+
+// One epoch: the padded dimension picks the instantiation.
+template <bool DENS>
+void um_epoch(const UmLayoutArgs& p, hipStream_t st) {
+  const int dim = p.dim;
+  if (dim == 1) um_launch<1, DENS>(p, st);
+  else if (dim == 2) um_launch<2, DENS>(p, st);
+  else if (dim <= 4) um_launch<4, DENS>(p, st);
+  else if (dim <= 8) um_launch<8, DENS>(p, st);
+  else if (dim <= 16) um_launch<16, DENS>(p, st);
+  else if (dim <= 32) um_launch<32, DENS>(p, st);
+  else um_launch<64, DENS>(p, st);
+}
+
+// ---- DensMAP: radii, statistics, per-vertex terms
+
+constexpr int DM_THREADS = 256;
+constexpr int DM_SLOTS = 128;
+constexpr size_t DM_HEAD = 64 + 4 * DM_SLOTS * sizeof(double);  // scalars and slots: 4160 bytes
+constexpr double DM_EPS = 1e-8;
+
+__device__ __forceinline__ bool dm_live(uint32_t q, uint32_t n_epochs) { return (uint64_t)q * n_epochs >= 65536ull; }
+
+__global__ __launch_bounds__(DM_THREADS) void densmap_graph_radii_kernel(const int* __restrict__ indptr,
+                                                                         const float* __restrict__ data,
+                                                                         const float* __restrict__ dists,
+                                                                         const uint32_t* __restrict__ q, int n,
+                                                                         uint32_t n_epochs, float* __restrict__ ro) {
+  const int i = blockIdx.x * DM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  double num = 0.0, den = 0.0;
+  for (int e = indptr[i]; e < indptr[i + 1]; ++e) {
+    if (!dm_live(q[e], n_epochs)) continue;
+    const double w = (double)data[e], d = (double)dists[e];
+    num += w * d * d;
+    den += w;
+  }
+  ro[i] = (float)log(DM_EPS + (den > 0.0 ? num / den : 0.0));
+}
+
+template <int W>
+__device__ __forceinline__ double dm_group_sum(double v) {
+#pragma unroll
+  for (int m = 1; m < W; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// D_i, N_i / D_i and re_i of the positions y; outputs that are null are not written.
+template <int DP>
+__global__ __launch_bounds__(UM_THREADS) void densmap_radii_kernel(const float* __restrict__ y, const int* __restrict__ indptr,
+                                                                   const int* __restrict__ indices,
+                                                                   const uint32_t* __restrict__ q, int n, int dim, double a,
+                                                                   double b, uint32_t n_epochs, double* __restrict__ re_d,
+                                                                   double* __restrict__ d_d, double* __restrict__ ratio_d,
+                                                                   float* __restrict__ re_f, float* __restrict__ d_f) {
+  constexpr int EPP = 64 / DP;
+  __shared__ double red[2][UM_THREADS / 64][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & (DP - 1), es = lane / DP;
+  const int i = blockIdx.x * (UM_THREADS / 64) + __builtin_amdgcn_readfirstlane(wave);
+  const bool live = i < n;
+  const bool comp = c < dim;
+  double sd = 0.0, sn = 0.0;
+  if (live) {
+    const double yi = comp ? (double)y[(size_t)i * dim + c] : 0.0;
+    const int beg = indptr[i], end = indptr[i + 1];
+    // A batch of 64 entries is DP passes of EPP entries; pass ps leaves the r of slot es's entry in lane (es, c = ps), so
+    // that after the batch every lane holds one entry and the wave pays for one pow per 64 entries, not one per pass.
+    for (int b0 = beg; b0 < end; b0 += 64) {
+      double rm = 0.0;
+      bool lm = false;
+      for (int ps = 0; ps < DP && b0 + ps * EPP < end; ++ps) {
+        const int e = b0 + ps * EPP + es;
+        const bool lv = e < end && dm_live(q[e], n_epochs);
+        if (__ballot(lv) == 0ull) continue;
+        const int j = lv ? indices[e] : i;
+        const double yj = comp ? (double)y[(size_t)j * dim + c] : 0.0;
+        const double d = yi - yj;
+        const double r = dm_group_sum<DP>(d * d);
+        if (c == ps) {
+          rm = r;
+          lm = lv;
+        }
+      }
+      if (lm) {
+        const double phi = 1.0 / (1.0 + a * pow(rm, b));
+        sd += phi;
+        sn += phi * rm;
+      }
+    }
+  }
+  red[0][wave][lane] = sd;
+  red[1][wave][lane] = sn;
+  __syncthreads();
+  if (live && lane == 0) {
+    double dsum = 0.0, nsum = 0.0;
+    for (int s = 0; s < 64; ++s) {
+      dsum += red[0][wave][s];
+      nsum += red[1][wave][s];
+    }
+    dsum *= 2.0;
+    nsum *= 2.0;
+    const double ratio = dsum > 0.0 ? nsum / dsum : 0.0;
+    const double re = log(DM_EPS + ratio);
+    if (re_d) re_d[i] = re;
+    if (d_d) d_d[i] = dsum;
+    if (ratio_d) ratio_d[i] = ratio;
+    if (re_f) re_f[i] = (float)re;
+    if (d_f) d_f[i] = (float)dsum;
+  }
+}
+
+// The sum of one value per thread over a block of DM_THREADS threads, in a fixed tree; every thread gets it.
+__device__ __forceinline__ double dm_block_sum(double v, double* lds) {
+  lds[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = DM_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) lds[threadIdx.x] += lds[threadIdx.x + s];
+    __syncthreads();
+  }
+  const double r = lds[0];
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ double dm_slot_total(const double* __restrict__ slots, int nb, double* lds) {
+  return dm_block_sum((int)threadIdx.x < nb ? slots[threadIdx.x] : 0.0, lds);
+}
+static_assert(DM_SLOTS <= DM_THREADS, "one slot per thread");
+
+// slots[0][block] = the block's part of mu_tot = sum_live w_e
+__global__ __launch_bounds__(DM_THREADS) void densmap_mu_kernel(const float* __restrict__ data, const uint32_t* __restrict__ q,
+                                                                long long nnz, uint32_t n_epochs, double* __restrict__ slots) {
+  __shared__ double lds[DM_THREADS];
+  double v = 0.0;
+  for (long long e = (long long)blockIdx.x * DM_THREADS + threadIdx.x; e < nnz; e += (long long)gridDim.x * DM_THREADS)
+    if (dm_live(q[e], n_epochs)) v += (double)data[e];
+  const double t = dm_block_sum(v, lds);
+  if (threadIdx.x == 0) slots[blockIdx.x] = t;
+}
+
+// slots[1][block] = the block's part of sum re
+__global__ __launch_bounds__(DM_THREADS) void densmap_sum1_kernel(const double* __restrict__ re, int n, double* __restrict__ slots) {
+  __shared__ double lds[DM_THREADS];
+  double v = 0.0;
+  for (int i = blockIdx.x * DM_THREADS + threadIdx.x; i < n; i += gridDim.x * DM_THREADS) v += re[i];
+  const double t = dm_block_sum(v, lds);
+  if (threadIdx.x == 0) slots[DM_SLOTS + blockIdx.x] = t;
+}
+
+// slots[2][block], slots[3][block] = the block's parts of sum (re - mean)^2 and sum re R
+__global__ __launch_bounds__(DM_THREADS) void densmap_sum2_kernel(const double* __restrict__ re, const float* __restrict__ rad, int n,
+                                                                  double* __restrict__ slots) {
+  __shared__ double lds[DM_THREADS];
+  const double mean = dm_slot_total(slots + DM_SLOTS, gridDim.x, lds) / (double)n;
+  double v = 0.0, cv = 0.0;
+  for (int i = blockIdx.x * DM_THREADS + threadIdx.x; i < n; i += gridDim.x * DM_THREADS) {
+    const double x = re[i];
+    v += (x - mean) * (x - mean);
+    cv += x * (double)rad[i];
+  }
+  const double tv = dm_block_sum(v, lds), tc = dm_block_sum(cv, lds);
+  if (threadIdx.x == 0) {
+    slots[2 * DM_SLOTS + blockIdx.x] = tv;
+    slots[3 * DM_SLOTS + blockIdx.x] = tc;
+  }
+}
+
+// The per-vertex float32 values and the scalar s the density layout reads; one thread per vertex.
+__global__ __launch_bounds__(DM_THREADS) void densmap_terms_kernel(const double* __restrict__ re, const double* __restrict__ dd,
+                                                                   const double* __restrict__ ratio, const float* __restrict__ rad,
+                                                                   int n, int nb_vertex, int nb_entry, double dens_lambda,
+                                                                   double var_shift, const double* __restrict__ slots,
+                                                                   float4* __restrict__ vert, double* __restrict__ scal) {
+  __shared__ double lds[DM_THREADS];
+  const double mu = dm_slot_total(slots, nb_entry, lds);
+  const double mean = dm_slot_total(slots + DM_SLOTS, nb_vertex, lds) / (double)n;
+  const double var = dm_slot_total(slots + 2 * DM_SLOTS, nb_vertex, lds) / (double)n;
+  const double cov = dm_slot_total(slots + 3 * DM_SLOTS, nb_vertex, lds) / (double)(n - 1);
+  const double sd = sqrt(var + var_shift);
+  const int i = blockIdx.x * DM_THREADS + threadIdx.x;
+  if (i < n) {
+    const double d = dd[i], x = re[i], r = (double)rad[i];
+    float4 v;
+    v.x = (float)(d > 0.0 ? 1.0 / d : 0.0);
+    v.y = (float)(1.0 / (DM_EPS + ratio[i]));
+    v.z = (float)(sd > 0.0 ? r - cov * (x - mean) / (sd * sd) : r);
+    v.w = (float)x;
+    vert[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scal[0] = mu;
+    scal[1] = mean;
+    scal[2] = var;
+    scal[3] = cov;
+    scal[4] = sd;
+    reinterpret_cast<float*>(scal + 5)[0] = (float)(sd > 0.0 ? dens_lambda * mu / (sd * (double)n) : 0.0);
+  }
+}
+
+void dm_radii_launch(const float* y, const int* indptr, const int* indices, const uint32_t* q, int n, int dim, double a, double b,
+                     int n_epochs, double* re_d, double* d_d, double* ratio_d, float* re_f, float* d_f, hipStream_t st) {
+  const int grid = wm_cdiv(n, UM_THREADS / 64);
+#define DM_RADII(DP) \
+  densmap_radii_kernel<DP><<<grid, UM_THREADS, 0, st>>>(y, indptr, indices, q, n, dim, a, b, (uint32_t)n_epochs, re_d, d_d, ratio_d, re_f, d_f)
+  if (dim == 1) DM_RADII(1);
+  else if (dim == 2) DM_RADII(2);
+  else if (dim <= 4) DM_RADII(4);
+  else if (dim <= 8) DM_RADII(8);
+  else if (dim <= 16) DM_RADII(16);
+  else if (dim <= 32) DM_RADII(32);
+  else DM_RADII(64);
+#undef DM_RADII
+}
+
+inline int dm_blocks(long long count) {
+  const int nb = wm_cdiv(count, DM_THREADS);
+  return nb < 1 ? 1 : (nb > DM_SLOTS ? DM_SLOTS : nb);
 }
 
 inline uint32_t um_mix_host(uint32_t x) {
@@ -221,13 +500,109 @@ extern "C" int wm_umap_layout(float* y_a, float* y_b, const int32_t* indptr, con
     p.ep = (uint32_t)ep;
     p.ep_key = um_mix_host(seed ^ ((uint32_t)ep * 0x9e3779b9U));
     p.alpha = (float)(learning_rate * (1.0 - (double)ep / (double)n_epochs));
-    if (dim == 1) um_launch<1>(p, st);
-    else if (dim == 2) um_launch<2>(p, st);
-    else if (dim <= 4) um_launch<4>(p, st);
-    else if (dim <= 8) um_launch<8>(p, st);
-    else if (dim <= 16) um_launch<16>(p, st);
-    else if (dim <= 32) um_launch<32>(p, st);
-    else um_launch<64>(p, st);
+    um_epoch<false>(p, st);
+    WM_LAUNCH_CHECK();
+    float* sw = cur;
+    cur = nxt;
+    nxt = sw;
+  }
+  *result_buffer = cur == y_a ? 0 : 1;
+  return WM_OK;
+}
+
+extern "C" int wm_densmap_graph_radii(const int32_t* indptr, const float* data, const float* dists, const uint32_t* q, int n,
+                                      int n_epochs, float* ro, void* stream) {
+  WM_REQUIRE(indptr && data && dists && q && ro, WM_EINVAL);
+  WM_REQUIRE(n > 0 && n_epochs > 0, WM_EINVAL);
+  WM_REQUIRE(n <= (1 << 24), WM_EUNSUPPORTED);
+  densmap_graph_radii_kernel<<<wm_cdiv(n, DM_THREADS), DM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      indptr, data, dists, q, n, (uint32_t)n_epochs, ro);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_densmap_embedding_radii(const float* y, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n,
+                                          int dim, double a, double b, int n_epochs, float* re, float* d, void* stream) {
+  WM_REQUIRE(y && indptr && indices && q && re && d, WM_EINVAL);
+  WM_REQUIRE(n > 0 && dim > 0 && n_epochs > 0 && a > 0.0 && b > 0.0, WM_EINVAL);
+  WM_REQUIRE(dim <= UM_MAX_DIM && n <= (1 << 24), WM_EUNSUPPORTED);
+  dm_radii_launch(y, indptr, indices, q, n, dim, a, b, n_epochs, nullptr, nullptr, nullptr, re, d, static_cast<hipStream_t>(stream));
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_densmap_layout_workspace_bytes(int n) {
+  if (n < 2 || n > (1 << 24)) return 0;
+  return DM_HEAD + (size_t)n * (sizeof(float4) + 3 * sizeof(double));
+}
+
+extern "C" int wm_densmap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q,
+                                 const float* data, const float* rad, int n, int nnz, int dim, double a, double b,
+                                 double gamma, double learning_rate, double dens_lambda, double dens_frac, double dens_var_shift, uint32_t seed,
+                                 int epoch_begin, int epoch_end, int n_epochs, int neg_rate, void* workspace,
+                                 size_t workspace_bytes, int* result_buffer, void* stream) {
+  WM_REQUIRE(y_a && y_b && y_a != y_b && indptr && indices && q && data && rad && workspace && result_buffer, WM_EINVAL);
+  WM_REQUIRE(n > 1 && nnz >= 0 && dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end && epoch_end <= n_epochs,
+             WM_EINVAL);
+  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
+  WM_REQUIRE(dens_lambda >= 0.0 && dens_frac >= 0.0 && dens_frac <= 1.0 && dens_var_shift >= 0.0, WM_EINVAL);
+  WM_REQUIRE(dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG && n <= (1 << 24), WM_EUNSUPPORTED);
+  WM_REQUIRE(workspace_bytes >= wm_densmap_layout_workspace_bytes(n), WM_EWORKSPACE);
+  WM_REQUIRE(((uintptr_t)workspace & 15u) == 0, WM_EALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(workspace);
+  double* scal = reinterpret_cast<double*>(ws);
+  double* slots = reinterpret_cast<double*>(ws + 64);
+  float4* vert = reinterpret_cast<float4*>(ws + DM_HEAD);
+  double* re_d = reinterpret_cast<double*>(ws + DM_HEAD + (size_t)n * sizeof(float4));
+  double* d_d = re_d + n;
+  double* ratio_d = d_d + n;
+  UmLayoutArgs p = {};
+  p.indptr = indptr;
+  p.indices = indices;
+  p.q = q;
+  p.n = n;
+  p.dim = dim;
+  p.neg_rate = neg_rate;
+  p.a = (float)a;
+  p.b = (float)b;
+  p.c_att = (float)(-2.0 * a * b);
+  p.c_rep = (float)(2.0 * gamma * b);
+  p.data = data;
+  p.vert = vert;
+  p.scale = reinterpret_cast<const float*>(scal + 5);
+  p.ab = (float)(a * b);
+  p.omb = (float)(1.0 - b);
+  const int nb_vertex = dm_blocks(n);
+  int nb_entry = 0;  // (mu_tot is summed before the call's first phase epoch)
+  float* cur = y_a;
+  float* nxt = y_b;
+  for (int ep = epoch_begin; ep < epoch_end; ++ep) {
+    p.y = cur;
+    p.y_out = nxt;
+    p.ep = (uint32_t)ep;
+    p.ep_key = um_mix_host(seed ^ ((uint32_t)ep * 0x9e3779b9U));
+    p.alpha = (float)(learning_rate * (1.0 - (double)ep / (double)n_epochs));
+    const bool phase = dens_lambda > 0.0 && (double)(ep + 1) / (double)n_epochs > 1.0 - dens_frac;
+    if (phase) {
+      if (nb_entry == 0) {
+        nb_entry = dm_blocks(nnz);
+        densmap_mu_kernel<<<nb_entry, DM_THREADS, 0, st>>>(data, q, (long long)nnz, (uint32_t)n_epochs, slots);
+        WM_LAUNCH_CHECK();
+      }
+      dm_radii_launch(cur, indptr, indices, q, n, dim, a, b, n_epochs, re_d, d_d, ratio_d, nullptr, nullptr, st);
+      WM_LAUNCH_CHECK();
+      densmap_sum1_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, n, slots);
+      WM_LAUNCH_CHECK();
+      densmap_sum2_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, rad, n, slots);
+      WM_LAUNCH_CHECK();
+      densmap_terms_kernel<<<wm_cdiv(n, DM_THREADS), DM_THREADS, 0, st>>>(re_d, d_d, ratio_d, rad, n, nb_vertex, nb_entry,
+                                                                         dens_lambda, dens_var_shift, slots, vert, scal);
+      WM_LAUNCH_CHECK();
+      um_epoch<true>(p, st);
+    } else {
+      um_epoch<false>(p, st);
+    }
     WM_LAUNCH_CHECK();
     float* sw = cur;
     cur = nxt;

@@ -16,7 +16,15 @@ Three steps, the GPU-shaped ones as HIP kernels:
 What runs on the host: the curve fit of (a, b) (scipy, 300 points, as umap-learn's find_ab_params) and the spectral
 initialisation (scipy eigsh on the normalised Laplacian, as umap-learn itself does).
 
-Not built (NotImplementedError naming the feature): densmap=True, y= (semi-supervised fits), transform of new rows.
+DensMAP (`umap.UMAP(densmap=True, dens_lambda=...)` of notebooks 3.0, 3.1 and 3.2) is its own estimator, `DensMAP`:
+the same three steps, plus
+  4. the graph's radii ro_i = log(eps + sum w d^2 / sum w) once per fit (csrc/umap.hip: wm_densmap_graph_radii) over the
+     graph distances max(d_ij, d_ji) that `fuzzy_simplicial_set(..., return_dists=True)` returns, and, in the last
+     `dens_frac` of the epochs, the density term: per epoch the embedding's radii, their statistics and the per-vertex
+     terms by fixed-order kernels, then the layout kernel with the term compiled in (wm_densmap_layout).
+`UMAP(densmap=True)` itself keeps raising and names `DensMAP`.
+
+Not built (NotImplementedError naming the feature): y= (semi-supervised fits), transform of new rows.
 Only local_connectivity = 1 and set_op_mix_ratio = 1 are supported.
 """
 from __future__ import annotations
@@ -140,10 +148,12 @@ class CSR(NamedTuple):
         return csr_matrix((self.data.cpu().numpy(), self.indices.cpu().numpy(), self.indptr.cpu().numpy()), shape=self.shape)
 
 
-def fuzzy_union(idx, weights) -> CSR:
+def fuzzy_union(idx, weights, dist=None):
     """G = P + P^T - P o P^T of the directed membership matrix P[i, idx[i, j]] = weights[i, j] (zeros dropped), as CSR
     on the device.  The value of an entry is formed in double from the two float32 memberships and rounded once, by
-    the same expression for (i, j) and (j, i): G is symmetric in bits and within 2^-24 relative of the exact union."""
+    the same expression for (i, j) and (j, i): G is symmetric in bits and within 2^-24 relative of the exact union.
+    With `dist` (the kNN distances float32 [n, k]) the result is (G, dists): dists float32 [nnz], aligned with G's
+    entries, max(d_ij, d_ji) over the kNN graph with a missing direction counting 0 (umap-learn's dmat.maximum(dmat.T))."""
     import torch
 
     require_gpu(idx, weights)
@@ -169,14 +179,22 @@ def fuzzy_union(idx, weights) -> CSR:
     r = both // n
     indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     indptr[1:] = torch.cumsum(torch.bincount(r, minlength=n), 0)
-    return CSR(indptr.to(torch.int32), (both % n).to(torch.int32).contiguous(), data.contiguous())
+    graph = CSR(indptr.to(torch.int32), (both % n).to(torch.int32).contiguous(), data.contiguous())
+    if dist is None:
+        return graph
+    require_gpu(dist)
+    # every kNN entry carries a distance, also one whose membership is 0
+    key, order = torch.sort((rows * n + cols).reshape(-1))
+    val = dist.reshape(-1).double()[order]
+    return graph, torch.maximum(lookup(both), lookup((both % n) * n + both // n)).float().contiguous()
 
 
-def fuzzy_simplicial_set(x, n_neighbors: int, metric: str = "euclidean") -> CSR:
-    """umap-learn's fuzzy_simplicial_set (local_connectivity = 1, set_op_mix_ratio = 1) of the rows of x."""
+def fuzzy_simplicial_set(x, n_neighbors: int, metric: str = "euclidean", return_dists: bool = False):
+    """umap-learn's fuzzy_simplicial_set (local_connectivity = 1, set_op_mix_ratio = 1) of the rows of x; with
+    `return_dists` also the graph distances aligned with its entries (`fuzzy_union`)."""
     dist, idx = knn_graph(x, n_neighbors, metric)
     _, _, w = smooth_knn(dist, idx)
-    return fuzzy_union(idx, w)
+    return fuzzy_union(idx, w, dist if return_dists else None)
 
 
 def sample_rates(data):
@@ -190,16 +208,11 @@ def sample_rates(data):
     return torch.round(65536.0 * w / w.max()).to(torch.int32).contiguous()
 
 
-def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
-                    epoch_end: Optional[int] = None, gamma: float = 1.0, learning_rate: float = 1.0, seed: int = 0,
-                    negative_sample_rate: int = 5):
-    """Epochs [epoch_begin, epoch_end) of `n_epochs` of the layout optimisation (csrc/umap.hip) from the positions
-    y float32 [n, dim] over the symmetric CSR graph (indptr, indices int32) with sampling rates q (`sample_rates`).
-    Returns the new positions; y is left unchanged.  Splitting the epoch range over several calls changes no bit."""
+def _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate,
+                       negative_sample_rate):
+    """The validation `optimize_layout` and `optimize_layout_densmap` share; returns (n, dim)."""
     import torch
 
-    require_gpu(y, indptr, indices, q)
-    epoch_end = n_epochs if epoch_end is None else epoch_end
     if y.dim() != 2 or y.dtype != torch.float32:
         raise ValueError("y float32 [n, dim] expected")
     n, dim = y.shape
@@ -219,8 +232,23 @@ def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, ep
         raise ValueError("0 <= epoch_begin <= epoch_end <= n_epochs expected")
     if not (a > 0 and b > 0 and gamma >= 0 and learning_rate >= 0 and 0 <= int(negative_sample_rate) <= 64):
         raise ValueError("a, b > 0, gamma, learning_rate >= 0 and 0 <= negative_sample_rate <= 64 expected")
+    return n, dim
+
+
+def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
+                    epoch_end: Optional[int] = None, gamma: float = 1.0, learning_rate: float = 1.0, seed: int = 0,
+                    negative_sample_rate: int = 5):
+    """Epochs [epoch_begin, epoch_end) of `n_epochs` of the layout optimisation (csrc/umap.hip) from the positions
+    y float32 [n, dim] over the symmetric CSR graph (indptr, indices int32) with sampling rates q (`sample_rates`).
+    Returns the new positions; y is left unchanged.  Splitting the epoch range over several calls changes no bit."""
     import ctypes
 
+    import torch
+
+    require_gpu(y, indptr, indices, q)
+    epoch_end = n_epochs if epoch_end is None else epoch_end
+    n, dim = _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate,
+                                negative_sample_rate)
     bufs = (y.clone(), torch.empty_like(y))
     which = ctypes.c_int(0)
     check(_lib.load().wm_umap_layout(ptr(bufs[0]), ptr(bufs[1]), ptr(indptr), ptr(indices), ptr(q), n, dim, float(a), float(b),
@@ -228,6 +256,131 @@ def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, ep
                                      int(n_epochs), int(negative_sample_rate), ctypes.addressof(which), stream_ptr()),
           "wm_umap_layout")
     return bufs[which.value]
+
+
+# ------------------------------------------------------------------------------------------------ DensMAP steps
+
+
+def in_density_phase(epoch: int, n_epochs: int, dens_lambda: float, dens_frac: float) -> bool:
+    """Whether 0-based `epoch` of `n_epochs` carries the density term (csrc/umap.hip evaluates the same expression)."""
+    return bool(dens_lambda > 0 and (epoch + 1) / n_epochs > 1.0 - dens_frac)
+
+
+def graph_radii(indptr, data, dists, q, n_epochs: int):
+    """ro float32 [n]: the log of the weighted mean squared graph distance over each row's live entries (those sampled
+    at least once in `n_epochs`), log 1e-8 for a row without one (csrc/umap.hip: wm_densmap_graph_radii)."""
+    import torch
+
+    require_gpu(indptr, data, dists, q)
+    if indptr.dtype != torch.int32 or q.dtype != torch.int32 or data.dtype != torch.float32 or dists.dtype != torch.float32:
+        raise ValueError("indptr, q int32 and data, dists float32 expected")
+    if indptr.dim() != 1 or indptr.numel() < 2 or data.dim() != 1 or dists.shape != data.shape or q.shape != data.shape:
+        raise ValueError("indptr [n + 1] and data, dists, q [nnz] expected")
+    ip = indptr.long()
+    if int(ip[0]) != 0 or int(ip[-1]) != data.numel() or bool((ip[1:] < ip[:-1]).any()):
+        raise ValueError("indptr must rise from 0 to nnz")
+    if int(n_epochs) < 1:
+        raise ValueError("n_epochs must be positive")
+    n = indptr.numel() - 1
+    ro = torch.empty(n, dtype=torch.float32, device=data.device)
+    check(_lib.load().wm_densmap_graph_radii(ptr(indptr), ptr(data.contiguous()), ptr(dists.contiguous()), ptr(q.contiguous()), n,
+                                             int(n_epochs), ptr(ro), stream_ptr()), "wm_densmap_graph_radii")
+    return ro
+
+
+def standardize_radii(ro):
+    """R = (ro - mean) / std in double (population std), 0 when std = 0, as float32."""
+    import torch
+
+    r = ro.double()
+    std = r.std(unbiased=False) if r.numel() > 1 else torch.zeros((), dtype=torch.float64, device=ro.device)
+    if float(std) == 0.0:
+        return torch.zeros_like(ro)
+    return ((r - r.mean()) / std).float().contiguous()
+
+
+def embedding_radii(y, indptr, indices, q, a: float, b: float, n_epochs: int):
+    """(re, D) float32 [n] of the positions y float32 [n, dim] over the graph's live entries:
+    D_i = 2 sum 1 / (1 + a r^b), re_i = log(1e-8 + N_i / D_i) with N_i = 2 sum r / (1 + a r^b), r the squared distance
+    (csrc/umap.hip: wm_densmap_embedding_radii)."""
+    import torch
+
+    require_gpu(y, indptr, indices, q)
+    n, dim = _check_layout_args(y, indptr, indices, q, a, b, n_epochs, 0, n_epochs, 0.0, 0.0, 0)
+    re = torch.empty(n, dtype=torch.float32, device=y.device)
+    d = torch.empty(n, dtype=torch.float32, device=y.device)
+    check(_lib.load().wm_densmap_embedding_radii(ptr(y.contiguous()), ptr(indptr), ptr(indices), ptr(q), n, dim, float(a), float(b),
+                                                 int(n_epochs), ptr(re), ptr(d), stream_ptr()), "wm_densmap_embedding_radii")
+    return re, d
+
+
+class DensityTerms(NamedTuple):
+    """What the last density-phase epoch of an `optimize_layout_densmap` call computed from the positions before it:
+    per vertex float32 [n] 1 / D, 1 / (1e-8 + N / D), W and re, the float32 scalar `scale` =
+    dens_lambda mu_tot / (std n) the layout kernel multiplies with, and mu_tot, mean, var, cov, std in float64."""
+
+    inv_d: "object"
+    inv_den: "object"
+    w: "object"
+    re: "object"
+    scale: float
+    mu_tot: float
+    mean: float
+    var: float
+    cov: float
+    std: float
+
+
+def optimize_layout_densmap(y, indptr, indices, q, data, R, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
+                            epoch_end: Optional[int] = None, gamma: float = 1.0, learning_rate: float = 1.0, seed: int = 0,
+                            negative_sample_rate: int = 5, dens_lambda: float = 2.0, dens_frac: float = 0.3,
+                            dens_var_shift: float = 0.1, return_terms: bool = False):
+    """`optimize_layout` with DensMAP's density term in the epochs of the density phase (`in_density_phase`): `data`
+    float32 [nnz] > 0 are the graph's weights and `R` float32 [n] the standardised graph radii (`graph_radii`,
+    `standardize_radii`).  Epochs outside the phase, and every epoch when dens_lambda = 0, are `optimize_layout`'s bit for
+    bit; splitting the epoch range over several calls changes no bit.  With `return_terms` the result is
+    (positions, DensityTerms or None when the call ran no phase epoch)."""
+    import ctypes
+
+    import torch
+
+    require_gpu(y, indptr, indices, q, data, R)
+    epoch_end = n_epochs if epoch_end is None else epoch_end
+    n, dim = _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate,
+                                negative_sample_rate)
+    if n < 2:
+        raise ValueError("at least 2 vertices expected")
+    if data.dtype != torch.float32 or R.dtype != torch.float32 or data.shape != indices.shape or R.shape != (n,):
+        raise ValueError("data float32 [nnz] and R float32 [n] expected")
+    if data.numel() and not bool((torch.isfinite(data) & (data > 0)).all()):
+        raise ValueError("data must be positive and finite")
+    if not bool(torch.isfinite(R).all()):
+        raise ValueError("R must be finite")
+    if not (dens_lambda >= 0 and 0 <= dens_frac <= 1 and dens_var_shift >= 0):
+        raise ValueError("dens_lambda >= 0, 0 <= dens_frac <= 1 and dens_var_shift >= 0 expected")
+    lib = _lib.load()
+    need = lib.wm_densmap_layout_workspace_bytes(n)
+    if need == 0:
+        raise ValueError(f"optimize_layout_densmap: unsupported n = {n}")
+    ws = torch.zeros(need, dtype=torch.uint8, device=y.device)
+    bufs = (y.clone(), torch.empty_like(y))
+    which = ctypes.c_int(0)
+    check(lib.wm_densmap_layout(ptr(bufs[0]), ptr(bufs[1]), ptr(indptr), ptr(indices), ptr(q), ptr(data.contiguous()),
+                                ptr(R.contiguous()), n, int(indices.numel()), dim, float(a), float(b), float(gamma),
+                                float(learning_rate), float(dens_lambda), float(dens_frac), float(dens_var_shift),
+                                int(seed) & _MASK32, int(epoch_begin), int(epoch_end), int(n_epochs), int(negative_sample_rate),
+                                ptr(ws), need, ctypes.addressof(which), stream_ptr()), "wm_densmap_layout")
+    out = bufs[which.value]
+    if not return_terms:
+        return out
+    if not any(in_density_phase(ep, n_epochs, dens_lambda, dens_frac) for ep in range(epoch_begin, epoch_end)):
+        return out, None
+    head = 64 + 4 * 128 * 8  # (csrc/umap.hip: the workspace layout)
+    vert = ws[head:head + 16 * n].view(torch.float32).view(n, 4)
+    scal = ws[:40].view(torch.float64).cpu().tolist()
+    scale = float(ws[40:44].view(torch.float32).cpu()[0])
+    return out, DensityTerms(vert[:, 0].contiguous(), vert[:, 1].contiguous(), vert[:, 2].contiguous(), vert[:, 3].contiguous(),
+                             scale, *scal)
 
 
 # ------------------------------------------------------------------------------------------------ initialisation
@@ -282,7 +435,7 @@ class UMAP:
                  local_connectivity: float = 1.0, set_op_mix_ratio: float = 1.0, densmap: bool = False):
         metric_code(metric)
         if densmap:
-            raise NotImplementedError("densmap=True is not implemented (the density term of DensMAP has no kernel)")
+            raise NotImplementedError("densmap=True is not a switch of this class: use manifold.DensMAP")
         if float(local_connectivity) != 1.0 or float(set_op_mix_ratio) != 1.0:
             raise ValueError("only local_connectivity=1.0 and set_op_mix_ratio=1.0 are supported")
         if not 2 <= int(n_neighbors) <= MAX_NEIGHBORS:
@@ -335,13 +488,17 @@ class UMAP:
         span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
         return (10.0 * (y - lo) / span).float().contiguous()
 
-    def fit(self, x, y=None) -> "UMAP":
+    def _checked(self, x, y):
         if y is not None:
             raise NotImplementedError("y= (semi-supervised UMAP) is not implemented")
         x = _prep(x)
-        n = x.shape[0]
-        if n < 2:
+        if x.shape[0] < 2:
             raise ValueError("UMAP needs at least 2 rows")
+        return x
+
+    def fit(self, x, y=None) -> "UMAP":
+        x = self._checked(x, y)
+        n = x.shape[0]
         graph = fuzzy_simplicial_set(x, min(self.n_neighbors, n), self.metric)
         n_epochs = self.n_epochs if self.n_epochs is not None else (500 if n <= 10000 else 200)
         self.graph_ = graph
@@ -356,3 +513,39 @@ class UMAP:
 
     def transform(self, x):
         raise NotImplementedError("transform of new rows is not implemented (fit_transform embeds the fitted rows)")
+
+
+class DensMAP(UMAP):
+    """umap.UMAP(densmap=True, ...): UMAP whose last `dens_frac` of the epochs also pull the embedding's local radii
+    towards the data's (`optimize_layout_densmap`).  `UMAP`'s arguments plus umap-learn's dens_lambda = 2.0,
+    dens_frac = 0.3, dens_var_shift = 0.1; `n_epochs=None` means 700 for at most 10 000 rows and 400 above (umap-learn adds
+    200 epochs for densmap).  After `fit`, `rad_orig_` holds the graph's radii ro and `rad_emb_` the embedding's radii re
+    at the final positions, float32 [n] on the device."""
+
+    def __init__(self, *args, dens_lambda: float = 2.0, dens_frac: float = 0.3, dens_var_shift: float = 0.1, **kwargs):
+        if "densmap" in kwargs or len(args) > 13:
+            raise ValueError("DensMAP takes no densmap= argument: the class is the switch")
+        super().__init__(*args, **kwargs)
+        if not (dens_lambda >= 0 and 0 <= dens_frac <= 1 and dens_var_shift >= 0):
+            raise ValueError("dens_lambda >= 0, 0 <= dens_frac <= 1 and dens_var_shift >= 0 required")
+        self.dens_lambda, self.dens_frac, self.dens_var_shift = float(dens_lambda), float(dens_frac), float(dens_var_shift)
+        self.rad_orig_ = self.rad_emb_ = None
+
+    def default_epochs(self, n: int) -> int:
+        return self.n_epochs if self.n_epochs is not None else (700 if n <= 10000 else 400)
+
+    def fit(self, x, y=None) -> "DensMAP":
+        x = self._checked(x, y)
+        n = x.shape[0]
+        graph, dists = fuzzy_simplicial_set(x, min(self.n_neighbors, n), self.metric, return_dists=True)
+        n_epochs = self.default_epochs(n)
+        q = sample_rates(graph.data)
+        self.graph_ = graph
+        self.rad_orig_ = graph_radii(graph.indptr, graph.data, dists, q, n_epochs)
+        self.embedding_ = optimize_layout_densmap(
+            self._initial(x, graph), graph.indptr, graph.indices, q, graph.data, standardize_radii(self.rad_orig_), self.a_,
+            self.b_, n_epochs, gamma=self.repulsion_strength, learning_rate=self.learning_rate, seed=self.random_state,
+            negative_sample_rate=self.negative_sample_rate, dens_lambda=self.dens_lambda, dens_frac=self.dens_frac,
+            dens_var_shift=self.dens_var_shift)
+        self.rad_emb_ = embedding_radii(self.embedding_, graph.indptr, graph.indices, q, self.a_, self.b_, n_epochs)[0]
+        return self

@@ -2,13 +2,17 @@
 simplicial set and the layout epochs at the golden 12 449 x 512 embeddings and at a synthetic 172 950 x 512 matrix
 (the size of the reference's full WM-811K dump), on one MI355X.
 
-    python tools/bench_umap.py [--out profiles/umap_bench.md] [--reps 5] [--sizes golden synthetic]
+    python tools/bench_umap.py [--out profiles/umap_bench.md] [--densmap-out FILE] [--reps 5] [--sizes golden synthetic]
 
 Device events around the Python calls, one warm-up call per shape, then --reps calls: median (min .. max).  The kNN
 pass is set next to wm_core_distance on the same rows and k: both are one all-pairs pass of 3 n^2 d float32 operations
 on the vector ALU (157.3 TF peak).  The layout is reported per epoch and as sampled edges per second (an edge
 sample = one attraction and R negative samples, i.e. 1 + R row gathers).  Worst parity figures of the UMAP tests are
-appended when the parity log of tests/parity_log.py exists (tests/test_gpu_umap.py writes into it)."""
+appended when the parity log of tests/parity_log.py exists (tests/test_gpu_umap.py writes into it).
+
+With --densmap-out the DensMAP density phase (manifold.optimize_layout_densmap, wm_densmap_layout) is timed at the same
+shapes and written to that file: 50 epochs that are all in the phase (dens_frac = 1) next to the same 50 epochs of the
+plain layout from the same positions, per epoch, and the once-per-fit graph radii."""
 import argparse
 import json
 import statistics
@@ -54,7 +58,36 @@ def synthetic(n, d, seed):
     return (centers[which] + torch.randn(n, d, generator=g, device=DEV)).contiguous()
 
 
-def bench_shape(name, x, k, reps, lines):
+def bench_density(name, dist, idx, w, reps, lines):
+    """The density phase next to the plain epoch: epochs [0, 50) of n_epochs, all of them in the phase."""
+    graph, dists = manifold.fuzzy_union(idx, w, dist)
+    n = graph.shape[0]
+    n_epochs, span = (700 if n <= 10000 else 400), 50
+    q = manifold.sample_rates(graph.data)
+    live = int((q.long() * n_epochs >= 65536).sum())
+    a, b = manifold.find_ab_params(1.0, 0.1)
+    t_ro, ro = timed(lambda: manifold.graph_radii(graph.indptr, graph.data, dists, q, n_epochs), reps)
+    rad = manifold.standardize_radii(ro)
+    lines += [f"## {name}: {n} vertices, {int(graph.indices.numel())} entries ({live} live at {n_epochs} epochs)", "",
+              f"Graph radii (`wm_densmap_graph_radii`, once per fit): {fmt(t_ro)}.", "",
+              f"| layout, epochs [0, {span}) of {n_epochs} | plain (`wm_umap_layout`) | per epoch | density phase (`wm_densmap_layout`, "
+              "dens_frac = 1) | per epoch | phase / plain |", "|---|---|---|---|---|---|"]
+    rec = {"shape": name, "n": n, "live": live, "graph_radii_ms": t_ro[0], "density": []}
+    for dim in (2, 50):
+        g = torch.Generator(device="cuda").manual_seed(dim)
+        y0 = (10.0 * torch.rand(n, dim, generator=g, device=DEV)).contiguous()
+        t_p, _ = timed(lambda: manifold.optimize_layout(y0, graph.indptr, graph.indices, q, a, b, n_epochs, 0, span), reps)
+        t_d, _ = timed(lambda: manifold.optimize_layout_densmap(y0, graph.indptr, graph.indices, q, graph.data, rad, a, b, n_epochs, 0,
+                                                                span, dens_lambda=1.0, dens_frac=1.0), reps)
+        lines.append(f"| {dim}-D | {fmt(t_p)} | {t_p[0] / span * 1e3:.1f} us | {fmt(t_d)} | {t_d[0] / span * 1e3:.1f} us | "
+                     f"{t_d[0] / t_p[0]:.2f} x |")
+        rec["density"].append({"dim": dim, "epochs": span, "plain_ms": t_p[0], "phase_ms": t_d[0]})
+    lines.append("")
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def bench_shape(name, x, k, reps, lines, dens_lines=None):
     n, d = x.shape
     flop = 3.0 * n * n * d
     t_knn, (dist, idx) = timed(lambda: manifold.knn_graph(x, k), reps)
@@ -88,6 +121,8 @@ def bench_shape(name, x, k, reps, lines):
                               "edge_samples_per_s": samples / t_l[0] * 1e3})
     lines.append("")
     print(json.dumps(rec), flush=True)
+    if dens_lines is not None:
+        rec["densmap"] = bench_density(name, dist, idx, w, max(2, reps // 2), dens_lines)
     return rec
 
 
@@ -121,6 +156,7 @@ def parity_section(lines):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=str(ROOT / "profiles" / "umap_bench.md"))
+    ap.add_argument("--densmap-out", default="", help="also time the DensMAP density phase and write it to this file")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", nargs="+", default=["golden", "synthetic"], choices=["golden", "synthetic"])
     a = ap.parse_args(argv)
@@ -133,17 +169,31 @@ def main(argv=None):
              "pass is 3 n^2 d float32 operations; the share of peak is against the 157.3 TF vector rate.  Per-kernel times",
              "from a profiler trace: not measured.", ""]
     recs = []
+    dens_lines = None
+    if a.densmap_out:
+        dens_lines = ["# DensMAP: the density phase next to the plain layout epoch", "",
+                      "Scope: `csrc/umap.hip` (`wm_densmap_graph_radii`, `wm_densmap_layout`), `manifold.py`.  One MI355X.  Written by",
+                      "`tools/bench_umap.py --densmap-out`: device events around the Python call (validation, workspace and output",
+                      "allocation included), one warm-up call, then the median (min .. max) of the repeats.  A phase epoch is the",
+                      "plain epoch plus one gather pass over all live entries in double, three small reduction launches and the",
+                      "density term's 16-byte gather per sampled entry.", ""]
     if "golden" in a.sizes:
         emb = np.load(ROOT / "tests" / "golden" / "simsiam_preds_subset.npz")["embeddings"].astype(np.float32)
         x = StandardScaler().fit_transform(torch.from_numpy(emb).to(DEV))
-        recs.append(bench_shape("golden SimSiam embeddings, standardised", x, 15, a.reps, lines))
+        recs.append(bench_shape("golden SimSiam embeddings, standardised", x, 15, a.reps, lines, dens_lines))
     if "synthetic" in a.sizes:
-        recs.append(bench_shape("synthetic mixture of 38 Gaussians", synthetic(172950, 512, 0), 15, max(2, a.reps // 2), lines))
+        recs.append(bench_shape("synthetic mixture of 38 Gaussians", synthetic(172950, 512, 0), 15, max(2, a.reps // 2), lines,
+                                dens_lines))
     parity_section(lines)
     out = Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text("\n".join(lines) + "\n")
     print(f"wrote {out}")
+    if dens_lines is not None:
+        dout = Path(a.densmap_out)
+        dout.parent.mkdir(parents=True, exist_ok=True)
+        dout.write_text("\n".join(dens_lines) + "\n")
+        print(f"wrote {dout}")
     return recs
 
 
