@@ -25,8 +25,8 @@
 // their natural [pixel][channel] layout and read with ds_read_b64_tr_b16 (hardware transpose);
 // the k-slot <-> pixel assignment is permuted identically for both operands so that the two
 // 16-lane groups of each 32-lane half read 8 consecutive rows (conflict free with rows padded by
-// 32 B).  Partial sums over pixel ranges (split-K) are combined with f32 atomics into an
-// [K][R][S][C] f32 buffer the caller zeroes.
+// 32 B).  Partial sums over pixel ranges (split-K) are STORED, one [K][R][S][C] f32 slab per split, without
+// atomics; the caller sums the slabs in a fixed order (wm_wgrad_fold / wm_wgrad_finalize).
 //
 // Roofline: MFMA (dense bf16), 2*M*K*R*S*C FLOP per launch.
 #include "common.h"
@@ -90,6 +90,85 @@ __device__ __forceinline__ float cv_gelu_grad(float v) { return wm_gelu_grad(v);
 // 128 zero bytes: the global_load_lds source of padded / out-of-range taps
 __device__ __attribute__((aligned(256))) uint16_t conv_zero_page[128];
 
+// ---- pieces shared by the kernels below
+// MODE 2 (dgrad of a stride-2 convolution) orders the destination pixels by parity class (h & 1, w & 1), a quarter of
+// the rows each: row `row` of the tile at m0 lies in class pc = 2 ph + pw and is pixel (n, 2 h2 + ph, 2 w2 + pw).
+// (A tile lies inside one class: class size % 128 == 0, host-checked.)
+struct ClassRow {
+  int n, h2, w2;
+};
+__device__ __forceinline__ ClassRow class_row(const ConvArgs& a, int m) {  // m: index inside the class
+  uint32_t urem2, uw2;
+  const int n = (int)wm_divmod((uint32_t)m, a.d_h2w2, urem2);
+  const int h2 = (int)wm_divmod(urem2, a.d_w2, uw2);
+  return {n, h2, (int)uw2};
+}
+
+// Eight bf16 in a uint4, elementwise: f(e, value of element e) -> new value of element e
+template <typename F>
+__device__ __forceinline__ uint4 bf16x8_map(uint4 v, F f) {
+  const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+  uint32_t o[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    o[q] = pack_bf2(f(2 * q, bf2f((uint16_t)(vv[q] & 0xffff))), f(2 * q + 1, bf2f((uint16_t)(vv[q] >> 16))));
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+// ... of two operands: f(element of v, element of r)
+template <typename F>
+__device__ __forceinline__ uint4 bf16x8_zip(uint4 v, uint4 r, F f) {
+  const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
+  return bf16x8_map(v, [&](int e, float x) {
+    return f(x, bf2f((uint16_t)((e & 1) ? rr[e >> 1] >> 16 : rr[e >> 1] & 0xffff)));
+  });
+}
+__device__ __forceinline__ uint4 bf16x8_add(uint4 v, uint4 r) {
+  return bf16x8_zip(v, r, [](float x, float y) { return x + y; });
+}
+
+// One accumulator fragment -> the staged bf16 tile in LDS ([pixel][channel], rows of CS bytes: padded by 16 B): an
+// accumulator lane owns 4 consecutive channels, from ch on, of pixel pix.  (Per fragment, the loops over a wave's
+// NJ x 4 fragments stay in the kernels: a helper that takes the accumulator array by reference changed the register
+// allocation of the BatchNorm-backward instantiations and of the stem kernel.)
+__device__ __forceinline__ void stage_acc_frag(uint8_t* tile, int CS, f32x4_t acc, int pix, int ch) {
+  const uint2 v = make_uint2(pack_bf2(acc[0], acc[1]), pack_bf2(acc[2], acc[3]));
+  *reinterpret_cast<uint2*>(tile + pix * CS + ch * 2) = v;
+}
+
+// A PAIR of 8x8 output tiles (the patch kernels): staged row = tile * 64 + ty * 8 + tx; org = first pixel of each tile
+__device__ __forceinline__ size_t pair_origin(const ConvArgs& a, int n, int h0, int w0) {
+  return ((size_t)n * a.DH + h0) * a.DW + w0;
+}
+__device__ __forceinline__ size_t pair_pixel(const size_t (&org)[2], int row, int DW) {
+  return org[row >> 6] + (size_t)((row >> 3) & 7) * DW + (row & 7);
+}
+
+// Statistics slot of a 128-row tile: its group g and the slot t inside the group, a.stat[g][t].  Groups are runs of
+// stat_rpg rows, stat_rpg % 128 == 0.
+struct StatSlot {
+  int g, t;
+};
+__device__ __forceinline__ int stat_tile(const ConvArgs& a, int g, int row0) { return (row0 - g * a.stat_rpg) / 128; }
+// ... of the tile whose first row is row0; t0: slots of the group that precede those of this row space
+__device__ __forceinline__ StatSlot stat_slot(const ConvArgs& a, int row0, int t0 = 0) {
+  const int g = row0 / a.stat_rpg;
+  return {g, t0 + stat_tile(a, g, row0)};
+}
+// ... of tile pair `pair` in the patch kernels' tile order, its first tile in image n0 (groups are whole images)
+__device__ __forceinline__ StatSlot stat_slot_pair(const ConvArgs& a, int n0, int pair) {
+  const int g = (int)(((long long)n0 * a.DH * a.DW) / a.stat_rpg);
+  return {g, pair - g * (a.stat_rpg >> 7)};
+}
+__device__ __forceinline__ float* stat_slot_ptr(const ConvArgs& a, int idx, int DC) { return a.stat + ((size_t)idx * 2) * DC; }
+__device__ __forceinline__ float* stat_slot_ptr(const ConvArgs& a, StatSlot s, int DC) {
+  return stat_slot_ptr(a, s.g * a.stat_nb + s.t, DC);
+}
+// = stat_slot_ptr(a, stat_slot(a, row0), DC), the slot index formed in the order the forward kernels always formed it
+// (through StatSlot the scheduler places one scalar multiply elsewhere in their epilogue)
+__device__ __forceinline__ float* stat_slot_ptr_row(const ConvArgs& a, int row0, int DC) {
+  const int g = row0 / a.stat_rpg;
+  return stat_slot_ptr(a, g * a.stat_nb + stat_tile(a, g, row0), DC);
+}
 
 // Per-channel sums over the block of two per-thread running sums: a thread holds s1[8], s2[8] for the 8 channels of chunk
 // column tid % (BNC / 8), accumulated over its rows of the tile.  Lanes of a wave that share the column are summed on the
@@ -201,7 +280,7 @@ __device__ __forceinline__ void bnb_prefetch(const ConvArgs& a, BnbRegs<BNC>& R,
 // tile's (sum g, sum g * (bn_y - mean)) into its statistics slot.  `red`: 2 x 4 x BNC floats of LDS outside the tile.
 template <int BNC>
 __device__ __forceinline__ void bnb_epilogue(const ConvArgs& a, const BnbRegs<BNC>& R, const uint8_t* smem, int CS, float* red,
-                                             int g, int n0, int tile, int tid) {
+                                             StatSlot slot, int n0, int tid) {
   constexpr int CPR = BNC / 8;
   constexpr int NIT = BnbRegs<BNC>::NIT;
   const int chl = tid % CPR;
@@ -211,6 +290,7 @@ __device__ __forceinline__ void bnb_epilogue(const ConvArgs& a, const BnbRegs<BN
   const bool remask = a.bn_x == nullptr && a.bn_mask == nullptr;
   const bool bitmask = a.bn_mask != nullptr;
   float sc[8], sh[8], mu[8];
+  const int g = slot.g;
   const float* pm = a.bn_mean + (size_t)g * a.DC + c0;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -263,7 +343,7 @@ __device__ __forceinline__ void bnb_epilogue(const ConvArgs& a, const BnbRegs<BN
     }
     *reinterpret_cast<uint4*>(a.dst + R.pixs[it] * a.DC + c0) = make_uint4(o[0], o[1], o[2], o[3]);
   }
-  block_colsums_store<BNC>(s1, s2, red, a.stat + ((size_t)(g * a.stat_nb + tile) * 2) * a.DC, a.DC, n0, tid);
+  block_colsums_store<BNC>(s1, s2, red, stat_slot_ptr(a, slot, a.DC), a.DC, n0, tid);
 }
 
 // Both operand tiles go HBM -> LDS by global_load_lds (16 B per lane, 1 KiB per wave instruction,
@@ -283,20 +363,19 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
   constexpr bool DGRAD = MODE != 0;
   static_assert(!BNB || (DGRAD && !EPI && BM == 128), "BatchNorm-backward epilogue: dgrad tiles of 128 rows");
   extern __shared__ __attribute__((aligned(16))) uint8_t cv_smem[];
-  // BM x BN tile, 4 waves: 2 x 2 waves of 64 px x BN/2 ch for BM = 128; 4 x 1 waves of 64 px x BN ch
-  // for BM = 256 (measured no faster than 128 x 64 on the 64-channel layers: those are bound by the
-  // 9-fold re-read of the input through L2, not by MFMA issue; kept as a template option)
-  constexpr int WN = BM == 128 ? 2 : 1;
+  // BM x BN tile, 4 waves: 2 x 2 waves of 64 px x BN/2 ch.  (A 256-pixel tile of 4 x 1 waves measured no faster than
+  // 128 x 64 on the 64-channel layers: those are bound by the 9-fold re-read of the input through L2, not by MFMA issue.)
+  static_assert(BM == 128, "2 x 2 waves of 64 pixels");
   constexpr int A_BYTES = BM * CV_ROW;
   constexpr int B_BYTES = BN * CV_ROW;
   constexpr int STAGE = A_BYTES + B_BYTES;
   constexpr int NR = BM / 32;          // pixel rows fetched per thread
   constexpr int NB = BN / 32;          // weight rows fetched per thread
-  constexpr int NJ = BN / WN / 16;     // 16-channel fragments per wave
+  constexpr int NJ = BN / 2 / 16;      // 16-channel fragments per wave
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = WN == 2 ? wave >> 1 : wave, wn = WN == 2 ? wave & 1 : 0;
+  const int wm = wave >> 1, wn = wave & 1;
   // tile of this workgroup: column tiles fastest (they share the whole pixel tile), pixel tiles next (neighbours share
   // their halo rows), each XCD a contiguous range of that order (common.h: wm_xcd_swizzle)
   // (MODE 2: its tiles are ordered by parity class and the classes cost different amounts -- three of the four classes
@@ -316,6 +395,17 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
     }
   }
   const int m0 = bm * BM, n0 = bn * BN;
+  // destination pixel of row `row` of this tile: the row itself, except in the class order of MODE 2
+  auto row_pixel = [&](int row) -> size_t {
+    if constexpr (MODE == 2) {
+      const int cls = a.M >> 2;
+      const int pc = m0 / cls;
+      const ClassRow c = class_row(a, m0 + row - pc * cls);
+      return ((size_t)c.n * a.DH + 2 * c.h2 + (pc >> 1)) * a.DW + 2 * c.w2 + (pc & 1);
+    } else {
+      return (size_t)(m0 + row);
+    }
+  };
   const int rowl = tid >> 3;                   // rows rowl + 32 i; (rowl + 32 i) & 7 == rowl & 7
   const int chunk = (tid & 7) ^ (rowl & 7);    // logical 16-byte chunk this lane fetches
 
@@ -335,15 +425,12 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
     nkt = nr * ns * (a.SC >> 6);
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
-      const int m = m0 + rowl + 32 * i - pc * cls;  // index inside the class
-      mv[i] = true;                                   // class size % 128 == 0 (host-checked)
-      uint32_t urem2, uw2;
-      const int n = (int)wm_divmod((uint32_t)m, a.d_h2w2, urem2);
-      const int h2 = (int)wm_divmod(urem2, a.d_w2, uw2), w2 = (int)uw2;
+      const ClassRow c = class_row(a, m0 + rowl + 32 * i - pc * cls);
+      mv[i] = true;  // class size % 128 == 0 (host-checked)
       // source pixel of tap (r, s): (h2 + (ph + pad - r)/2, w2 + (pw + pad - s)/2)
-      bh[i] = h2 + ((ph + a.pad - r0) >> 1);
-      bw[i] = w2 + ((pw + a.pad - s0) >> 1);
-      nb[i] = n * a.SH * a.SW;
+      bh[i] = c.h2 + ((ph + a.pad - r0) >> 1);
+      bw[i] = c.w2 + ((pw + a.pad - s0) >> 1);
+      nb[i] = c.n * a.SH * a.SW;
       p0[i] = a.src + ((long long)(nb[i] + bh[i] * a.SW + bw[i]) * a.SC + chunk * 8);
     }
   } else {
@@ -471,7 +558,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
       }
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const int row = wn * (BN / WN) + j * 16 + fr;
+        const int row = wn * (BN / 2) + j * 16 + fr;
         wf[j] = *reinterpret_cast<const bf16x8_t*>(buf + A_BYTES + row * CV_ROW + ((c ^ (row & 7)) << 4));
       }
 #pragma unroll
@@ -484,19 +571,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
 
   BnbRegs<BNB ? BN : 64> bnb;  // (unused and eliminated unless BNB)
   if constexpr (BNB) {
-    bnb_prefetch<BN>(a, bnb, n0, tid, [&](int row) -> size_t {
-      if constexpr (MODE == 2) {  // class-ordered row -> pixel (n, 2 h2 + ph, 2 w2 + pw)
-        const int cls = a.M >> 2;
-        const int pc = m0 / cls;
-        const int m = m0 + row - pc * cls;
-        uint32_t urem2, uw2;
-        const int n = (int)wm_divmod((uint32_t)m, a.d_h2w2, urem2);
-        const int h2 = (int)wm_divmod(urem2, a.d_w2, uw2), w2 = (int)uw2;
-        return ((size_t)n * a.DH + 2 * h2 + (pc >> 1)) * a.DW + 2 * w2 + (pc & 1);
-      } else {
-        return (size_t)(m0 + row);
-      }
-    });
+    bnb_prefetch<BN>(a, bnb, n0, tid, row_pixel);
   }
   if (nkt > 0) issue(0, smem_base);
   for (int kt = 0; kt < nkt; ++kt) {
@@ -509,41 +584,34 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
   }
   __syncthreads();
 
-  // ---- epilogue: accumulators -> bf16 tile in LDS ([pixel][channel], rows padded by 16 B) -> HBM
+  // ---- epilogue: accumulators -> bf16 tile in LDS -> HBM
   constexpr int CS = BN * 2 + 16;
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int pix = wm * 64 + i * 16 + fr;
-      const int ch = wn * (BN / WN) + j * 16 + fg * 4;
-      const uint2 v = make_uint2(pack_bf2(acc[j][i][0], acc[j][i][1]), pack_bf2(acc[j][i][2], acc[j][i][3]));
-      *reinterpret_cast<uint2*>(cv_smem + pix * CS + ch * 2) = v;
-    }
+    for (int i = 0; i < 4; ++i)
+      stage_acc_frag(cv_smem, CS, acc[j][i], wm * 64 + i * 16 + fr, wn * (BN / 2) + j * 16 + fg * 4);
   __syncthreads();
   if constexpr (MODE == 0 && !EPI) {
     if (a.stat != nullptr) {
       // rows_per_group % BM == 0: the tile is full and lies inside one statistics group; its column sums ride on the
       // store loop
-      const int g = m0 / a.stat_rpg;
-      float* slot = a.stat + ((size_t)(g * a.stat_nb + (m0 - g * a.stat_rpg) / BM) * 2) * a.DC;
-      store_tile_with_stats<BN>(cv_smem, CS, a.dst, a.DC, n0, reinterpret_cast<float*>(cv_smem + BM * CS), slot, tid,
+      store_tile_with_stats<BN>(cv_smem, CS, a.dst, a.DC, n0, reinterpret_cast<float*>(cv_smem + BM * CS),
+                                stat_slot_ptr_row(a, m0, a.DC), tid,
                                 [&](int row) -> size_t { return (size_t)(m0 + row); });
       return;
     }
   }
   if constexpr (BNB) {
-    int g, tile;  // statistics group of this tile and its slot inside the group
-    if constexpr (MODE == 2) {
+    StatSlot slot;
+    if constexpr (MODE == 2) {  // stat_rpg: rows of one statistics group inside a parity class; a group's slots run class by class
       const int cls = a.M >> 2;
-      const int pc = m0 / cls, in_cls = m0 - pc * cls;
-      g = in_cls / a.stat_rpg;  // stat_rpg: rows of one statistics group inside a parity class
-      tile = pc * (a.stat_rpg / BM) + (in_cls - g * a.stat_rpg) / BM;
+      const int pc = m0 / cls;
+      slot = stat_slot(a, m0 - pc * cls, pc * (a.stat_rpg / BM));
     } else {
-      g = m0 / a.stat_rpg;
-      tile = (m0 - g * a.stat_rpg) / BM;
+      slot = stat_slot(a, m0);
     }
-    bnb_epilogue<BN>(a, bnb, cv_smem, CS, reinterpret_cast<float*>(cv_smem + BM * CS), g, n0, tile, tid);
+    bnb_epilogue<BN>(a, bnb, cv_smem, CS, reinterpret_cast<float*>(cv_smem + BM * CS), slot, n0, tid);
     return;
   }
   if constexpr (EPI) {
@@ -555,16 +623,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
     for (int it = 0; it < NIT; ++it) {
       const int p = tid + it * CV_THREADS;
       const int row = p / CPR, ch = p - row * CPR;
-      size_t pix = (size_t)(m0 + row);
-      if constexpr (MODE == 2) {  // class-ordered row -> pixel (n, 2 h2 + ph, 2 w2 + pw)
-        const int cls = a.M >> 2;
-        const int pc = m0 / cls;
-        const int m = m0 + row - pc * cls;
-            uint32_t urem2, uw2;
-        const int n = (int)wm_divmod((uint32_t)m, a.d_h2w2, urem2);
-        const int h2 = (int)wm_divmod(urem2, a.d_w2, uw2), w2 = (int)uw2;
-        pix = ((size_t)n * a.DH + 2 * h2 + (pc >> 1)) * a.DW + 2 * w2 + (pc & 1);
-      }
+      const size_t pix = row_pixel(row);
       pixs[it] = pix;
       // all residual chunks of the thread are requested before the first store (they may alias dst as
       // far as the compiler knows, so it would not hoist them itself)
@@ -593,73 +652,32 @@ __global__ __launch_bounds__(CV_THREADS) void conv_igemm(const ConvArgs a) {
         uint4 v = *reinterpret_cast<const uint4*>(cv_smem + row * CS + ch * 16);
         if constexpr (MODE == 0) {
           if (a.bias != nullptr) {
-            v = make_uint4(pack_bf2(bf2f((uint16_t)(v.x & 0xffff)) + b0.x, bf2f((uint16_t)(v.x >> 16)) + b0.y),
-                           pack_bf2(bf2f((uint16_t)(v.y & 0xffff)) + b0.z, bf2f((uint16_t)(v.y >> 16)) + b0.w),
-                           pack_bf2(bf2f((uint16_t)(v.z & 0xffff)) + b1.x, bf2f((uint16_t)(v.z >> 16)) + b1.y),
-                           pack_bf2(bf2f((uint16_t)(v.w & 0xffff)) + b1.z, bf2f((uint16_t)(v.w >> 16)) + b1.w));
+            const float b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+            v = bf16x8_map(v, [&](int e, float x) { return x + b[e]; });
           }
         }
         if (a.act == 1) {  // v = biased pre-activation (bf16): keep it for the backward pass, emit gelu(v)
           *reinterpret_cast<uint4*>(a.pre_out + pix * a.DC + n0 + ch * 8) = v;
-          const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-          uint32_t o[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            o[e] = pack_bf2(cv_gelu(bf2f((uint16_t)(vv[e] & 0xffff))), cv_gelu(bf2f((uint16_t)(vv[e] >> 16))));
-          v = make_uint4(o[0], o[1], o[2], o[3]);
+          v = bf16x8_map(v, [](int, float x) { return cv_gelu(x); });
         } else if (a.act == 2) {  // v = gradient w.r.t. gelu(pre): times gelu'(pre)
-          const uint4 r4 = rv[it];
-          const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
-          uint32_t o[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            o[e] = pack_bf2(bf2f((uint16_t)(vv[e] & 0xffff)) * cv_gelu_grad(bf2f((uint16_t)(rr[e] & 0xffff))),
-                            bf2f((uint16_t)(vv[e] >> 16)) * cv_gelu_grad(bf2f((uint16_t)(rr[e] >> 16))));
-          v = make_uint4(o[0], o[1], o[2], o[3]);
+          v = bf16x8_zip(v, rv[it], [](float x, float pre) { return x * cv_gelu_grad(pre); });
         } else if (a.res != nullptr) {
-          const uint4 r4 = rv[it];
-          const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
-          uint32_t o[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            o[e] = pack_bf2(bf2f((uint16_t)(vv[e] & 0xffff)) + bf2f((uint16_t)(rr[e] & 0xffff)),
-                            bf2f((uint16_t)(vv[e] >> 16)) + bf2f((uint16_t)(rr[e] >> 16)));
-          v = make_uint4(o[0], o[1], o[2], o[3]);
+          v = bf16x8_add(v, rv[it]);
         }
         *reinterpret_cast<uint4*>(a.dst + pix * a.DC + n0 + ch * 8) = v;
       }
     }
-
   } else {
     constexpr int CPR = BN / 8;
     for (int p = tid; p < BM * CPR; p += CV_THREADS) {
       const int row = p / CPR, ch = p - row * CPR;
-      size_t pix = (size_t)(m0 + row);
-      if constexpr (MODE == 2) {  // class-ordered row -> pixel (n, 2 h2 + ph, 2 w2 + pw)
-        const int cls = a.M >> 2;
-        const int pc = m0 / cls;
-        const int m = m0 + row - pc * cls;
-            uint32_t urem2, uw2;
-        const int n = (int)wm_divmod((uint32_t)m, a.d_h2w2, urem2);
-        const int h2 = (int)wm_divmod(urem2, a.d_w2, uw2), w2 = (int)uw2;
-        pix = ((size_t)n * a.DH + 2 * h2 + (pc >> 1)) * a.DW + 2 * w2 + (pc & 1);
-      }
+      const size_t pix = row_pixel(row);
       if (m0 + row < a.M) {
         uint4 v = *reinterpret_cast<const uint4*>(cv_smem + row * CS + ch * 16);
-        if (a.res != nullptr) {
-          const uint4 r4 = *reinterpret_cast<const uint4*>(a.res + pix * a.DC + n0 + ch * 8);
-          const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
-          uint32_t o[4];
-  #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            o[e] = pack_bf2(bf2f((uint16_t)(vv[e] & 0xffff)) + bf2f((uint16_t)(rr[e] & 0xffff)),
-                            bf2f((uint16_t)(vv[e] >> 16)) + bf2f((uint16_t)(rr[e] >> 16)));
-          v = make_uint4(o[0], o[1], o[2], o[3]);
-        }
+        if (a.res != nullptr) v = bf16x8_add(v, *reinterpret_cast<const uint4*>(a.res + pix * a.DC + n0 + ch * 8));
         *reinterpret_cast<uint4*>(a.dst + pix * a.DC + n0 + ch * 8) = v;
       }
     }
-
   }
 }
 
@@ -737,11 +755,9 @@ __global__ __launch_bounds__(CV_THREADS, BNB ? 3 : 1) void conv3x3_patch(const C
     }
   }
   BnbRegs<64> bnb;  // (unused and eliminated unless BNB)
-  if constexpr (BNB) {
-    const size_t porg[2] = {((size_t)tn[0] * a.DH + th0[0]) * a.DW + tw0[0], ((size_t)tn[1] * a.DH + th0[1]) * a.DW + tw0[1]};
-    bnb_prefetch<64>(a, bnb, 0, tid, [&](int row) -> size_t {
-      return porg[row >> 6] + (size_t)((row >> 3) & 7) * a.DW + (row & 7);
-    });
+  if constexpr (BNB) {  // (the only use of the tile origins in the BNB form: its epilogue stores through the prefetched pixels)
+    const size_t org[2] = {pair_origin(a, tn[0], th0[0], tw0[0]), pair_origin(a, tn[1], th0[1], tw0[1])};
+    bnb_prefetch<64>(a, bnb, 0, tid, [&](int row) -> size_t { return pair_pixel(org, row, a.DW); });
   }
   // ---- weights of one tap: 8 instructions, two per wave (rows rowl, rowl + 32)
   const int rowl = tid >> 3;
@@ -755,7 +771,6 @@ __global__ __launch_bounds__(CV_THREADS, BNB ? 3 : 1) void conv3x3_patch(const C
   };
   issue_w(0, smem_base + PT_PATCH_BYTES);
   issue_w(1, smem_base + PT_PATCH_BYTES + PT_W_BYTES);
-  if (PT_WSTAGES > 3) issue_w(2, smem_base + PT_PATCH_BYTES + 2 * PT_W_BYTES);
 
   f32x4_t acc[2][4];
 #pragma unroll
@@ -788,17 +803,11 @@ __global__ __launch_bounds__(CV_THREADS, BNB ? 3 : 1) void conv3x3_patch(const C
   // ring slot.
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    constexpr int AHEAD = PT_WSTAGES - 1;  // taps in flight ahead (incl. the one waited for)
-    if (tap + AHEAD - 1 < 9) {
-      if (AHEAD == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else if (tap + 1 < 9 && AHEAD == 3) {
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    static_assert(PT_WSTAGES == 3, "two taps in flight: this one and the next");
+    if (tap + 1 < 9) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wm_barrier();                                     // ... everyone's; and the previous tap's reads are over
-    if (tap + AHEAD < 9) issue_w(tap + AHEAD, smem_base + PT_PATCH_BYTES + ((tap + AHEAD) % PT_WSTAGES) * PT_W_BYTES);
+    if (tap + 2 < 9) issue_w(tap + 2, smem_base + PT_PATCH_BYTES + ((tap + 2) % PT_WSTAGES) * PT_W_BYTES);
     const int r = tap / 3, sx = tap % 3;
     const int prow = DGRAD ? 2 - r : r;      // patch row shift
     const int pcol = DGRAD ? 2 - sx : sx;    // patch column shift
@@ -820,33 +829,27 @@ __global__ __launch_bounds__(CV_THREADS, BNB ? 3 : 1) void conv3x3_patch(const C
   }
   __syncthreads();
 
-  // ---- epilogue: accumulators -> bf16 tile in LDS ([pixel][channel], rows padded by 16 B) -> HBM
-  // tile row = wm*64 + ty*8 + tx of 8x8 tile wm
+  // ---- epilogue: accumulators -> bf16 tile in LDS (row = wm*64 + ty*8 + tx of 8x8 tile wm) -> HBM
   constexpr int CS = 64 * 2 + 16;
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int pix = wm * 64 + i * 16 + fr;  // = wm*64 + (2i + dy)*8 + dx
-      const int ch = wn * 32 + j * 16 + fg * 4;
-      const uint2 v = make_uint2(pack_bf2(acc[j][i][0], acc[j][i][1]), pack_bf2(acc[j][i][2], acc[j][i][3]));
-      *reinterpret_cast<uint2*>(cv_smem + pix * CS + ch * 2) = v;
-    }
+    for (int i = 0; i < 4; ++i)
+      stage_acc_frag(cv_smem, CS, acc[j][i], wm * 64 + i * 16 + fr, wn * 32 + j * 16 + fg * 4);
   __syncthreads();
-  const size_t org[2] = {((size_t)tn[0] * a.DH + th0[0]) * a.DW + tw0[0], ((size_t)tn[1] * a.DH + th0[1]) * a.DW + tw0[1]};
+  // both 8x8 tiles lie in one statistics group (host-checked: an even number of tiles per group)
   if constexpr (BNB) {
-    const int g = (int)(((long long)tn[0] * a.DH * a.DW) / a.stat_rpg);
-    bnb_epilogue<64>(a, bnb, cv_smem, CS, reinterpret_cast<float*>(cv_smem + 128 * CS), g, 0,
-                     bx - g * (a.stat_rpg >> 7), tid);
+    bnb_epilogue<64>(a, bnb, cv_smem, CS, reinterpret_cast<float*>(cv_smem + 128 * CS), stat_slot_pair(a, tn[0], bx), 0, tid);
     return;
   }
+  // the other forms need the tile origins only here, after the loop (the BNB form has returned above): computed before
+  // it they would stay live across the nine taps
+  const size_t org[2] = {pair_origin(a, tn[0], th0[0], tw0[0]), pair_origin(a, tn[1], th0[1], tw0[1])};
   if constexpr (MODE == 0) {
     if (a.stat != nullptr) {
-      // both 8x8 tiles lie in one statistics group (host-checked: an even number of tiles per group)
-      const int g = (int)(((long long)tn[0] * a.DH * a.DW) / a.stat_rpg);
-      float* slot = a.stat + ((size_t)(g * a.stat_nb + (bx - g * (a.stat_rpg >> 7))) * 2) * 64;
-      store_tile_with_stats<64>(cv_smem, CS, a.dst, 64, 0, reinterpret_cast<float*>(cv_smem + 128 * CS), slot, tid,
-                                [&](int row) -> size_t { return org[row >> 6] + (size_t)((row >> 3) & 7) * a.DW + (row & 7); });
+      store_tile_with_stats<64>(cv_smem, CS, a.dst, 64, 0, reinterpret_cast<float*>(cv_smem + 128 * CS),
+                                stat_slot_ptr(a, stat_slot_pair(a, tn[0], bx), 64), tid,
+                                [&](int row) -> size_t { return pair_pixel(org, row, a.DW); });
       return;
     }
   }
@@ -854,18 +857,9 @@ __global__ __launch_bounds__(CV_THREADS, BNB ? 3 : 1) void conv3x3_patch(const C
   for (int q = 0; q < 128 * 8 / CV_THREADS; ++q) {
     const int p = tid + q * CV_THREADS;
     const int row = p >> 3, ch = p & 7;
-    const size_t pix = org[row >> 6] + (size_t)((row >> 3) & 7) * a.DW + (row & 7);
+    const size_t pix = pair_pixel(org, row, a.DW);
     uint4 v = *reinterpret_cast<const uint4*>(cv_smem + row * CS + ch * 16);
-    if (a.res != nullptr) {
-      const uint4 r4 = *reinterpret_cast<const uint4*>(a.res + pix * 64 + ch * 8);
-      const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
-      uint32_t o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        o[e] = pack_bf2(bf2f((uint16_t)(vv[e] & 0xffff)) + bf2f((uint16_t)(rr[e] & 0xffff)),
-                        bf2f((uint16_t)(vv[e] >> 16)) + bf2f((uint16_t)(rr[e] >> 16)));
-      v = make_uint4(o[0], o[1], o[2], o[3]);
-    }
+    if (a.res != nullptr) v = bf16x8_add(v, *reinterpret_cast<const uint4*>(a.res + pix * 64 + ch * 8));
     *reinterpret_cast<uint4*>(a.dst + pix * 64 + ch * 8) = v;
   }
 }
@@ -1000,16 +994,12 @@ __global__ __launch_bounds__(CV_THREADS, 3) void conv_stem_patch(const ConvArgs 
       }
     }
 
-    // ---- epilogue: accumulators -> bf16 tile in LDS ([pixel][channel], rows padded by 16 B) -> HBM
+    // ---- epilogue: accumulators -> bf16 tile in LDS -> HBM
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int pix = wm * 64 + i * 16 + fr;  // = wm*64 + (2i + dy)*8 + dx
-        const int ch = wn * 32 + j * 16 + fg * 4;
-        const uint2 v = make_uint2(pack_bf2(acc[j][i][0], acc[j][i][1]), pack_bf2(acc[j][i][2], acc[j][i][3]));
-        *reinterpret_cast<uint2*>(stage + pix * ST_CS + ch * 2) = v;
-      }
+      for (int i = 0; i < 4; ++i)
+        stage_acc_frag(stage, ST_CS, acc[j][i], wm * 64 + i * 16 + fr, wn * 32 + j * 16 + fg * 4);
     __syncthreads();
     const int T0 = pair * 2;
     if (a.stat != nullptr) {
@@ -1027,12 +1017,12 @@ __global__ __launch_bounds__(CV_THREADS, 3) void conv_stem_patch(const ConvArgs 
       int n[2], h0[2], w0[2];
       tile_origin(T0, n[0], h0[0], w0[0]);
       tile_origin(T0 + 1, n[1], h0[1], w0[1]);
-      const size_t org[2] = {((size_t)n[0] * a.DH + h0[0]) * a.DW + w0[0], ((size_t)n[1] * a.DH + h0[1]) * a.DW + w0[1]};
+      const size_t org[2] = {pair_origin(a, n[0], h0[0], w0[0]), pair_origin(a, n[1], h0[1], w0[1])};
 #pragma unroll
       for (int q = 0; q < 128 * 8 / CV_THREADS; ++q) {
         const int p = tid + q * CV_THREADS;
         const int row = p >> 3, ch = p & 7;
-        const size_t pix = org[row >> 6] + (size_t)((row >> 3) & 7) * a.DW + (row & 7);
+        const size_t pix = pair_pixel(org, row, a.DW);
         *reinterpret_cast<uint4*>(a.dst + pix * 64 + ch * 8) = *reinterpret_cast<const uint4*>(stage + row * ST_CS + ch * 16);
       }
     }
@@ -1072,6 +1062,22 @@ constexpr int WG_PIX = 64;  // pixels per staged chunk (two MFMA k-steps)
 template <int ROWB>
 __device__ __forceinline__ int wg_swz(int row, int blk) {
   return ROWB == 256 ? (blk ^ (row & 7)) : (blk ^ ((row >> 1) & 3));
+}
+
+// the 64-pixel chunks [chunk_begin, chunk_begin + iters) that row split bz reduces
+__device__ __forceinline__ void wg_chunk_range(const WgradArgs& a, int bz, int& chunk_begin, int& iters) {
+  chunk_begin = bz * a.chunks_per_split;
+  int chunk_end = chunk_begin + a.chunks_per_split;
+  if (chunk_end > a.total_chunks) chunk_end = a.total_chunks;
+  iters = chunk_end - chunk_begin;  // >= 1: the host derives the split count from chunks_per_split
+}
+// One MFMA operand fragment from two transposed reads (ds_read_b64_tr_b16): k-slots 0..3 of the lane from the 16 x 16
+// block at p0, k-slots 4..7 from the block 16 pixel rows further on, at p1
+__device__ __forceinline__ bf16x8_t wg_frag(const uint8_t* p0, const uint8_t* p1) {
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p0));
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p1));
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8_t, v);
 }
 
 // A block owns BMO output channels x NT consecutive 64-column tiles of the (r,s,c) axis: the dY
@@ -1119,10 +1125,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv_wgrad(const WgradArgs a) {
   const int a_pc = RA == 256 ? (lane & 15) : (lane & 7);   // physical 16-byte slot
   const int x_ro = lane >> 3, x_pc = lane & 7;             // X: 8 rows x 8 slots per instruction
 
-  const int chunk_begin = bz * a.chunks_per_split;
-  int chunk_end = chunk_begin + a.chunks_per_split;
-  if (chunk_end > a.total_chunks) chunk_end = a.total_chunks;
-  const int iters = chunk_end - chunk_begin;  // >= 1: the host derives the split count from chunks_per_split
+  int chunk_begin, iters;
+  wg_chunk_range(a, bz, chunk_begin, iters);
 
   // running (n, p, q) of this lane's two X rows (shared by the NT tiles).  Every chunk advances a row
   // by 64 pixels: (dq, dpp, dn) is that step in mixed radix (Q, P), applied with two carries.
@@ -1217,9 +1221,6 @@ __global__ __launch_bounds__(CV_THREADS) void conv_wgrad(const WgradArgs a) {
   // transposed-read geometry: 16-lane group g, lane (q, p) inside it; MFMA k-slot (g, e) holds
   // pixel 4g + e (e < 4) or 16 + 4g + (e - 4) of the 32-pixel k-step — same map for both operands.
   const int tg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-  auto tr_read = [&](const uint8_t* p) -> s16x4_t {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p));
-  };
   auto compute = [&](const uint8_t* buf) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -1228,10 +1229,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv_wgrad(const WgradArgs a) {
 #pragma unroll
       for (int i = 0; i < MJ; ++i) {
         const int blk = (cout_w + i * 16) >> 4;
-        const s16x4_t lo = tr_read(buf + r0 * RA + wg_swz<RA>(r0, blk) * 32 + 8 * tp);
-        const s16x4_t hi = tr_read(buf + r1 * RA + wg_swz<RA>(r1, blk) * 32 + 8 * tp);
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[i] = __builtin_bit_cast(bf16x8_t, v);
+        af[i] = wg_frag(buf + r0 * RA + wg_swz<RA>(r0, blk) * 32 + 8 * tp,
+                        buf + r1 * RA + wg_swz<RA>(r1, blk) * 32 + 8 * tp);
       }
       if (BIAS && bias_wave) {
 #pragma unroll
@@ -1244,10 +1243,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv_wgrad(const WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const int blk = (col_w + j * 16) >> 4;
-          const s16x4_t lo = tr_read(xb + r0 * RB + wg_swz<RB>(r0, blk) * 32 + 8 * tp);
-          const s16x4_t hi = tr_read(xb + r1 * RB + wg_swz<RB>(r1, blk) * 32 + 8 * tp);
-          const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          bfr[j] = __builtin_bit_cast(bf16x8_t, v);
+          bfr[j] = wg_frag(xb + r0 * RB + wg_swz<RB>(r0, blk) * 32 + 8 * tp,
+                           xb + r1 * RB + wg_swz<RB>(r1, blk) * 32 + 8 * tp);
         }
 #pragma unroll
         for (int i = 0; i < MJ; ++i)
@@ -1314,17 +1311,15 @@ constexpr int WP_LDS = 2 * WP_STAGE;
 
 __global__ __launch_bounds__(CV_THREADS, 2) void conv_wgrad_patch64(const WgradArgs a, const WmDiv d_tpi, const WmDiv d_tw) {
   extern __shared__ __attribute__((aligned(16))) uint8_t wg_smem[];
-  constexpr int RA = 128, RB = 128, MJ = 2, NJ = 2, NT = 9;
+  constexpr int RA = 128, MJ = 2, NJ = 2, NT = 9;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bz = blockIdx.x;
   if (a.xcd) bz = (int)wm_xcd_swizzle(blockIdx.x, gridDim.x);  // neighbouring tiles (shared halo rows) on one XCD
   const int cout_w = (wave >> 1) * 32, col_w = (wave & 1) * 32;  // 2 x 2 waves: 32 output channels x 32 columns of every tap
 
-  const int chunk_begin = bz * a.chunks_per_split;
-  int chunk_end = chunk_begin + a.chunks_per_split;
-  if (chunk_end > a.total_chunks) chunk_end = a.total_chunks;
-  const int iters = chunk_end - chunk_begin;
+  int chunk_begin, iters;
+  wg_chunk_range(a, bz, chunk_begin, iters);
 
   // ---- DMA lane geometry.  dY: instruction i covers tile row ty = i * 4 + wave (8 pixels x 128 B)
   const int a_ro = lane >> 3, a_pc = lane & 7;
@@ -1375,9 +1370,6 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_wgrad_patch64(const WgradA
     for (int j = 0; j < NT * NJ; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int tg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-  auto tr_read = [&](const uint8_t* p) -> s16x4_t {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(p));
-  };
   // pixel 4 tg + tq of the tile = (tg >> 1, 4 (tg & 1) + tq); column block col_w / 16; 8 bytes per tp
   const int x_lane = ((tg >> 1) * WP_PITCH + 4 * (tg & 1) + tq) * WP_XSLOT + (col_w >> 4) * 32 + 8 * tp;
   auto compute = [&](const uint8_t* buf) {
@@ -1389,10 +1381,8 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_wgrad_patch64(const WgradA
 #pragma unroll
       for (int i = 0; i < MJ; ++i) {
         const int blk = (cout_w + i * 16) >> 4;
-        const s16x4_t lo = tr_read(buf + r0 * RA + wg_swz<RA>(r0, blk) * 32 + 8 * tp);
-        const s16x4_t hi = tr_read(buf + r1 * RA + wg_swz<RA>(r1, blk) * 32 + 8 * tp);
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[i] = __builtin_bit_cast(bf16x8_t, v);
+        af[i] = wg_frag(buf + r0 * RA + wg_swz<RA>(r0, blk) * 32 + 8 * tp,
+                        buf + r1 * RA + wg_swz<RA>(r1, blk) * 32 + 8 * tp);
       }
       // this lane's patch address for tap (0, 0), k-step 0, column block 0; everything else is a constant offset
       const uint8_t* xl = xb + x_lane + ks * (4 * WP_PITCH * WP_XSLOT);
@@ -1402,10 +1392,7 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_wgrad_patch64(const WgradA
         bf16x8_t bfr[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          const s16x4_t lo = tr_read(xl + toff + j * 32);
-          const s16x4_t hi = tr_read(xl + toff + j * 32 + 2 * WP_PITCH * WP_XSLOT);
-          const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          bfr[j] = __builtin_bit_cast(bf16x8_t, v);
+          bfr[j] = wg_frag(xl + toff + j * 32, xl + toff + j * 32 + 2 * WP_PITCH * WP_XSLOT);
         }
 #pragma unroll
         for (int i = 0; i < MJ; ++i)
@@ -1442,368 +1429,313 @@ __global__ __launch_bounds__(CV_THREADS, 2) void conv_wgrad_patch64(const WgradA
         }
 }
 
-template <typename K>
-int set_lds(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return e == hipSuccess ? WM_OK : (int)e;
+// ------------------------------------------------------------------------------------ host side
+// Environment switches keep the semantics they always had: the A/B switches (WM_XCD_SWIZZLE, WM_WGRAD_PATCH,
+// WM_WGRAD_PATCH_BLOCKS) are read on every call, the others once.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
+}
+inline int xcd_order() { return env_int("WM_XCD_SWIZZLE", 1); }  // 0: hardware block order
+inline bool conv_patch_enabled() {  // WM_CONV_PATCH=0 keeps conv_igemm where a patch-resident forward / dgrad kernel would run
+  static const bool on = env_int("WM_CONV_PATCH", 1) != 0;
+  return on;
 }
 
-template <int BM, int BN, int CPT, int MODE, bool EPI = false, bool BNB = false>
-int launch_igemm(const ConvArgs& a, hipStream_t st) {
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Raise a kernel's dynamic-LDS limit before its first launch (one flag per kernel: the kernel is a template argument)
+template <auto Kernel>
+int ensure_lds(int bytes) {
+  static bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  return WM_OK;
+}
+
+// The eleven integers every entry point receives: "x" is always the forward input [N][H][W][C], "y" the forward
+// output [N][P][Q][K].
+struct ConvGeom {
+  int N, H, W, C, K, R, S, P, Q, stride, pad;
+  long long rows_x() const { return (long long)N * H * W; }
+  long long rows_y() const { return (long long)N * P * Q; }
+};
+
+int conv_check(const ConvGeom& g) {
+  WM_REQUIRE(g.N > 0 && g.H > 0 && g.W > 0 && g.C > 0 && g.K > 0 && g.R > 0 && g.S > 0 && g.P > 0 && g.Q > 0, WM_EINVAL);
+  WM_REQUIRE(g.stride == 1 || g.stride == 2, WM_EUNSUPPORTED);
+  WM_REQUIRE(g.pad >= 0 && g.pad <= g.R, WM_EUNSUPPORTED);
+  WM_REQUIRE(g.K % 64 == 0, WM_EUNSUPPORTED);
+  WM_REQUIRE(g.C % 64 == 0 || (g.C == 16 && g.S == 4), WM_EUNSUPPORTED);
+  // every output pixel's window must start no later than the input's far edge
+  WM_REQUIRE((long long)(g.P - 1) * g.stride - g.pad < g.H && (long long)(g.Q - 1) * g.stride - g.pad < g.W, WM_EINVAL);
+  WM_REQUIRE(g.rows_y() < (1ll << 31) && g.rows_x() * g.C < (1ll << 40), WM_EUNSUPPORTED);
+  WM_REQUIRE(g.rows_x() < (1ll << 31), WM_EUNSUPPORTED);
+  return WM_OK;
+}
+
+// Geometry part of the kernel arguments of a forward (x -> y) or input-gradient (dy -> dx) launch; the caller adds the
+// operand pointers and the optional epilogues (all null here)
+ConvArgs conv_args(const ConvGeom& g, bool dgrad) {
+  ConvArgs a{};
+  a.xcd = xcd_order();
+  a.N = g.N; a.R = g.R; a.S = g.S; a.stride = g.stride; a.pad = g.pad;
+  if (!dgrad) {
+    a.SH = g.H; a.SW = g.W; a.SC = g.C; a.DH = g.P; a.DW = g.Q; a.DC = g.K;
+    a.nkt = g.C == 16 ? g.R : g.R * g.S * (g.C / 64);  // stem: one k-tile per kernel row
+    a.d_h2w2 = wm_div_make(1); a.d_w2 = wm_div_make(1);
+  } else {
+    a.SH = g.P; a.SW = g.Q; a.SC = g.K; a.DH = g.H; a.DW = g.W; a.DC = g.C;
+    a.nkt = g.R * g.S * (g.K / 64);
+    a.d_h2w2 = wm_div_make((uint32_t)((g.H >> 1) * (g.W >> 1) > 0 ? (g.H >> 1) * (g.W >> 1) : 1));
+    a.d_w2 = wm_div_make((uint32_t)((g.W >> 1) > 0 ? (g.W >> 1) : 1));
+  }
+  a.M = a.N * a.DH * a.DW;
+  a.d_dhw = wm_div_make((uint32_t)(a.DH * a.DW)); a.d_dw = wm_div_make((uint32_t)a.DW);
+  a.stat_rpg = 1;
+  return a;
+}
+
+// ---- which kernel serves a geometry: predicates over the geometry and the few flags they need
+// The tile-pair kernels: output the size of the input, sides multiples of 8, an even number of 8x8 tiles; with
+// statistics (stat_rpg rows per group, 0: none) an even number of tiles per group and groups of whole images
+inline bool tile_pairs_ok(const ConvGeom& g, int stat_rpg) {
+  if (g.P != g.H || g.Q != g.W || (g.H & 7) || (g.W & 7)) return false;
+  if (((long long)g.N * (g.H >> 3) * (g.W >> 3)) & 1) return false;
+  return stat_rpg == 0 || (stat_rpg % 128 == 0 && stat_rpg % (g.H * g.W) == 0);
+}
+// conv3x3_patch: 3x3 / stride 1 / pad 1, 64 -> 64 channels, forward or input gradient
+inline bool conv_patch_ok(const ConvGeom& g, bool has_bias, int stat_rpg) {
+  return conv_patch_enabled() && g.C == 64 && g.K == 64 && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 &&
+         !has_bias && tile_pairs_ok(g, stat_rpg);
+}
+// conv_stem_patch: the space-to-depth stem, 4x4 window, stride 1, 16 source channels, 64 outputs
+inline bool stem_patch_ok(const ConvGeom& g, bool has_bias, bool has_res, int stat_rpg) {
+  return conv_patch_enabled() && g.C == 16 && g.K == 64 && g.R == 4 && g.S == 4 && g.stride == 1 && g.pad >= 0 &&
+         g.pad <= 3 && !has_bias && !has_res && tile_pairs_ok(g, stat_rpg);
+}
+// conv_wgrad_patch64 (no bias-gradient form): WM_WGRAD_PATCH=0 keeps conv_wgrad<64, 8, 3>
+inline bool wgrad_patch_ok(const ConvGeom& g) {
+  return env_int("WM_WGRAD_PATCH", 1) != 0 && g.C == 64 && g.K == 64 && g.R == 3 && g.S == 3 && g.stride == 1 &&
+         g.pad == 1 && g.P == g.H && g.Q == g.W && (g.H & 7) == 0 && (g.W & 7) == 0;
+}
+// conv_igemm MODE of an input gradient.  Stride 1: MODE 3 = MODE 1 without the stride-2 address path in the k-loop's
+// issue phase (hipcc if-converts the run-time branch: its 64-bit address arithmetic was executed on every k-step).
+// Stride 2 with even image sides and class size % 128 == 0: MODE 2, parity-class ordering (no wasted taps).
+inline long long dgrad_class_rows(const ConvGeom& g) { return (long long)g.N * (g.H / 2) * (g.W / 2); }
+inline int dgrad_mode(const ConvGeom& g) {
+  if (g.stride == 1) return 3;
+  return (g.H % 2 == 0 && g.W % 2 == 0 && dgrad_class_rows(g) % 128 == 0) ? 2 : 1;
+}
+// rows of the space the statistics groups of the BatchNorm-backward epilogue divide: all of them, or one parity class
+inline long long dgrad_stat_rows(const ConvGeom& g, int mode) { return mode == 2 ? dgrad_class_rows(g) : g.rows_x(); }
+
+// ---- launches
+template <int BM, int BN, int CPT, int MODE, bool EPI, bool BNB>
+int launch_igemm_tile(const ConvArgs& a, hipStream_t st) {
   // two operand stages; the epilogue reuses them: staged tile BM x (BN * 2 + 16) B + the forward-statistics scratch
   // (2 x 256 floats) or the 16 KB of cross-thread sums of the BatchNorm-backward epilogue -- always smaller
   constexpr int lds = 2 * (BM * CV_ROW + BN * CV_ROW);
   static_assert(BM * (BN * 2 + 16) + 2 * CV_THREADS * 4 <= lds, "epilogue LDS");
-  static bool attr = false;
-  if (!attr) {
-    const int rc = set_lds(&conv_igemm<BM, BN, CPT, MODE, EPI, BNB>, lds);
-    if (rc != WM_OK) return rc;
-    attr = true;
-  }
+  const int rc = ensure_lds<&conv_igemm<BM, BN, CPT, MODE, EPI, BNB>>(lds);
+  if (rc != WM_OK) return rc;
   dim3 grid(wm_cdiv(a.M, BM), a.DC / BN);
   conv_igemm<BM, BN, CPT, MODE, EPI, BNB><<<grid, CV_THREADS, lds, st>>>(a);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
-
-// 3x3 / stride 1 / pad 1, 64 -> 64 channels, image sides multiples of 8, an even number of 8x8 tiles
-// (and of tiles per statistics group): the patch-resident kernel.  WM_CONV_PATCH=0 keeps conv_igemm.
-inline bool conv_patch_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("WM_CONV_PATCH");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
-}
-
-inline bool conv_patch_ok(const ConvArgs& a) {
-  if (!conv_patch_enabled()) return false;
-  if (a.SC != 64 || a.DC != 64 || a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1) return false;
-  if (a.SH != a.DH || a.SW != a.DW || (a.DH & 7) || (a.DW & 7) || a.bias != nullptr) return false;
-  const long long tiles = (long long)a.N * (a.DH >> 3) * (a.DW >> 3);
-  if (tiles & 1) return false;
-  if (a.stat != nullptr) {
-    if (a.stat_rpg % 128 != 0) return false;           // tiles per group even
-    if (a.stat_rpg % (a.DH * a.DW) != 0) return false;  // groups are whole images
-  }
-  return true;
-}
-
-// The space-to-depth stem in its patch-resident form: 4x4 window, stride 1, 16 source channels, 64 outputs, output
-// the size of the source, sides multiples of 8, an even number of 8x8 tiles (per statistics group too).
-inline bool stem_patch_ok(const ConvArgs& a) {
-  if (!conv_patch_enabled()) return false;
-  if (a.SC != 16 || a.DC != 64 || a.R != 4 || a.S != 4 || a.stride != 1 || a.pad < 0 || a.pad > 3) return false;
-  if (a.SH != a.DH || a.SW != a.DW || (a.DH & 7) || (a.DW & 7) || a.bias != nullptr || a.res != nullptr) return false;
-  const long long tiles = (long long)a.N * (a.DH >> 3) * (a.DW >> 3);
-  if (tiles & 1) return false;
-  if (a.stat != nullptr) {
-    if (a.stat_rpg % 128 != 0) return false;
-    if (a.stat_rpg % (a.DH * a.DW) != 0) return false;
-  }
-  return true;
+// 128 output channels per block where they divide the layer's, else 64
+template <int CPT, int MODE, bool EPI = false, bool BNB = false>
+int launch_igemm(const ConvArgs& a, hipStream_t st) {
+  return a.DC % 128 == 0 ? launch_igemm_tile<128, 128, CPT, MODE, EPI, BNB>(a, st)
+                         : launch_igemm_tile<128, 64, CPT, MODE, EPI, BNB>(a, st);
 }
 
 template <int MODE, bool BNB = false>
 int launch_patch(const ConvArgs& a, hipStream_t st) {
   static_assert(128 * (64 * 2 + 16) + 2 * CV_THREADS * 4 <= PT_LDS, "epilogue LDS");
-  static bool attr = false;
-  if (!attr) {
-    const int rc = set_lds(&conv3x3_patch<MODE, BNB>, PT_LDS);
-    if (rc != WM_OK) return rc;
-    attr = true;
-  }
+  const int rc = ensure_lds<&conv3x3_patch<MODE, BNB>>(PT_LDS);
+  if (rc != WM_OK) return rc;
   const int blocks = (int)((long long)a.N * (a.DH >> 3) * (a.DW >> 3) / 2);
-  static int lds_pad = -1;  // WM_PATCH_LDS_PAD: extra dynamic LDS per block (experiment: 12288 -> two blocks per CU)
-  if (lds_pad < 0) {
-    const char* e = getenv("WM_PATCH_LDS_PAD");
-    lds_pad = e ? atoi(e) : 0;
-    if (lds_pad > 0 && set_lds(&conv3x3_patch<MODE, BNB>, PT_LDS + lds_pad) != WM_OK) lds_pad = 0;
-  }
-  conv3x3_patch<MODE, BNB><<<blocks, CV_THREADS, PT_LDS + lds_pad, st>>>(a);
+  conv3x3_patch<MODE, BNB><<<blocks, CV_THREADS, PT_LDS, st>>>(a);
   WM_LAUNCH_CHECK();
   return WM_OK;
-}
-
-// split-K plan of a weight-gradient launch: enough blocks to fill the chip (2 resident per CU), no more -- every split
-// writes (and the fold reads) one K x R x S x C slab
-inline void wgrad_plan(const WgradArgs& a, int BMO, int NT, int& nsplit, int& chunks_per_split, int& total_chunks) {
-  const int colgroups = a.R * a.S * a.C / 64 / NT;
-  const int ktiles = a.K / BMO;
-  total_chunks = wm_cdiv((long long)a.N * a.P * a.Q, WG_PIX);
-  static int target = 0;
-  if (target == 0) {
-    const char* e = getenv("WM_WGRAD_BLOCKS");
-    target = e ? atoi(e) : 512;
-  }
-  // Linear layers (1 x 1 on a 1 x 1 image: the transformer GEMMs): the output tile is small and every split ends in
-  // a K x C f32 slab (round 2, with atomics: half the blocks, 3.06 vs 3.57 ms of wgrad per DINO ViT-Tiny step).
-  // Re-measured with slabs (round 3, ms per step at 256 / 512 blocks): DINO ViT-Tiny 9.79 / 9.53, DINO ViT-S 19.68 / 18.62
-  // (39 424 token rows: the slab traffic is small beside the operands), MAE ViT-S/16 4.64 / 4.74 (3 200 and 12 608 rows:
-  // there every extra split is mostly slab bytes).  So: the full target from 16 384 rows on, half of it below.
-  static int target_lin = -1;
-  if (target_lin < 0) {
-    const char* e = getenv("WM_WGRAD_BLOCKS_LINEAR");
-    target_lin = e ? atoi(e) : 0;
-  }
-  int tgt = target;
-  if (a.R * a.S == 1 && a.H * a.W == 1 && target == 512) tgt = target_lin > 0 ? target_lin : (total_chunks >= 256 ? 512 : 256);
-  if (NT == 9) {  // conv_wgrad_patch64: one block owns the whole K x R x S x C gradient, every split costs a full slab
-    // (kernel alone 112 us with 512 blocks, 130 with 256 -- but the fold then reads 150 instead of 300 MB of slabs
-    // for the four layer1 convolutions: SimCLR step 11.32 ms with 256 or 384 blocks, 11.38 with 512, 11.51 without this
-    // kernel, one box)
-    const char* e = getenv("WM_WGRAD_PATCH_BLOCKS");  // (read per call)
-    tgt = e ? atoi(e) : 256;
-  }
-  nsplit = tgt / (colgroups * ktiles);
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > total_chunks) nsplit = total_chunks;
-  chunks_per_split = wm_cdiv(total_chunks, nsplit);
-  nsplit = wm_cdiv(total_chunks, chunks_per_split);
-}
-
-template <int BMO, int CPT, int NT, bool BIAS>
-int launch_wgrad_impl(WgradArgs a, hipStream_t st) {
-  constexpr int lds = 2 * (WG_PIX * BMO * 2 + NT * WG_PIX * 128);
-  static bool attr = false;
-  if (!attr) {
-    const int rc = set_lds(&conv_wgrad<BMO, CPT, NT, BIAS>, lds);
-    if (rc != WM_OK) return rc;
-    attr = true;
-  }
-  int nsplit;
-  wgrad_plan(a, BMO, NT, nsplit, a.chunks_per_split, a.total_chunks);
-  dim3 grid(a.R * a.S * a.C / 64 / NT, a.K / BMO, nsplit);
-  conv_wgrad<BMO, CPT, NT, BIAS><<<grid, CV_THREADS, lds, st>>>(a);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
-}
-
-template <int BMO, int CPT, int NT>
-int launch_wgrad(const WgradArgs& a, hipStream_t st) {
-  if (a.dbias == nullptr) return launch_wgrad_impl<BMO, CPT, NT, false>(a, st);
-  if constexpr (CPT == 8) return launch_wgrad_impl<BMO, CPT, NT, true>(a, st);
-  return WM_EUNSUPPORTED;  // no bias gradient on the space-to-depth stem form
-}
-
-// the patch-resident form (conv_wgrad_patch64): WM_WGRAD_PATCH=0 keeps conv_wgrad<64, 8, 3>
-inline bool wgrad_patch_ok(const WgradArgs& a) {
-  const char* e = getenv("WM_WGRAD_PATCH");  // (read per call: A/B switch)
-  if (e != nullptr && atoi(e) == 0) return false;
-  return a.C == 64 && a.K == 64 && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.P == a.H && a.Q == a.W &&
-         (a.H & 7) == 0 && (a.W & 7) == 0 && a.dbias == nullptr;
-}
-inline int launch_wgrad_patch(WgradArgs a, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    const int rc = set_lds(&conv_wgrad_patch64, WP_LDS);
-    if (rc != WM_OK) return rc;
-    attr = true;
-  }
-  int nsplit;
-  wgrad_plan(a, 64, 9, nsplit, a.chunks_per_split, a.total_chunks);  // one block per split: all nine taps, all 64 channels
-  const int tiles_w = a.W >> 3, tpi = (a.H >> 3) * tiles_w;
-  conv_wgrad_patch64<<<nsplit, CV_THREADS, WP_LDS, st>>>(a, wm_div_make((uint32_t)tpi), wm_div_make((uint32_t)tiles_w));
-  WM_LAUNCH_CHECK();
-  return WM_OK;
-}
-
-// tile configuration of a weight-gradient shape (one place: the launch and wm_conv2d_wgrad_splits must agree)
-inline void wgrad_config(int C, int K, int R, int S, int& bmo, int& cpt, int& nt) {
-  const int coltiles = R * S * C / 64;
-  if (C == 16) {  // stem: the 4 kernel rows together
-    cpt = 2;
-    if (K % 128 == 0) { bmo = 128; nt = coltiles % 2 == 0 ? 2 : 1; }
-    else { bmo = 64; nt = coltiles % 4 == 0 ? 4 : 1; }
-    return;
-  }
-  cpt = 8;
-  if (K % 128 == 0) {
-    bmo = 128;
-    static int force_nt = -1;  // WM_WGRAD_NT: experiment switch (1, 2 or 3 column tiles per block)
-    if (force_nt < 0) {
-      const char* e = getenv("WM_WGRAD_NT");
-      force_nt = e ? atoi(e) : 0;
-    }
-    if (force_nt == 3 && coltiles % 3 == 0) { nt = 3; return; }
-    if (force_nt == 2 && coltiles % 2 == 0) { nt = 2; return; }
-    if (force_nt == 1) { nt = 1; return; }
-    // column tiles per block, measured per ResNet-18 shape at batch 512 (profiles/r01_conv_layers_v3.txt):
-    // three taps per block where the dY tile is the larger share of the traffic (C <= 128 with K = 128)
-    // and for the 512-channel layers, two for 256 channels, one for the stride-2 128 -> 256 layer
-    nt = (coltiles % 2 == 0 && C > 128) ? 2 : 1;
-    // 3x3: three taps per block everywhere.  (Round 1 measured one tap per block best for the stride-2 128 -> 256 layer
-    // and two for 256 channels -- with f32 atomics and hardware block order.  With slabs and the blocks of a row split on
-    // one XCD, tools/bench_conv.py at batch 512: layer3.0 105.5 -> 73.0 us, layer3 3x3 145.7 -> 132.1 us.)
-    if (R * S == 9) nt = 3;
-    if (nt == 3 && coltiles % 3 != 0) nt = 1;
-    if (nt == 2 && coltiles % 2 != 0) nt = 1;
-    return;
-  }
-  bmo = 64;
-  nt = coltiles % 3 == 0 ? 3 : 1;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-inline int xcd_order() {  // WM_XCD_SWIZZLE=0: hardware block order (A/B switch; read per call)
-  const char* e = getenv("WM_XCD_SWIZZLE");
-  return e != nullptr ? atoi(e) : 1;
-}
-
-}  // namespace
-
-// Geometry checks shared by the three entry points.  "x" is always the forward input
-// [N][H][W][C], "y" the forward output [N][P][Q][K].
-static int conv_check(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad) {
-  WM_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0 && P > 0 && Q > 0, WM_EINVAL);
-  WM_REQUIRE(stride == 1 || stride == 2, WM_EUNSUPPORTED);
-  WM_REQUIRE(pad >= 0 && pad <= R, WM_EUNSUPPORTED);
-  WM_REQUIRE(K % 64 == 0, WM_EUNSUPPORTED);
-  WM_REQUIRE(C % 64 == 0 || (C == 16 && S == 4), WM_EUNSUPPORTED);
-  // every output pixel's window must start no later than the input's far edge
-  WM_REQUIRE((long long)(P - 1) * stride - pad < H && (long long)(Q - 1) * stride - pad < W, WM_EINVAL);
-  WM_REQUIRE((long long)N * P * Q < (1ll << 31) && (long long)N * H * W * C < (1ll << 40), WM_EUNSUPPORTED);
-  WM_REQUIRE((long long)N * H * W < (1ll << 31), WM_EUNSUPPORTED);
-  return WM_OK;
-}
-
-static int conv_fwd_impl(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C, int K, int R,
-                         int S, int P, int Q, int stride, int pad, float* stat, int stat_nb, int stat_rpg,
-                         void* stream, const float* bias = nullptr, const void* residual = nullptr,
-                         void* pre_out = nullptr);
-
-extern "C" int wm_conv2d_fwd(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C,
-                             int K, int R, int S, int P, int Q, int stride, int pad, void* stream) {
-  return conv_fwd_impl(x, w_krsc, y, N, H, W, C, K, R, S, P, Q, stride, pad, nullptr, 0, 0, stream);
-}
-
-extern "C" int wm_conv2d_fwd_bias_res(const void* x, const void* w_krsc, const float* bias, const void* residual,
-                                      void* y, int N, int H, int W, int C, int K, int R, int S, int P, int Q,
-                                      int stride, int pad, void* stream) {
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(residual) & 15) == 0, WM_EALIGN);
-  return conv_fwd_impl(x, w_krsc, y, N, H, W, C, K, R, S, P, Q, stride, pad, nullptr, 0, 0, stream, bias, residual);
-}
-
-// Statistics slots per group a forward-with-statistics launch of this geometry writes: one per 128-row tile, except
-// the persistent stem kernel, whose blocks accumulate over their tiles and write one slot each.
-static int stem_patch_slots();
-extern "C" int wm_conv2d_fwd_stats_tiles(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride,
-                                         int pad, int rows_per_group) {
-  if (conv_check(N, H, W, C, K, R, S, P, Q, stride, pad) != WM_OK || rows_per_group <= 0) return WM_EINVAL;
-  const long long M = (long long)N * P * Q;
-  if (rows_per_group % 128 != 0 || M % rows_per_group != 0) return WM_EUNSUPPORTED;
-  if (C == 16) {
-    ConvArgs a{};
-    a.N = N; a.SH = H; a.SW = W; a.SC = C; a.DH = P; a.DW = Q; a.DC = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-    a.M = (int)M; a.stat = reinterpret_cast<float*>(1); a.stat_rpg = rows_per_group; a.bias = nullptr; a.res = nullptr;
-    if (stem_patch_ok(a)) {
-      const int pairs_g = rows_per_group / 128;
-      const int slots = stem_patch_slots();
-      return pairs_g < slots ? pairs_g : slots;
-    }
-  }
-  return rows_per_group / 128;
-}
-
-extern "C" int wm_conv2d_fwd_stats(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C,
-                                   int K, int R, int S, int P, int Q, int stride, int pad, float* stat_part,
-                                   int stat_tiles, int rows_per_group, void* stream) {
-  WM_REQUIRE(stat_part && rows_per_group > 0, WM_EINVAL);
-  WM_REQUIRE(rows_per_group % 128 == 0 && ((long long)N * P * Q) % rows_per_group == 0, WM_EUNSUPPORTED);
-  WM_REQUIRE(stat_tiles == wm_conv2d_fwd_stats_tiles(N, H, W, C, K, R, S, P, Q, stride, pad, rows_per_group), WM_EINVAL);
-  return conv_fwd_impl(x, w_krsc, y, N, H, W, C, K, R, S, P, Q, stride, pad, stat_part, stat_tiles, rows_per_group, stream);
 }
 
 // resident blocks of the persistent stem kernel: 38 KB of LDS, 168 registers per lane -> three per CU
-static int stem_patch_slots() {
+int stem_patch_slots() {
   static int slots = 0;
   if (slots == 0) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
-    const char* e = getenv("WM_STEM_BLOCKS_PER_CU");
-    slots = cus * (e ? atoi(e) : 3);
+    slots = cus * env_int("WM_STEM_BLOCKS_PER_CU", 3);
   }
   return slots;
 }
+// Statistics slots per group of the stem kernel: its blocks accumulate over their tile pairs and write one slot each
+inline int stem_patch_group_slots(int pairs_g) {
+  const int slots = stem_patch_slots();
+  return pairs_g < slots ? pairs_g : slots;
+}
+int launch_stem_patch(const ConvArgs& a, hipStream_t st) {
+  const int rc = ensure_lds<&conv_stem_patch>(ST_LDS);
+  if (rc != WM_OK) return rc;
+  const int npairs = (int)((long long)a.N * (a.DH >> 3) * (a.DW >> 3) / 2);
+  // one launch per statistics group (whole images, an even number of tiles: stem_patch_ok): a block then flushes
+  // its running sums once, after its last tile pair
+  const int groups = a.stat != nullptr ? a.M / a.stat_rpg : 1;
+  const int n_g = a.N / groups;
+  const int pairs_g = npairs / groups;
+  for (int g = 0; g < groups; ++g) {
+    ConvArgs ag = a;
+    ag.N = n_g;
+    ag.M = n_g * a.DH * a.DW;
+    ag.src = a.src + (size_t)g * n_g * a.SH * a.SW * 16;
+    ag.dst = a.dst + (size_t)g * n_g * a.DH * a.DW * 64;
+    if (a.stat != nullptr) ag.stat = a.stat + (size_t)g * a.stat_nb * 2 * 64;  // (stat_nb = blocks of a launch)
+    conv_stem_patch<<<stem_patch_group_slots(pairs_g), CV_THREADS, ST_LDS, st>>>(
+        ag, pairs_g, wm_div_make((uint32_t)((a.DH >> 3) * (a.DW >> 3))), wm_div_make((uint32_t)(a.DW >> 3)));
+    WM_LAUNCH_CHECK();
+  }
+  return WM_OK;
+}
 
-static int conv_fwd_impl(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C, int K, int R,
-                         int S, int P, int Q, int stride, int pad, float* stat, int stat_nb, int stat_rpg,
-                         void* stream, const float* bias, const void* residual, void* pre_out) {
-  WM_REQUIRE(pre_out == nullptr || (residual == nullptr && R == 1 && S == 1), WM_EUNSUPPORTED);
+// ---- weight gradient: the kernel, its tile shape and its split-K plan, chosen in one place: the launch and
+// wm_conv2d_wgrad_splits agree by construction
+struct WgradChoice {
+  bool patch;        // conv_wgrad_patch64; else conv_wgrad<bmo, cpt, nt>
+  int bmo, cpt, nt;  // (patch: 64 output channels, all nine taps in one block)
+  int nsplit, chunks_per_split, total_chunks;
+};
+inline void wgrad_tiles(const ConvGeom& g, WgradChoice& c) {
+  const int coltiles = g.R * g.S * g.C / 64;
+  if (g.C == 16) {  // stem: the 4 kernel rows together
+    c.cpt = 2;
+    if (g.K % 128 == 0) { c.bmo = 128; c.nt = coltiles % 2 == 0 ? 2 : 1; }
+    else { c.bmo = 64; c.nt = coltiles % 4 == 0 ? 4 : 1; }
+    return;
+  }
+  c.cpt = 8;
+  if (g.K % 128 == 0) {
+    c.bmo = 128;
+    // column tiles per block, measured per ResNet-18 shape at batch 512 (profiles/r01_conv_layers_v3.txt):
+    // three taps per block where the dY tile is the larger share of the traffic (C <= 128 with K = 128)
+    // and for the 512-channel layers, two for 256 channels, one for the stride-2 128 -> 256 layer
+    c.nt = (coltiles % 2 == 0 && g.C > 128) ? 2 : 1;
+    // 3x3: three taps per block everywhere.  (Round 1 measured one tap per block best for the stride-2 128 -> 256 layer
+    // and two for 256 channels -- with f32 atomics and hardware block order.  With slabs and the blocks of a row split on
+    // one XCD, tools/bench_conv.py at batch 512: layer3.0 105.5 -> 73.0 us, layer3 3x3 145.7 -> 132.1 us.)
+    if (g.R * g.S == 9) c.nt = 3;
+    if (c.nt == 3 && coltiles % 3 != 0) c.nt = 1;
+    return;
+  }
+  c.bmo = 64;
+  c.nt = coltiles % 3 == 0 ? 3 : 1;
+}
+// split-K plan: enough blocks to fill the chip (2 resident per CU), no more -- every split writes (and the fold reads)
+// one K x R x S x C slab
+inline void wgrad_plan(const ConvGeom& g, WgradChoice& c) {
+  const int colgroups = g.R * g.S * g.C / 64 / c.nt;
+  const int ktiles = g.K / c.bmo;
+  c.total_chunks = wm_cdiv(g.rows_y(), WG_PIX);
+  static const int target = env_int("WM_WGRAD_BLOCKS", 512);
+  // Linear layers (1 x 1 on a 1 x 1 image: the transformer GEMMs): the output tile is small and every split ends in
+  // a K x C f32 slab (round 2, with atomics: half the blocks, 3.06 vs 3.57 ms of wgrad per DINO ViT-Tiny step).
+  // Re-measured with slabs (round 3, ms per step at 256 / 512 blocks): DINO ViT-Tiny 9.79 / 9.53, DINO ViT-S 19.68 / 18.62
+  // (39 424 token rows: the slab traffic is small beside the operands), MAE ViT-S/16 4.64 / 4.74 (3 200 and 12 608 rows:
+  // there every extra split is mostly slab bytes).  So: the full target from 16 384 rows on, half of it below.
+  static const int target_lin = env_int("WM_WGRAD_BLOCKS_LINEAR", 0);
+  int tgt = target;
+  if (g.R * g.S == 1 && g.H * g.W == 1 && target == 512) tgt = target_lin > 0 ? target_lin : (c.total_chunks >= 256 ? 512 : 256);
+  // conv_wgrad_patch64: one block owns the whole K x R x S x C gradient, every split costs a full slab
+  // (kernel alone 112 us with 512 blocks, 130 with 256 -- but the fold then reads 150 instead of 300 MB of slabs
+  // for the four layer1 convolutions: SimCLR step 11.32 ms with 256 or 384 blocks, 11.38 with 512, 11.51 without this
+  // kernel, one box)
+  if (c.patch) tgt = env_int("WM_WGRAD_PATCH_BLOCKS", 256);
+  c.nsplit = tgt / (colgroups * ktiles);
+  if (c.nsplit < 1) c.nsplit = 1;
+  if (c.nsplit > c.total_chunks) c.nsplit = c.total_chunks;
+  c.chunks_per_split = wm_cdiv(c.total_chunks, c.nsplit);
+  c.nsplit = wm_cdiv(c.total_chunks, c.chunks_per_split);
+}
+// (The choice is made WITHOUT regard to a bias gradient: wm_conv2d_wgrad_splits answers for the geometry alone.)
+inline WgradChoice wgrad_choice(const ConvGeom& g) {
+  WgradChoice c{};
+  c.patch = wgrad_patch_ok(g);
+  if (c.patch) { c.bmo = 64; c.cpt = 8; c.nt = 9; }
+  else wgrad_tiles(g, c);
+  wgrad_plan(g, c);
+  return c;
+}
+
+template <int BMO, int CPT, int NT, bool BIAS>
+int launch_wgrad_impl(const WgradArgs& a, int nsplit, hipStream_t st) {
+  constexpr int lds = 2 * (WG_PIX * BMO * 2 + NT * WG_PIX * 128);
+  const int rc = ensure_lds<&conv_wgrad<BMO, CPT, NT, BIAS>>(lds);
+  if (rc != WM_OK) return rc;
+  dim3 grid(a.R * a.S * a.C / 64 / NT, a.K / BMO, nsplit);
+  conv_wgrad<BMO, CPT, NT, BIAS><<<grid, CV_THREADS, lds, st>>>(a);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+template <int BMO, int CPT, int NT>
+int launch_wgrad(const WgradArgs& a, int nsplit, hipStream_t st) {
+  if (a.dbias == nullptr) return launch_wgrad_impl<BMO, CPT, NT, false>(a, nsplit, st);
+  if constexpr (CPT == 8) return launch_wgrad_impl<BMO, CPT, NT, true>(a, nsplit, st);
+  return WM_EUNSUPPORTED;  // no bias gradient on the space-to-depth stem form
+}
+int launch_wgrad_patch(const WgradArgs& a, int nsplit, hipStream_t st) {
+  const int rc = ensure_lds<&conv_wgrad_patch64>(WP_LDS);
+  if (rc != WM_OK) return rc;
+  const int tiles_w = a.W >> 3, tpi = (a.H >> 3) * tiles_w;
+  conv_wgrad_patch64<<<nsplit, CV_THREADS, WP_LDS, st>>>(a, wm_div_make((uint32_t)tpi), wm_div_make((uint32_t)tiles_w));
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+// ---- forward
+int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const ConvGeom& g, float* stat, int stat_nb, int stat_rpg,
+                  void* stream, const float* bias = nullptr, const void* residual = nullptr, void* pre_out = nullptr) {
+  WM_REQUIRE(pre_out == nullptr || (residual == nullptr && g.R == 1 && g.S == 1), WM_EUNSUPPORTED);
   WM_REQUIRE(x && w_krsc && y, WM_EINVAL);
-  const int rc = conv_check(N, H, W, C, K, R, S, P, Q, stride, pad);
+  const int rc = conv_check(g);
   if (rc != WM_OK) return rc;
   WM_REQUIRE(aligned16(x) && aligned16(w_krsc) && aligned16(y), WM_EALIGN);
-  ConvArgs a;
-  a.xcd = xcd_order();
+  ConvArgs a = conv_args(g, false);
   a.src = static_cast<const uint16_t*>(x);
   a.wt = static_cast<const uint16_t*>(w_krsc);
   a.dst = static_cast<uint16_t*>(y);
-  a.N = N; a.SH = H; a.SW = W; a.SC = C; a.DH = P; a.DW = Q; a.DC = K;
-  a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.M = N * P * Q;
-  a.d_dhw = wm_div_make((uint32_t)(P * Q)); a.d_dw = wm_div_make((uint32_t)Q);
-  a.d_h2w2 = wm_div_make(1); a.d_w2 = wm_div_make(1);
   a.stat = stat; a.stat_nb = stat_nb; a.stat_rpg = stat_rpg;
   a.res = static_cast<const uint16_t*>(residual);
   a.bias = bias;
-  a.pre_in = nullptr;
   a.pre_out = static_cast<uint16_t*>(pre_out);
   a.act = pre_out != nullptr ? 1 : 0;
-  a.bn_y = a.bn_x = nullptr;
-  a.bn_mask = nullptr;
-  a.bn_mean = a.bn_invstd = a.bn_gamma = a.bn_beta = nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (C == 16) {
+  const int rpg = stat != nullptr ? stat_rpg : 0;
+  if (g.C == 16) {
     WM_REQUIRE(bias == nullptr && residual == nullptr, WM_EUNSUPPORTED);
-    a.nkt = R;
-    if (stem_patch_ok(a)) {
-      const int npairs = (int)((long long)a.N * (a.DH >> 3) * (a.DW >> 3) / 2);
-      static bool attr = false;
-      if (!attr) {
-        const int rc2 = set_lds(&conv_stem_patch, ST_LDS);
-        if (rc2 != WM_OK) return rc2;
-        attr = true;
-      }
-      const int slots = stem_patch_slots();
-      // one launch per statistics group (whole images, an even number of tiles: stem_patch_ok): a block then flushes
-      // its running sums once, after its last tile pair
-      const int groups = a.stat != nullptr ? a.M / a.stat_rpg : 1;
-      const int n_g = a.N / groups;
-      const int pairs_g = npairs / groups;
-      for (int g = 0; g < groups; ++g) {
-        ConvArgs ag = a;
-        ag.N = n_g;
-        ag.M = n_g * a.DH * a.DW;
-        ag.src = a.src + (size_t)g * n_g * a.SH * a.SW * 16;
-        ag.dst = a.dst + (size_t)g * n_g * a.DH * a.DW * 64;
-        if (a.stat != nullptr) ag.stat = a.stat + (size_t)g * a.stat_nb * 2 * 64;  // (stat_nb = blocks of a launch)
-        conv_stem_patch<<<pairs_g < slots ? pairs_g : slots, CV_THREADS, ST_LDS, st>>>(
-            ag, pairs_g, wm_div_make((uint32_t)((a.DH >> 3) * (a.DW >> 3))), wm_div_make((uint32_t)(a.DW >> 3)));
-        WM_LAUNCH_CHECK();
-      }
-      return WM_OK;
-    }
+    if (stem_patch_ok(g, false, false, rpg)) return launch_stem_patch(a, st);
     // (256-pixel tiles for the 64-channel stem are 7 % faster alone but 10 % slower inside the training
     // step, where the epilogue also accumulates the BatchNorm statistics: 564 vs 509 us)
-    return K % 128 == 0 ? launch_igemm<128, 128, 2, 0>(a, st) : launch_igemm<128, 64, 2, 0>(a, st);
+    return launch_igemm<2, 0>(a, st);
   }
-  a.nkt = R * S * (C / 64);
-  if (R == 1 && S == 1 && stride == 1 && pad == 0 && stat == nullptr && wm_panel_ok(a.M, C, K, residual != nullptr)) {
+  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && stat == nullptr && wm_panel_ok(a.M, g.C, g.K, residual != nullptr)) {
     // Linear with a 192-wide input (ViT-Tiny): token rows resident in registers, weight tiles streamed (panel.hip)
-    WmPanelArgs pa{a.src, a.wt, bias, a.res, nullptr, a.pre_out, a.dst, a.M, K, a.act, 0, nullptr, nullptr, 0.f, 0};
+    WmPanelArgs pa{a.src, a.wt, bias, a.res, nullptr, a.pre_out, a.dst, a.M, g.K, a.act, 0, nullptr, nullptr, 0.f, 0};
     return wm_panel_launch(pa, st);
   }
-  if (residual == nullptr && conv_patch_ok(a)) return launch_patch<0>(a, st);
-  if (bias != nullptr || residual != nullptr || pre_out != nullptr)
-    return K % 128 == 0 ? launch_igemm<128, 128, 8, 0, true>(a, st) : launch_igemm<128, 64, 8, 0, true>(a, st);
-  return K % 128 == 0 ? launch_igemm<128, 128, 8, 0>(a, st) : launch_igemm<128, 64, 8, 0>(a, st);
+  if (residual == nullptr && conv_patch_ok(g, bias != nullptr, rpg)) return launch_patch<0>(a, st);
+  if (bias != nullptr || residual != nullptr || pre_out != nullptr) return launch_igemm<8, 0, true>(a, st);
+  return launch_igemm<8, 0>(a, st);
 }
 
+// ---- input gradient
 struct BnbArgs {  // BatchNorm-backward epilogue (ConvArgs: bn_*)
   const void* bn_y;
   const void* bn_x;
@@ -1814,17 +1746,86 @@ struct BnbArgs {  // BatchNorm-backward epilogue (ConvArgs: bn_*)
   int stat_nb;
 };
 
-static int conv_dgrad_impl(const void* dy, const void* w_crsk, void* dx, const void* residual, int N, int H,
-                           int W, int C, int K, int R, int S, int P, int Q, int stride, int pad, void* stream,
-                           const void* pre_in = nullptr, const BnbArgs* bnb = nullptr);
+int conv_dgrad_impl(const void* dy, const void* w_crsk, void* dx, const void* residual, const ConvGeom& g, void* stream,
+                    const void* pre_in = nullptr, const BnbArgs* bnb = nullptr) {
+  WM_REQUIRE(dy && w_crsk && dx, WM_EINVAL);
+  WM_REQUIRE(pre_in == nullptr || (residual == nullptr && g.R == 1 && g.S == 1 && g.stride == 1 && aligned16(pre_in)), WM_EUNSUPPORTED);
+  const int rc = conv_check(g);
+  if (rc != WM_OK) return rc;
+  WM_REQUIRE(g.C % 64 == 0, WM_EUNSUPPORTED);  // the stem needs no input gradient
+  WM_REQUIRE(aligned16(dy) && aligned16(w_crsk) && aligned16(dx), WM_EALIGN);
+  ConvArgs a = conv_args(g, true);
+  a.src = static_cast<const uint16_t*>(dy);
+  a.wt = static_cast<const uint16_t*>(w_crsk);
+  a.dst = static_cast<uint16_t*>(dx);
+  a.res = static_cast<const uint16_t*>(residual);
+  a.pre_in = static_cast<const uint16_t*>(pre_in);
+  a.act = pre_in != nullptr ? 2 : 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int mode = dgrad_mode(g);
+  if (bnb != nullptr) {  // (mode 3 or 2: wm_conv2d_dgrad_bnstat_ok)
+    WM_REQUIRE(pre_in == nullptr, WM_EUNSUPPORTED);
+    a.bn_y = static_cast<const uint16_t*>(bnb->bn_y);
+    a.bn_x = static_cast<const uint16_t*>(bnb->bn_x);
+    a.bn_mask = static_cast<const uint8_t*>(bnb->bn_mask);
+    a.bn_mean = bnb->mean; a.bn_invstd = bnb->invstd; a.bn_gamma = bnb->gamma; a.bn_beta = bnb->beta;
+    a.stat = bnb->stat; a.stat_nb = bnb->stat_nb;
+    a.stat_rpg = (int)(dgrad_stat_rows(g, mode) / bnb->G);
+    if (mode == 3 && conv_patch_ok(g, false, a.stat_rpg)) return launch_patch<1, true>(a, st);
+    return mode == 3 ? launch_igemm<8, 3, false, true>(a, st) : launch_igemm<8, 2, false, true>(a, st);
+  }
+  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && wm_panel_ok(a.M, g.K, g.C, residual != nullptr || pre_in != nullptr)) {
+    // input gradient of a Linear with 192 OUTPUT features: dx = dy [rows][192] . w_crsk^T, w_crsk [C][192]
+    WmPanelArgs pa{a.src, a.wt, nullptr, a.res, a.pre_in, nullptr, a.dst, a.M, g.C, a.act, 0, nullptr, nullptr, 0.f, 0};
+    return wm_panel_launch(pa, st);
+  }
+  if (pre_in != nullptr) return launch_igemm<8, 3, true>(a, st);  // (stride 1: checked above)
+  if (conv_patch_ok(g, false, 0)) return launch_patch<1>(a, st);
+  if (mode == 3) return launch_igemm<8, 3>(a, st);
+  return mode == 2 ? launch_igemm<8, 2>(a, st) : launch_igemm<8, 1>(a, st);
+}
+
+}  // namespace
+
+extern "C" int wm_conv2d_fwd(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C,
+                             int K, int R, int S, int P, int Q, int stride, int pad, void* stream) {
+  return conv_fwd_impl(x, w_krsc, y, {N, H, W, C, K, R, S, P, Q, stride, pad}, nullptr, 0, 0, stream);
+}
+
+extern "C" int wm_conv2d_fwd_bias_res(const void* x, const void* w_krsc, const float* bias, const void* residual,
+                                      void* y, int N, int H, int W, int C, int K, int R, int S, int P, int Q,
+                                      int stride, int pad, void* stream) {
+  WM_REQUIRE(aligned16(bias) && aligned16(residual), WM_EALIGN);
+  return conv_fwd_impl(x, w_krsc, y, {N, H, W, C, K, R, S, P, Q, stride, pad}, nullptr, 0, 0, stream, bias, residual);
+}
+
+// Statistics slots per group a forward-with-statistics launch of this geometry writes: one per 128-row tile, except
+// the persistent stem kernel (stem_patch_group_slots).
+extern "C" int wm_conv2d_fwd_stats_tiles(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride,
+                                         int pad, int rows_per_group) {
+  const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
+  if (conv_check(g) != WM_OK || rows_per_group <= 0) return WM_EINVAL;
+  if (rows_per_group % 128 != 0 || g.rows_y() % rows_per_group != 0) return WM_EUNSUPPORTED;
+  if (stem_patch_ok(g, false, false, rows_per_group)) return stem_patch_group_slots(rows_per_group / 128);
+  return rows_per_group / 128;
+}
+
+extern "C" int wm_conv2d_fwd_stats(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C,
+                                   int K, int R, int S, int P, int Q, int stride, int pad, float* stat_part,
+                                   int stat_tiles, int rows_per_group, void* stream) {
+  WM_REQUIRE(stat_part && rows_per_group > 0, WM_EINVAL);
+  WM_REQUIRE(rows_per_group % 128 == 0 && ((long long)N * P * Q) % rows_per_group == 0, WM_EUNSUPPORTED);
+  WM_REQUIRE(stat_tiles == wm_conv2d_fwd_stats_tiles(N, H, W, C, K, R, S, P, Q, stride, pad, rows_per_group), WM_EINVAL);
+  return conv_fwd_impl(x, w_krsc, y, {N, H, W, C, K, R, S, P, Q, stride, pad}, stat_part, stat_tiles, rows_per_group, stream);
+}
 
 // Linear + bias + GELU in one launch (ViT MLP fc1): pre = x W^T + bias -> pre_out (bf16, saved for the backward
 // pass), gelu(pre) -> y.
 extern "C" int wm_linear_bias_gelu_fwd(const void* x, const void* w_krsc, const float* bias, void* pre_out, void* y,
                                        int rows, int C, int K, void* stream) {
   WM_REQUIRE(pre_out && bias, WM_EINVAL);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(pre_out) & 15) == 0, WM_EALIGN);
-  return conv_fwd_impl(x, w_krsc, y, rows, 1, 1, C, K, 1, 1, 1, 1, 1, 0, nullptr, 0, 0, stream, bias, nullptr, pre_out);
+  WM_REQUIRE(aligned16(bias) && aligned16(pre_out), WM_EALIGN);
+  return conv_fwd_impl(x, w_krsc, y, {rows, 1, 1, C, K, 1, 1, 1, 1, 1, 0}, nullptr, 0, 0, stream, bias, nullptr, pre_out);
 }
 
 // Input gradient of a Linear whose INPUT was gelu(pre): dx = (dy W) * gelu'(pre)  (ViT MLP fc2 backward): the
@@ -1832,33 +1833,31 @@ extern "C" int wm_linear_bias_gelu_fwd(const void* x, const void* w_krsc, const 
 extern "C" int wm_linear_dgrad_gelu(const void* dy, const void* w_crsk, const void* pre, void* dx, int rows, int C,
                                     int K, void* stream) {
   WM_REQUIRE(pre, WM_EINVAL);
-  return conv_dgrad_impl(dy, w_crsk, dx, nullptr, rows, 1, 1, C, K, 1, 1, 1, 1, 1, 0, stream, pre);
+  return conv_dgrad_impl(dy, w_crsk, dx, nullptr, {rows, 1, 1, C, K, 1, 1, 1, 1, 1, 0}, stream, pre);
 }
 
 extern "C" int wm_conv2d_dgrad(const void* dy, const void* w_crsk, void* dx, int N, int H, int W,
                                int C, int K, int R, int S, int P, int Q, int stride, int pad,
                                void* stream) {
-  return conv_dgrad_impl(dy, w_crsk, dx, nullptr, N, H, W, C, K, R, S, P, Q, stride, pad, stream);
+  return conv_dgrad_impl(dy, w_crsk, dx, nullptr, {N, H, W, C, K, R, S, P, Q, stride, pad}, stream);
 }
 
 extern "C" int wm_conv2d_dgrad_add(const void* dy, const void* w_crsk, const void* residual, void* dx, int N,
                                    int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad,
                                    void* stream) {
   WM_REQUIRE(residual, WM_EINVAL);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(residual) & 15) == 0, WM_EALIGN);
-  return conv_dgrad_impl(dy, w_crsk, dx, residual, N, H, W, C, K, R, S, P, Q, stride, pad, stream);
+  WM_REQUIRE(aligned16(residual), WM_EALIGN);
+  return conv_dgrad_impl(dy, w_crsk, dx, residual, {N, H, W, C, K, R, S, P, Q, stride, pad}, stream);
 }
 
-// Can the BatchNorm-backward epilogue serve this dgrad?  Every 128-row tile must lie inside one statistics group
-// (stride 2: inside one group of one parity class) and the kernel must be one of the BNB instantiations.
+// Can the BatchNorm-backward epilogue serve this dgrad?  The kernel must be one of the BNB instantiations (MODE 3 or
+// 2) and every 128-row tile must lie inside one statistics group (MODE 2: inside one group of one parity class).
 extern "C" int wm_conv2d_dgrad_bnstat_ok(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride,
                                          int pad, int G) {
-  if (conv_check(N, H, W, C, K, R, S, P, Q, stride, pad) != WM_OK || C % 64 != 0 || G <= 0 || N % G != 0) return 0;
-  const long long rows = (long long)N * H * W;
-  if (stride == 1) return (rows / G) % 128 == 0 ? 1 : 0;
-  if (H % 2 || W % 2) return 0;
-  const long long cls = (long long)N * (H / 2) * (W / 2);
-  return (cls % 128 == 0 && (cls / G) % 128 == 0) ? 1 : 0;
+  const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
+  if (conv_check(g) != WM_OK || C % 64 != 0 || G <= 0 || N % G != 0) return 0;
+  const int mode = dgrad_mode(g);
+  return mode != 1 && (dgrad_stat_rows(g, mode) / G) % 128 == 0 ? 1 : 0;
 }
 
 extern "C" int wm_conv2d_dgrad_bnstat(const void* dy, const void* w_crsk, const void* residual, void* dx, int N, int H,
@@ -1871,79 +1870,13 @@ extern "C" int wm_conv2d_dgrad_bnstat(const void* dy, const void* w_crsk, const 
   WM_REQUIRE(relu_x || relu_mask || (gamma && beta), WM_EINVAL);
   WM_REQUIRE(!(relu_x && relu_mask), WM_EINVAL);
   WM_REQUIRE(wm_conv2d_dgrad_bnstat_ok(N, H, W, C, K, R, S, P, Q, stride, pad, G), WM_EUNSUPPORTED);
-  WM_REQUIRE(aligned16(bn_y) && aligned16(save_mean) && aligned16(save_invstd) && (relu_x == nullptr || aligned16(relu_x)) &&
-                 (residual == nullptr || aligned16(residual)),
+  WM_REQUIRE(aligned16(bn_y) && aligned16(save_mean) && aligned16(save_invstd) && aligned16(relu_x) && aligned16(residual),
              WM_EALIGN);
   BnbArgs b{bn_y, relu_x, relu_mask, save_mean, save_invstd, gamma, beta, G, stat_part, stat_tiles};
-  return conv_dgrad_impl(dy, w_crsk, dx, residual, N, H, W, C, K, R, S, P, Q, stride, pad, stream, nullptr, &b);
+  return conv_dgrad_impl(dy, w_crsk, dx, residual, {N, H, W, C, K, R, S, P, Q, stride, pad}, stream, nullptr, &b);
 }
 
-static int conv_dgrad_impl(const void* dy, const void* w_crsk, void* dx, const void* residual, int N, int H,
-                           int W, int C, int K, int R, int S, int P, int Q, int stride, int pad, void* stream,
-                           const void* pre_in, const BnbArgs* bnb) {
-  WM_REQUIRE(dy && w_crsk && dx, WM_EINVAL);
-  WM_REQUIRE(pre_in == nullptr || (residual == nullptr && R == 1 && S == 1 && stride == 1 && aligned16(pre_in)), WM_EUNSUPPORTED);
-  const int rc = conv_check(N, H, W, C, K, R, S, P, Q, stride, pad);
-  if (rc != WM_OK) return rc;
-  WM_REQUIRE(C % 64 == 0, WM_EUNSUPPORTED);  // the stem needs no input gradient
-  WM_REQUIRE(aligned16(dy) && aligned16(w_crsk) && aligned16(dx), WM_EALIGN);
-  ConvArgs a;
-  a.xcd = xcd_order();
-  a.src = static_cast<const uint16_t*>(dy);
-  a.wt = static_cast<const uint16_t*>(w_crsk);
-  a.dst = static_cast<uint16_t*>(dx);
-  a.N = N; a.SH = P; a.SW = Q; a.SC = K; a.DH = H; a.DW = W; a.DC = C;
-  a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.M = N * H * W;
-  a.d_dhw = wm_div_make((uint32_t)(H * W)); a.d_dw = wm_div_make((uint32_t)W);
-  a.d_h2w2 = wm_div_make((uint32_t)((H >> 1) * (W >> 1) > 0 ? (H >> 1) * (W >> 1) : 1));
-  a.d_w2 = wm_div_make((uint32_t)((W >> 1) > 0 ? (W >> 1) : 1));
-  a.stat = nullptr; a.stat_nb = 0; a.stat_rpg = 1;
-  a.res = static_cast<const uint16_t*>(residual);
-  a.nkt = R * S * (K / 64);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  a.bias = nullptr;
-  a.pre_in = static_cast<const uint16_t*>(pre_in);
-  a.pre_out = nullptr;
-  a.act = pre_in != nullptr ? 2 : 0;
-  a.bn_y = a.bn_x = nullptr;
-  a.bn_mask = nullptr;
-  a.bn_mean = a.bn_invstd = a.bn_gamma = a.bn_beta = nullptr;
-  if (bnb != nullptr) {
-    WM_REQUIRE(pre_in == nullptr, WM_EUNSUPPORTED);
-    a.bn_y = static_cast<const uint16_t*>(bnb->bn_y);
-    a.bn_x = static_cast<const uint16_t*>(bnb->bn_x);
-    a.bn_mask = static_cast<const uint8_t*>(bnb->bn_mask);
-    a.bn_mean = bnb->mean; a.bn_invstd = bnb->invstd; a.bn_gamma = bnb->gamma; a.bn_beta = bnb->beta;
-    a.stat = bnb->stat; a.stat_nb = bnb->stat_nb;
-    if (stride == 1) {
-      a.stat_rpg = (int)((long long)N * H * W / bnb->G);
-      if (conv_patch_ok(a)) return launch_patch<1, true>(a, st);
-      return C % 128 == 0 ? launch_igemm<128, 128, 8, 3, false, true>(a, st) : launch_igemm<128, 64, 8, 3, false, true>(a, st);
-    }
-    a.stat_rpg = (int)((long long)N * (H / 2) * (W / 2) / bnb->G);
-    return C % 128 == 0 ? launch_igemm<128, 128, 8, 2, false, true>(a, st) : launch_igemm<128, 64, 8, 2, false, true>(a, st);
-  }
-  if (R == 1 && S == 1 && stride == 1 && pad == 0 && bnb == nullptr &&
-      wm_panel_ok(a.M, K, C, residual != nullptr || pre_in != nullptr)) {
-    // input gradient of a Linear with 192 OUTPUT features: dx = dy [rows][192] . w_crsk^T, w_crsk [C][192]
-    WmPanelArgs pa{a.src, a.wt, nullptr, a.res, a.pre_in, nullptr, a.dst, a.M, C, a.act, 0, nullptr, nullptr, 0.f, 0};
-    return wm_panel_launch(pa, st);
-  }
-  if (pre_in != nullptr)
-    return C % 128 == 0 ? launch_igemm<128, 128, 8, 3, true>(a, st) : launch_igemm<128, 64, 8, 3, true>(a, st);
-  if (conv_patch_ok(a)) return launch_patch<1>(a, st);
-  // stride 2 with even image sides and class size % 128 == 0: parity-class ordering (no wasted taps)
-  const long long cls = (long long)N * (H / 2) * (W / 2);
-  if (stride == 2 && H % 2 == 0 && W % 2 == 0) {
-    if (C % 128 == 0 && cls % 128 == 0) return launch_igemm<128, 128, 8, 2>(a, st);
-    if (C % 128 != 0 && cls % 128 == 0) return launch_igemm<128, 64, 8, 2>(a, st);
-  }
-  // stride 1: MODE 3 = MODE 1 without the stride-2 address path in the k-loop's issue phase (hipcc
-  // if-converts the run-time branch: its 64-bit address arithmetic was executed on every k-step)
-  if (stride == 1) return C % 128 == 0 ? launch_igemm<128, 128, 8, 3>(a, st) : launch_igemm<128, 64, 8, 3>(a, st);
-  return C % 128 == 0 ? launch_igemm<128, 128, 8, 1>(a, st) : launch_igemm<128, 64, 8, 1>(a, st);
-}
-
+// ---- weight gradient
 extern "C" int wm_conv2d_wgrad(const void* dy, const void* x, float* dw_krsc, int N, int H, int W,
                                int C, int K, int R, int S, int P, int Q, int stride, int pad,
                                void* stream) {
@@ -1954,12 +1887,17 @@ extern "C" int wm_conv2d_wgrad_bias(const void* dy, const void* x, float* dw_krs
                                     int W, int C, int K, int R, int S, int P, int Q, int stride, int pad,
                                     void* stream) {
   WM_REQUIRE(dy && x && dw_krsc, WM_EINVAL);
-  const int rc = conv_check(N, H, W, C, K, R, S, P, Q, stride, pad);
+  const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
+  const int rc = conv_check(g);
   if (rc != WM_OK) return rc;
   WM_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(dw_krsc), WM_EALIGN);
   // the kernel forms element offsets in 32 bits
-  WM_REQUIRE((long long)N * H * W * C < (1ll << 32) - (1 << 20) && (long long)N * P * Q * K < (1ll << 32) - (1 << 20),
-             WM_EUNSUPPORTED);
+  WM_REQUIRE(g.rows_x() * C < (1ll << 32) - (1 << 20) && g.rows_y() * K < (1ll << 32) - (1 << 20), WM_EUNSUPPORTED);
+  const WgradChoice c = wgrad_choice(g);
+  // wm_conv2d_wgrad_splits answers for the launch WITHOUT a bias gradient; a shape whose plan would differ with one
+  // (the patch-resident 64 -> 64 3x3 form has no bias path) is refused instead of leaving slabs of the caller's
+  // buffer unwritten.  Only Linear layers (1x1) ask for a bias gradient.
+  WM_REQUIRE(!(dbias != nullptr && c.patch), WM_EUNSUPPORTED);
   WgradArgs a;
   a.xcd = xcd_order();
   a.dy = static_cast<const uint16_t*>(dy);
@@ -1968,40 +1906,24 @@ extern "C" int wm_conv2d_wgrad_bias(const void* dy, const void* x, float* dw_krs
   a.dbias = dbias;
   a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.P = P; a.Q = Q;
   a.stride = stride; a.pad = pad; a.M = N * P * Q;
-  a.chunks_per_split = 0; a.total_chunks = 0;
+  a.chunks_per_split = c.chunks_per_split; a.total_chunks = c.total_chunks;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dbias != nullptr) {
-    // wm_conv2d_wgrad_splits answers for the launch WITHOUT a bias gradient; a shape whose plan would differ with one
-    // (the patch-resident 64 -> 64 3x3 form has no bias path) is refused instead of leaving slabs of the caller's
-    // buffer unwritten.  Only Linear layers (1x1) ask for a bias gradient.
-    WgradArgs q = a;
-    q.dbias = nullptr;
-    WM_REQUIRE(!wgrad_patch_ok(q), WM_EUNSUPPORTED);
+  if (c.patch) return launch_wgrad_patch(a, c.nsplit, st);
+  if (c.cpt == 2) {
+    if (c.bmo == 128) return c.nt == 2 ? launch_wgrad<128, 2, 2>(a, c.nsplit, st) : launch_wgrad<128, 2, 1>(a, c.nsplit, st);
+    return c.nt == 4 ? launch_wgrad<64, 2, 4>(a, c.nsplit, st) : launch_wgrad<64, 2, 1>(a, c.nsplit, st);
   }
-  if (wgrad_patch_ok(a)) return launch_wgrad_patch(a, st);
-  int bmo, cpt, nt;
-  wgrad_config(C, K, R, S, bmo, cpt, nt);
-  if (cpt == 2) {
-    if (bmo == 128) return nt == 2 ? launch_wgrad<128, 2, 2>(a, st) : launch_wgrad<128, 2, 1>(a, st);
-    return nt == 4 ? launch_wgrad<64, 2, 4>(a, st) : launch_wgrad<64, 2, 1>(a, st);
+  if (c.bmo == 128) {
+    if (c.nt == 3) return launch_wgrad<128, 8, 3>(a, c.nsplit, st);
+    if (c.nt == 2) return launch_wgrad<128, 8, 2>(a, c.nsplit, st);
+    return launch_wgrad<128, 8, 1>(a, c.nsplit, st);
   }
-  if (bmo == 128) {
-    if (nt == 3) return launch_wgrad<128, 8, 3>(a, st);
-    if (nt == 2) return launch_wgrad<128, 8, 2>(a, st);
-    return launch_wgrad<128, 8, 1>(a, st);
-  }
-  return nt == 3 ? launch_wgrad<64, 8, 3>(a, st) : launch_wgrad<64, 8, 1>(a, st);
+  return c.nt == 3 ? launch_wgrad<64, 8, 3>(a, c.nsplit, st) : launch_wgrad<64, 8, 1>(a, c.nsplit, st);
 }
 
 extern "C" int wm_conv2d_wgrad_splits(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad) {
-  const int rc = conv_check(N, H, W, C, K, R, S, P, Q, stride, pad);
+  const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
+  const int rc = conv_check(g);
   if (rc != WM_OK) return rc;
-  WgradArgs a{};
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.P = P; a.Q = Q;
-  a.stride = stride; a.pad = pad; a.dbias = nullptr;
-  int bmo, cpt, nt, nsplit, cps, tc;
-  wgrad_config(C, K, R, S, bmo, cpt, nt);
-  if (wgrad_patch_ok(a)) { bmo = 64; nt = 9; }  // (a bias gradient is only asked of Linear layers: never this shape)
-  wgrad_plan(a, bmo, nt, nsplit, cps, tc);
-  return nsplit;
+  return wgrad_choice(g).nsplit;
 }
