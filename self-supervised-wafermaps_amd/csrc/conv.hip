@@ -1727,7 +1727,7 @@ int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const ConvGeom& g,
   }
   if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && stat == nullptr && wm_panel_ok(a.M, g.C, g.K, residual != nullptr)) {
     // Linear with a 192-wide input (ViT-Tiny): token rows resident in registers, weight tiles streamed (panel.hip)
-    WmPanelArgs pa{a.src, a.wt, bias, a.res, nullptr, a.pre_out, a.dst, a.M, g.K, a.act, 0, nullptr, nullptr, 0.f, 0};
+    WmPanelArgs pa{a.src, a.wt, bias, a.res, nullptr, a.pre_out, a.dst, a.M, g.K, a.act, 0, nullptr, nullptr, 0.f};
     return wm_panel_launch(pa, st);
   }
   if (residual == nullptr && conv_patch_ok(g, bias != nullptr, rpg)) return launch_patch<0>(a, st);
@@ -1776,7 +1776,7 @@ int conv_dgrad_impl(const void* dy, const void* w_crsk, void* dx, const void* re
   }
   if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && wm_panel_ok(a.M, g.K, g.C, residual != nullptr || pre_in != nullptr)) {
     // input gradient of a Linear with 192 OUTPUT features: dx = dy [rows][192] . w_crsk^T, w_crsk [C][192]
-    WmPanelArgs pa{a.src, a.wt, nullptr, a.res, a.pre_in, nullptr, a.dst, a.M, g.C, a.act, 0, nullptr, nullptr, 0.f, 0};
+    WmPanelArgs pa{a.src, a.wt, nullptr, a.res, a.pre_in, nullptr, a.dst, a.M, g.C, a.act, 0, nullptr, nullptr, 0.f};
     return wm_panel_launch(pa, st);
   }
   if (pre_in != nullptr) return launch_igemm<8, 3, true>(a, st);  // (stride 1: checked above)

@@ -156,6 +156,47 @@ __device__ __forceinline__ int acc_row(int reg, int half) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * half;
 }
 
+// ---- pieces the two streaming kernels share; operands are taken the way the kernels form them.  (The list
+// initialisation, the group offer and the query-tile staging stay spelled out in both kernels: as helpers each of them
+// changed the kernels' code, profiles/knn_refactor.md section 1.)
+
+// Fold the 16 values an accumulator tile gives this lane into the running group maxima.  nb = first bank row of the
+// wave's 32-row sub-tile; the test is wave-uniform, and only the bank's last chunk masks rows past the end.
+template <int QT>
+__device__ __forceinline__ void fold_group_max(const f32x16_t (&acc)[QT], float (&gmax)[QT], int nb, int n, int h) {
+  if (nb + 32 <= n) {
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      float m = gmax[t];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) m = fmaxf(m, acc[t][e]);
+      gmax[t] = m;
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      float m = gmax[t];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) m = fmaxf(m, (nb + acc_row(e, h) < n) ? acc[t][e] : -INFINITY);
+      gmax[t] = m;
+    }
+  }
+}
+
+// The oldest stage of an S-stage ring has landed: while the ring is still being refilled (`more`), the S-2 younger
+// stages (8 DMA instructions each) may stay in flight.
+template <int S>
+__device__ __forceinline__ void wait_stage(bool more) {
+  static_assert(S >= 2 && S <= 4, "ring depths that are instantiated");
+  if (more) {
+    if constexpr (S == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else if constexpr (S == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
+
 // 256 zero bytes: the global_load_lds source of bank rows past the end
 __device__ __attribute__((aligned(256))) uint8_t knn_zero_page[256];
 
@@ -167,10 +208,8 @@ __device__ __attribute__((aligned(256))) uint8_t knn_zero_page[256];
 template <int DT, int QT, int K, int S>
 __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
     const uint8_t* __restrict__ query, const uint8_t* __restrict__ bank, int nq, int n,
-    int rowbytes, int chunks_per_slice, int nslices, float* __restrict__ part_sim,
-    int* __restrict__ part_idx) {
+    int rowbytes, int nslices, float* __restrict__ part_sim, int* __restrict__ part_idx) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int dbg = chunks_per_slice >> 24;  // timing-only ablation bits (WM_KNN_DEBUG); 0 in production
   constexpr int QB = QT * 32;
   constexpr int PER_STAGE = 8;  // global_load_lds instructions per thread per stage
   const int tid = threadIdx.x;
@@ -191,7 +230,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
   const int total_chunks = (n + KNN_ROWS - 1) / KNN_ROWS;
   const int my_chunks = slice < total_chunks ? (total_chunks - slice + nslices - 1) / nslices : 0;
   const int iters = my_chunks * nslab;
-  (void)chunks_per_slice;
 
   // lane geometry of one DMA instruction: 4 rows x 16 chunks.  A thread's 8 source addresses
   // advance by a constant stride from one of its chunks to the next, so they are kept as running
@@ -206,12 +244,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
     soff[i] = (dpc ^ (row & 15)) * 16;  // logical chunk that lands at physical slot dpc
     srcp[i] = bank + ((size_t)slice * KNN_ROWS + row) * rowbytes + soff[i];
   }
-  // issue() is called for it = 0, 1, 2, ... in order: (chunk, slab) advance by a carry instead of a division,
+  // issue() is called once per ring step, in order: (chunk, slab) advance by a carry instead of a division,
   // the ring slot by a wrap-around counter; LDS addresses are plain integers (no pointer cast per piece)
-  int issued = 0, it_slab = 0, it_chunk = slice, it_slot = 0;
+  int it_slab = 0, it_chunk = slice, it_slot = 0;
   const uint32_t ring_base = lds_addr(ring);
-  auto issue = [&](int it) {
-    (void)it;
+  auto issue = [&]() {
     const int slab = it_slab;
     const int nb = it_chunk * KNN_ROWS;
     const bool tail = nb + KNN_ROWS > n;  // block-uniform
@@ -230,14 +267,12 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
       for (int i = 0; i < PER_STAGE; ++i) srcp[i] += chunk_stride_bytes;
     }
     if (++it_slot == S) it_slot = 0;
-    ++issued;
   };
-  (void)issued;
 
   // prologue: S-1 stages in flight, then the query tile (plain loads; drained before the loop)
 #pragma unroll
   for (int p = 0; p < S - 1; ++p)
-    if (p < iters && !(dbg & 2)) issue(p);
+    if (p < iters) issue();
   {
     const int ppr = rowbytes >> 4;
     const int total = QB * ppr;
@@ -269,21 +304,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
 
   for (int it = 0; it < iters; ++it) {
     // stage `it` must have landed: in steady state S-2 younger stages may still be in flight
-    if (it + S - 1 < iters) {
-      if constexpr (S == 5) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-      else if constexpr (S == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if constexpr (S == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    wait_stage<S>(it + S - 1 < iters);
     // No barrier: a wave DMA-fetches exactly the rows it consumes, so its own counted vmcnt orders the
     // data for its own ds_reads, and lgkmcnt(0) retires last iteration's fragment reads before the
     // DMA below may overwrite that stage.  The four waves of a block (and all blocks) drift apart,
     // which spreads the HBM requests instead of issuing them in block-wide bursts.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (it + S - 1 < iters && !(dbg & 2)) issue(it + S - 1);  // reuses the stage consumed in iteration it-1
-    if (dbg & 1) continue;
+    if (it + S - 1 < iters) issue();  // reuses the stage consumed in iteration it-1
     const int slab = it % nslab;
     if (slab == 0) {
 #pragma unroll
@@ -317,23 +344,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
     if (slab == nslab - 1) {
       const int crel = it / nslab;  // chunk index inside this slice
       const int nb = (slice + crel * nslices) * KNN_ROWS + wave * 32;
-      if (nb + 32 <= n) {  // wave-uniform: every row of this wave's sub-tile is a real bank row
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          float m = gmax[t];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) m = fmaxf(m, acc[t][e]);
-          gmax[t] = m;
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          float m = gmax[t];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) m = fmaxf(m, (nb + acc_row(e, h) < n) ? acc[t][e] : -INFINITY);
-          gmax[t] = m;
-        }
-      }
+      fold_group_max<QT>(acc, gmax, nb, n, h);
       if ((crel & 3) == 3 || it == iters - 1) {  // group of 4 chunks complete (or slice ends)
         const int gid = ((slice + (crel & ~3) * nslices) << 3) | (wave << 1) | h;
 #pragma unroll
@@ -357,24 +368,24 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
 // destination together by 1 KiB per instruction.  The ring slot is a compile-time constant (loop
 // unrolled by S), so ds_read addresses are loop-invariant registers + immediates and the query
 // fragments stay in registers.
-#define KNN_GLDS8(POLICY)                                                                              \
+#define KNN_GLDS8()                                                                                    \
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\t"                                                       \
-               "global_load_lds_dwordx4 %1, %5 offset:-4096" POLICY "\n\t"                             \
-               "global_load_lds_dwordx4 %2, %5 offset:-3072" POLICY "\n\t"                             \
-               "global_load_lds_dwordx4 %3, %5 offset:-2048" POLICY "\n\t"                             \
-               "global_load_lds_dwordx4 %4, %5 offset:-1024" POLICY "\n\t"                             \
-               "global_load_lds_dwordx4 %1, %5" POLICY "\n\t"                                          \
-               "global_load_lds_dwordx4 %2, %5 offset:1024" POLICY "\n\t"                              \
-               "global_load_lds_dwordx4 %3, %5 offset:2048" POLICY "\n\t"                              \
-               "global_load_lds_dwordx4 %4, %5 offset:3072" POLICY                                     \
+               "global_load_lds_dwordx4 %1, %5 offset:-4096 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %2, %5 offset:-3072 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %3, %5 offset:-2048 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %4, %5 offset:-1024 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %1, %5 nt\n\t"                                                 \
+               "global_load_lds_dwordx4 %2, %5 offset:1024 nt\n\t"                                     \
+               "global_load_lds_dwordx4 %3, %5 offset:2048 nt\n\t"                                     \
+               "global_load_lds_dwordx4 %4, %5 offset:3072 nt"                                         \
                :                                                                                       \
                : "s"(m0v), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(sbase)          \
                : "memory", "m0")
 
-template <int QT, int K, int S, bool NT>
+template <int QT, int K, int S>
 __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
     const uint8_t* __restrict__ query, const uint8_t* __restrict__ bank, int nq, int n, int nslices,
-    int dbg, float* __restrict__ part_sim, int* __restrict__ part_idx) {
+    float* __restrict__ part_sim, int* __restrict__ part_idx) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int QB = QT * 32;
   constexpr int RB = KNN_SLAB;  // bytes per row
@@ -385,9 +396,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
   const int q0 = blockIdx.y * QB;
   const int slice = blockIdx.x;
   uint8_t* qbuf = smem + (S - 1) * KNN_BUF;  // query tile staged inside the last ring stage
-  // WM_KNN_DEBUG bit 2: 100 MHz timestamps of the block's phases over query q0's partial similarities (timing only)
-  unsigned long long stamp[4];
-  stamp[0] = __builtin_amdgcn_s_memrealtime();
 
   const int total_chunks = (n + KNN_ROWS - 1) / KNN_ROWS;
   const int iters = slice < total_chunks ? (total_chunks - slice + nslices - 1) / nslices : 0;
@@ -412,12 +420,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
         int row = nb + wave * 32 + i * 4 + drow;
         row = row < n ? row : n - 1;
         const uint8_t* src = bank + (size_t)row * RB + ((dpc ^ ((4 * i + drow) & 15)) << 4);
-        if constexpr (NT) glds16_nt_at(src, m0v - 4096 + i * 1024);
-        else glds16_at(src, m0v - 4096 + i * 1024);
+        glds16_nt_at(src, m0v - 4096 + i * 1024);
       }
     } else {
-      if constexpr (NT) KNN_GLDS8(" nt");
-      else KNN_GLDS8("");
+      KNN_GLDS8();
     }
     it_chunk += nslices;
     sbase += chunk_stride_bytes;
@@ -425,7 +431,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
 
 #pragma unroll
   for (int p = 0; p < S - 1; ++p)
-    if (p < iters && !(dbg & 2)) issue(p);
+    if (p < iters) issue(p);
   for (int p = tid; p < QB * 16; p += KNN_THREADS) {
     const int row = p >> 4, c = p & 15;
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -461,7 +467,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
       qreg[t][s8] = *reinterpret_cast<const uint4*>(qbuf + (t * 32 + r) * RB + (((2 * s8 + h) ^ (r & 15)) << 4));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();  // every wave has its fragments: the stage may now be overwritten
-  stamp[1] = __builtin_amdgcn_s_memrealtime();
 
   for (int it0 = 0; it0 < iters; it0 += S) {
 #pragma unroll
@@ -469,17 +474,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
       const int it = it0 + st;
       if (it >= iters) break;
       const bool more = it + S - 1 < iters;
-      if (more) {
-        if constexpr (S == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if constexpr (S == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      wait_stage<S>(more);
       // no barrier: a wave fetches exactly the rows it multiplies (see knn_stream)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (more && !(dbg & 2)) issue((st + S - 1) % S);
-      if (dbg & 1) continue;
+      if (more) issue((st + S - 1) % S);
       uint4 a[8];
 #pragma unroll
       for (int s8 = 0; s8 < 8; ++s8) a[s8] = *reinterpret_cast<const uint4*>(smem + st * KNN_BUF + aoff[s8]);
@@ -495,23 +493,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
         }
       }
       const int nb = (slice + it * nslices) * KNN_ROWS + wave * 32;
-      if (nb + 32 <= n) {  // wave-uniform: all 32 rows of this wave's sub-tile exist
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          float m = gmax[t];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) m = fmaxf(m, acc[t][e]);
-          gmax[t] = m;
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          float m = gmax[t];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) m = fmaxf(m, (nb + acc_row(e, h) < n) ? acc[t][e] : -INFINITY);
-          gmax[t] = m;
-        }
-      }
+      fold_group_max<QT>(acc, gmax, nb, n, h);
       if ((it & 3) == 3 || it == iters - 1) {  // group of 4 chunks complete (or slice ends)
         const int gid = ((slice + (it & ~3) * nslices) << 3) | (wave << 1) | h;
 #pragma unroll
@@ -522,15 +504,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
       }
     }
   }
-  stamp[2] = __builtin_amdgcn_s_memrealtime();
   __syncthreads();  // ring is free: reuse it for the cross-wave merge
   block_merge_store<QT, K>(lv, li, smem, tid, q0, nslices, slice, part_sim, part_idx);
-  if ((dbg & 4) && tid == 0) {
-    stamp[3] = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(part_sim + ((size_t)q0 * nslices + slice) * K);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = stamp[j];
-  }
 }
 
 // One wave per query: merge `parts` sorted lists of `kin` candidates into the best `kout`.
@@ -669,10 +644,6 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
   const int q = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
   const size_t qbase = (size_t)q * nslices * K;
-  unsigned long long stamp[6];  // WM_KNN_DEBUG bit 2 (kout < 0): phase timestamps, see tools/knn_stamps.py
-  const bool stamps = kout < 0;
-  if (stamps) kout = -kout;
-  stamp[0] = __builtin_amdgcn_s_memrealtime();
 
   for (int c = tid; c < d; c += TH) {
     if constexpr (DT == WM_BF16) qf[c] = bf2f(reinterpret_cast<const uint16_t*>(query + (size_t)q * rowbytes)[c]);
@@ -696,7 +667,6 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
     }
   }
   __syncthreads();
-  stamp[1] = __builtin_amdgcn_s_memrealtime();
   // 2. wave 0: the K runs that can hold the K best groups, then (K = 8) the K best of their K x K entries
   if (wv == 0) {
     constexpr int P2 = (NW * K + 63) / 64;  // wave winners per lane
@@ -758,7 +728,6 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
     }
     __syncthreads();
   }
-  stamp[2] = __builtin_amdgcn_s_memrealtime();
 
   // ---- exact rescoring: 4 lanes per row, 64 rows per pass; a lane's pieces are sub, sub+4, ...
   // All loads of PASSES passes are issued before any arithmetic (the work is pure latency).
@@ -834,7 +803,6 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
     }
   }
   __syncthreads();
-  stamp[3] = __builtin_amdgcn_s_memrealtime();
   if (tid < 64) {
     // one wave: every lane keeps its K candidates as 64-bit keys in registers (0 = none); bank rows are distinct,
     // so the key identifies the winner of a round
@@ -862,11 +830,6 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
         }
       }
     }
-  }
-  if (stamps && tid == 0) {
-    stamp[4] = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(const_cast<float*>(part_sim) + qbase);
-    for (int j = 0; j < 5; ++j) o[j] = stamp[j];
   }
 }
 
@@ -911,7 +874,7 @@ inline int pick_qt(int rowbytes, int nq, int kt) {
 }
 
 struct KnnPlan {
-  int qt, qtiles, nslices, chunks_per_slice, kt;
+  int qt, qtiles, nslices, kt;
 };
 
 inline KnnPlan make_plan(int nq, int n, int rowbytes, int k) {
@@ -923,70 +886,53 @@ inline KnnPlan make_plan(int nq, int n, int rowbytes, int k) {
   int want = (p.qt == 4 ? 256 : 512) / p.qtiles;  // resident blocks per CU: 1 (128-query tiles) or 2
   if (want < 1) want = 1;
   if (want > 512) want = 512;
-  static const int forced = [] {  // experiment knob, read once
-    const char* e = getenv("WM_KNN_SLICES");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0) want = forced;
   p.nslices = total_chunks < want ? total_chunks : want;
-  p.chunks_per_slice = wm_cdiv(total_chunks, p.nslices);
-  p.nslices = wm_cdiv(total_chunks, p.chunks_per_slice);
+  const int chunks_per_slice = wm_cdiv(total_chunks, p.nslices);
+  p.nslices = wm_cdiv(total_chunks, chunks_per_slice);
   return p;
 }
 
-inline int knn_debug_bits() {
-  static int bits = -1;
-  if (bits < 0) {
-    const char* e = getenv("WM_KNN_DEBUG");
-    bits = e ? atoi(e) & 7 : 0;
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The streaming kernels use up to 160 KB of dynamic LDS: raise the kernel's limit once (idempotent; a race only
+// repeats the call).
+template <auto Kernel>
+int ensure_lds() {
+  static bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    if (e != hipSuccess) return (int)e;
+    done = true;
   }
-  return bits;
+  return WM_OK;
 }
 
 template <int DT, int QT, int K, int S>
 int launch_stream(const KnnPlan& p, const void* query, const void* bank, int nq, int n, int rowbytes,
                   float* ps, int* pi, hipStream_t st) {
   const size_t lds = (size_t)S * KNN_BUF + (size_t)QT * 32 * rowbytes;
-  static bool attr_set = false;  // idempotent; a race only repeats the call
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_stream<DT, QT, K, S>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  const int rc = ensure_lds<&knn_stream<DT, QT, K, S>>();
+  if (rc != WM_OK) return rc;
   dim3 grid(p.nslices, p.qtiles);
   knn_stream<DT, QT, K, S><<<grid, KNN_THREADS, lds, st>>>(
-      static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank), nq, n, rowbytes,
-      p.chunks_per_slice | (knn_debug_bits() << 24), p.nslices, ps, pi);
+      static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank), nq, n, rowbytes, p.nslices,
+      ps, pi);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-template <int QT, int K, int S, bool NT>
+template <int QT, int K, int S>
 int launch_stream_b128(const KnnPlan& p, const void* query, const void* bank, int nq, int n, float* ps, int* pi,
                        hipStream_t st) {
   const size_t lds = (size_t)S * KNN_BUF;
-  static bool attr_set = false;  // idempotent; a race only repeats the call
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_stream_b128<QT, K, S, NT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  const int rc = ensure_lds<&knn_stream_b128<QT, K, S>>();
+  if (rc != WM_OK) return rc;
   dim3 grid(p.nslices, p.qtiles);
-  knn_stream_b128<QT, K, S, NT><<<grid, KNN_THREADS, lds, st>>>(
-      static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank), nq, n, p.nslices, knn_debug_bits(), ps, pi);
+  knn_stream_b128<QT, K, S><<<grid, KNN_THREADS, lds, st>>>(
+      static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank), nq, n, p.nslices, ps, pi);
   WM_LAUNCH_CHECK();
   return WM_OK;
-}
-
-inline bool knn_nt() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("WM_KNN_NT");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
 }
 
 // Instantiations are kept few (each is a large, fully unrolled kernel): query tiles of 64 or 128
@@ -999,13 +945,7 @@ int launch_block(const KnnPlan& p, const void* query, const void* bank, int nq, 
     // 64-query tiles: 2-stage ring, two blocks per CU (2 waves/SIMD overlap issue and waits);
     // 128-query tiles need ~400 registers per lane, i.e. one block per CU: 4-stage ring instead
     if (rowbytes == KNN_SLAB) {
-      if constexpr (QT == 4) {
-        return knn_nt() ? launch_stream_b128<QT, K, 4, true>(p, query, bank, nq, n, ps, pi, st)
-                        : launch_stream_b128<QT, K, 4, false>(p, query, bank, nq, n, ps, pi, st);
-      } else {
-        return knn_nt() ? launch_stream_b128<QT, K, 2, true>(p, query, bank, nq, n, ps, pi, st)
-                        : launch_stream_b128<QT, K, 2, false>(p, query, bank, nq, n, ps, pi, st);
-      }
+      return launch_stream_b128<QT, K, QT == 4 ? 4 : 2>(p, query, bank, nq, n, ps, pi, st);
     }
   }
   return launch_stream<DT, QT, K, 3>(p, query, bank, nq, n, rowbytes, ps, pi, st);
@@ -1031,7 +971,6 @@ int launch_select(const KnnPlan& p, const void* query, const void* bank, int n, 
   if (p.nslices > 512) return WM_EUNSUPPORTED;  // two runs per lane of the selection block
   // wave winners (up to 16 waves), selected runs / groups, rescored candidates, the query
   const size_t lds = (16 * K * 8 + K * 4 + (size_t)K * 64 * 8 + (size_t)d * 4 + 15) & ~(size_t)15;
-  const int kk = (knn_debug_bits() & 4) ? -kout : kout;
   if constexpr (K == 8) {
     // 1024 threads: the 512 candidate rows are rescored in ONE round of dependent loads instead of four
     // (WM_KNN_SELECT_THREADS=256 keeps the lean form; read per call: A/B switch)
@@ -1039,16 +978,25 @@ int launch_select(const KnnPlan& p, const void* query, const void* bank, int n, 
     if (e == nullptr || atoi(e) == 1024) {
       knn_select<DT, K, 1024><<<nq, 1024, lds, st>>>(static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank),
                                                      n, d, rowbytes, ps, pi, p.nslices, p.nslices, wm_cdiv(n, KNN_ROWS),
-                                                     index_base, kk, out_sim, out_idx);
+                                                     index_base, kout, out_sim, out_idx);
       WM_LAUNCH_CHECK();
       return WM_OK;
     }
   }
   knn_select<DT, K><<<nq, 256, lds, st>>>(static_cast<const uint8_t*>(query), static_cast<const uint8_t*>(bank), n, d,
                                           rowbytes, ps, pi, p.nslices, p.nslices, wm_cdiv(n, KNN_ROWS), index_base,
-                                          kk, out_sim, out_idx);
+                                          kout, out_sim, out_idx);
   WM_LAUNCH_CHECK();
   return WM_OK;
+}
+
+// One call: the streaming launch into the workspace's partial lists, then the selection launch.
+template <int DT, int K>
+int topk_run(const KnnPlan& p, const void* query, const void* bank, int nq, int n, int d, int rowbytes, float* ps,
+             int* pi, int index_base, int kout, float* out_sim, int* out_idx, hipStream_t st) {
+  const int rc = dispatch_qt<DT, K>(p, query, bank, nq, n, rowbytes, ps, pi, st);
+  if (rc != WM_OK) return rc;
+  return launch_select<DT, K>(p, query, bank, n, d, rowbytes, nq, ps, pi, index_base, kout, out_sim, out_idx, st);
 }
 
 }  // namespace
@@ -1072,30 +1020,16 @@ extern "C" int wm_knn_topk(const void* query, const void* bank, int nq, int n, i
   WM_REQUIRE(k <= 16 && k <= n, WM_EUNSUPPORTED);
   const int rowbytes = d * (dtype == WM_BF16 ? 2 : 4);
   WM_REQUIRE(rowbytes % KNN_SLAB == 0 && rowbytes <= (dtype == WM_F32 ? 2048 : 1024), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(query) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(bank) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-             WM_EALIGN);
+  WM_REQUIRE(al16(query) && al16(bank) && al16(workspace), WM_EALIGN);
   const KnnPlan p = make_plan(nq, n, rowbytes, k);
   const size_t cand = (size_t)p.qtiles * p.qt * 32 * p.nslices * p.kt;
   WM_REQUIRE(workspace_bytes >= cand * 8 + (size_t)nq * p.kt * 8, WM_EWORKSPACE);
   float* ps = static_cast<float*>(workspace);
   int* pi = reinterpret_cast<int*>(ps + cand);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc;
-  if (dtype == WM_BF16) {
-    rc = p.kt == 8 ? dispatch_qt<WM_BF16, 8>(p, query, bank, nq, n, rowbytes, ps, pi, st)
-                   : dispatch_qt<WM_BF16, 16>(p, query, bank, nq, n, rowbytes, ps, pi, st);
-  } else {
-    rc = p.kt == 8 ? dispatch_qt<WM_F32, 8>(p, query, bank, nq, n, rowbytes, ps, pi, st)
-                   : dispatch_qt<WM_F32, 16>(p, query, bank, nq, n, rowbytes, ps, pi, st);
-  }
-  if (rc != WM_OK) return rc;
-  if (dtype == WM_BF16)
-    return p.kt == 8 ? launch_select<WM_BF16, 8>(p, query, bank, n, d, rowbytes, nq, ps, pi, bank_index_base, k, out_sim, out_idx, st)
-                     : launch_select<WM_BF16, 16>(p, query, bank, n, d, rowbytes, nq, ps, pi, bank_index_base, k, out_sim, out_idx, st);
-  return p.kt == 8 ? launch_select<WM_F32, 8>(p, query, bank, n, d, rowbytes, nq, ps, pi, bank_index_base, k, out_sim, out_idx, st)
-                   : launch_select<WM_F32, 16>(p, query, bank, n, d, rowbytes, nq, ps, pi, bank_index_base, k, out_sim, out_idx, st);
+  const auto run = dtype == WM_BF16 ? (p.kt == 8 ? topk_run<WM_BF16, 8> : topk_run<WM_BF16, 16>)
+                                     : (p.kt == 8 ? topk_run<WM_F32, 8> : topk_run<WM_F32, 16>);
+  return run(p, query, bank, nq, n, d, rowbytes, ps, pi, bank_index_base, k, out_sim, out_idx, st);
 }
 
 // Many query batches, whole calls (streaming kernel + selection kernel) round-robin over the caller's streams, all

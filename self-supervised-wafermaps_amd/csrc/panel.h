@@ -18,7 +18,6 @@ struct WmPanelArgs {
   const float* ln_gamma;   // optional LayerNorm applied to the token rows first (on the register fragments): [192]
   const float* ln_beta;
   float ln_eps;
-  int debug;               // WM_PANEL_DEBUG bits (timing experiments): 1 no stores, 2 no MFMAs, 4 no staging, 8 no x rows
 };
 
 bool wm_panel_ok(long long rows, int C, int N, bool has_aux);

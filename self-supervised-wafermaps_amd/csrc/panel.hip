@@ -71,7 +71,7 @@ __global__ __launch_bounds__(PN_THREADS, 2) void linear_panel(const WmPanelArgs 
   int nt = a.N / 64 - t0;
   nt = nt < a.tiles_per_block ? nt : a.tiles_per_block;
   // Counted waits need every thread to have issued the same number of stores per tile: full blocks only.
-  const bool full = m0 + 128 <= a.rows && !(a.debug & 1);
+  const bool full = m0 + 128 <= a.rows;
   const int nst = a.act == 1 ? 4 : 2;         // 16-byte stores per thread and tile
 
   const int rl = tid >> 3, slot = tid & 7;    // weight row inside a panel / physical 16-byte slot
@@ -90,7 +90,6 @@ __global__ __launch_bounds__(PN_THREADS, 2) void linear_panel(const WmPanelArgs 
   for (int i = 0; i < 2; ++i) {
     int row = m0 + wm * 32 + i * 16 + fr;
     row = row < a.rows ? row : a.rows - 1;
-    if (a.debug & 8) row = fr;
     const uint16_t* xr = a.x + (size_t)row * C + fg * 8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) xf[i][ks] = *reinterpret_cast<const bf16x8_t*>(xr + ks * 32);
@@ -121,7 +120,6 @@ __global__ __launch_bounds__(PN_THREADS, 2) void linear_panel(const WmPanelArgs 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int i = 0; i < 2; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    if (!(a.debug & 2))
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       bf16x8_t wf[2];
@@ -137,7 +135,6 @@ __global__ __launch_bounds__(PN_THREADS, 2) void linear_panel(const WmPanelArgs 
         for (int i = 0; i < 2; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i][ks], acc[j][i], 0, 0, 0);
     }
     wm_barrier();   // every wave is done with the weights of this stage: it becomes the staging tile
-    if (!(a.debug & 4))
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(PN_THREADS, 2) void linear_panel(const WmPanelArgs 
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const int rloc = erow + it * 64;
-      if (m0 + rloc >= a.rows || (a.debug & 1)) continue;
+      if (m0 + rloc >= a.rows) continue;
       const uint4 v4 = *reinterpret_cast<const uint4*>(stage + rloc * PN_CS + ech * 16);
       uint32_t vv[4] = {v4.x, v4.y, v4.z, v4.w};
       const size_t off = (size_t)(m0 + rloc) * a.N + n0 + ech * 8;
@@ -206,9 +203,9 @@ int wm_panel_launch(WmPanelArgs a, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     attr = true;
   }
-  // column tiles per block: as many blocks as fit twice into the chip's 512 block slots (two per CU); measured
-  // (tools/probes/panel_probe.py, 39 424 rows): fc1 + GELU 65 us with all 12 tiles in one block (308 blocks), 49 us with
-  // 4 tiles per block (924 blocks); conv_igemm 57 us.  Never more than PN_MAX_N columns per block.
+  // column tiles per block: as many blocks as fit twice into the chip's 512 block slots (two per CU); measured at
+  // 39 424 rows: fc1 + GELU 65 us with all 12 tiles in one block (308 blocks), 49 us with 4 tiles per block (924
+  // blocks); conv_igemm 57 us.  Never more than PN_MAX_N columns per block.
   const int rowtiles = (a.rows + 127) / 128, tiles = a.N / 64;
   int split = 0;
   for (int s = 1; s <= tiles; ++s) {
@@ -216,12 +213,6 @@ int wm_panel_launch(WmPanelArgs a, hipStream_t st) {
     if (split == 0 || (long long)rowtiles * s <= 1024) split = s;
   }
   a.tiles_per_block = tiles / split;
-  {
-    const char* e = getenv("WM_PANEL_DEBUG");
-    a.debug = e ? atoi(e) : 0;
-    const char* f = getenv("WM_PANEL_SPLIT");
-    if (f && atoi(f) > 0 && tiles % atoi(f) == 0) { split = atoi(f); a.tiles_per_block = tiles / split; }
-  }
   if (a.ln_gamma != nullptr) linear_panel<192, true><<<dim3(rowtiles, split), PN_THREADS, lds, st>>>(a);
   else linear_panel<192, false><<<dim3(rowtiles, split), PN_THREADS, lds, st>>>(a);
   WM_LAUNCH_CHECK();
@@ -240,6 +231,6 @@ extern "C" int wm_ln_linear_fwd(const void* x, const float* ln_gamma, const floa
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   WM_REQUIRE(al(x) && al(ln_gamma) && al(ln_beta) && al(w_krsc) && al(y) && (bias == nullptr || al(bias)), WM_EALIGN);
   WmPanelArgs pa{static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(w_krsc), bias, nullptr, nullptr, nullptr,
-                 static_cast<uint16_t*>(y), rows, N, 0, 0, ln_gamma, ln_beta, ln_eps, 0};
+                 static_cast<uint16_t*>(y), rows, N, 0, 0, ln_gamma, ln_beta, ln_eps};
   return wm_panel_launch(pa, static_cast<hipStream_t>(stream));
 }

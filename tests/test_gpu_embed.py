@@ -47,8 +47,10 @@ def test_knn_topk_f32(nq, n, d, k):
 
 
 # (64, 262235, 128, 8): 2 049 chunks on 410 slices (a last round that only some slices take part in)
+# (100, 100003, 256, 8): the general bf16 kernel with 128-query tiles; 782 chunks on 196 slices, so its 3-stage ring
+# wraps (8 ring steps per slice) and the last chunk is ragged
 @pytest.mark.parametrize("nq,n,d,k", [(256, 50000, 128, 8), (64, 12449, 512, 5), (100, 3000, 256, 16), (64, 262235, 128, 8),
-                                      (40, 262235, 128, 16)])
+                                      (40, 262235, 128, 16), (100, 100003, 256, 8)])
 def test_knn_topk_bf16(nq, n, d, k):
     from ssl_wafermap_amd import functional as F
 
