@@ -777,6 +777,13 @@ int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, in
 size_t wm_knn_graph_workspace_bytes(int n, int d, int k);
 int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* The rectangular form: for every row of xq float32 [m][d] its k nearest rows of x float32 [n][d] under the same
+ * distance function, dist float32 [m][k] and idx int32 [m][k] in [0, n), every row ordered by (distance, index).
+ * m >= 1, 1 <= k <= 64, k <= n (k > n: WM_EINVAL); xq, x and the workspace 16-byte aligned.  With xq = x it returns
+ * wm_knn_graph's bits. */
+size_t wm_knn_query_workspace_bytes(int m, int n, int d, int k);
+int wm_knn_query(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas
@@ -797,6 +804,30 @@ int wm_umap_smooth_knn(const float* dist, const int32_t* idx, int n, int k, cons
 int wm_umap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n, int dim,
                    double a, double b, double gamma, double learning_rate, uint32_t seed, int epoch_begin, int epoch_end,
                    int n_epochs, int neg_rate, int* result_buffer, void* stream);
+
+/* Semi-supervised fits and the transform of new rows (umap-learn's discrete_metric_simplicial_set_intersection +
+ * reset_local_connectivity, and UMAP.transform); formulas in csrc/umap.hip.
+ *
+ * wm_umap_label_intersect: the categorical-target intersection of the symmetric-pattern CSR graph (indptr, indices,
+ * data float32 [nnz]) with labels int32 [n] (-1: unknown): every entry times f_unk (a label unknown), f_far (labels
+ * differ) or 1, rows divided by their maximum, then G + G^T - G o G^T, in double, rounded once into out float32 [nnz]
+ * (the pattern is kept; out may not alias data).  Symmetric in bits; a zero row stays zero.  workspace: n doubles,
+ * owned by the caller.  No atomics. */
+int wm_umap_label_intersect(const int32_t* indptr, const int32_t* indices, const float* data, const int32_t* labels, int n,
+                            double f_far, double f_unk, float* out, double* workspace, void* stream);
+/* wm_umap_smooth_knn for the rows of a rectangular kNN result dist float32 [m][k] (wm_knn_query): rho = 0 for every
+ * row (umap-learn's local_connectivity - 1 = 0), sigma[i] by the same bisection over j >= 1, floored at
+ * 1e-3 * *mean_dist, weights[i][j] = exp(-d_j / sigma) (1 where d_j <= 0; no self test).  1 <= k <= 64. */
+int wm_umap_smooth_knn_query(const float* dist, int m, int k, const double* mean_dist, float* sigma, float* weights,
+                             void* stream);
+/* Layout epochs [epoch_begin, epoch_end) of n_epochs for m new points among n fixed ones, ONE launch for all of them:
+ * y_in float32 [m][dim] -> y_out [m][dim] (may be the same buffer), y_train float32 [n][dim] read only, idx int32
+ * [m][k] in [0, n), q uint32 [m][k] = rint(65536 * weight / max weight).  Only the new points move, none reads another;
+ * the step of epoch ep is float32((learning_rate / 4) (1 - ep / n_epochs)).  Deterministic: splitting the epoch range
+ * over several calls, or calling twice, gives the same bits.  1 <= k <= 64, 1 <= dim <= 64, 0 <= neg_rate <= 64. */
+int wm_umap_transform_layout(const float* y_in, float* y_out, const float* y_train, const int32_t* idx, const uint32_t* q,
+                             int m, int n, int k, int dim, double a, double b, double gamma, double learning_rate,
+                             uint32_t seed, int epoch_begin, int epoch_end, int n_epochs, int neg_rate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DensMAP (umap.UMAP(densmap=True, ...): the density-preserving term added to the last dens_frac of the layout epochs);

@@ -289,10 +289,18 @@ SIGNATURES = {
     "wm_cluster_dist_sums": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "wm_knn_graph_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wm_knn_graph": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_knn_query_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_knn_query": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                             c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
                                c_double, c_uint32, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wm_umap_label_intersect": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,
+                                        c_void_p]),
+    "wm_umap_smooth_knn_query": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wm_umap_transform_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double,
+                                         c_double, c_double, c_double, c_uint32, c_int, c_int, c_int, c_int, c_void_p]),
     # ---- DensMAP
     "wm_densmap_graph_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "wm_densmap_embedding_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int,

@@ -5,7 +5,10 @@
 //                         leaves the row's component;
 //   wm_cluster_dist_sums  per row the sum of its distances to the members of every cluster (silhouette);
 //   wm_knn_graph          the k nearest rows of every row with their indices, ordered by (distance, index), the row
-//                         itself among its candidates (the exact kNN graph that manifold.UMAP starts from).
+//                         itself among its candidates (the exact kNN graph that manifold.UMAP starts from);
+//   wm_knn_query          the same for the rows of a second matrix against x (the rectangular form that the transform of
+//                         new rows starts from): cl_pairs takes its rows from a row operand of its own (xr, nr), which
+//                         every square mode sets to (x, n).
 //
 // ONE distance function serves all four (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
@@ -61,11 +64,12 @@ __device__ __forceinline__ float cl_finish(float acc) {
 }
 
 struct ClArgs {
-  const float* x;
-  int n, d, tiles_per_slice, col_tiles;
+  const float* x;   // the column operand [n][d]
+  const float* xr;  // the row operand [nr][d]: x itself in the square modes, the query rows in wm_knn_query
+  int n, nr, d, tiles_per_slice, col_tiles;
   // core
   int k, kl;
-  float* part_lists;  // [slices][n][k]
+  float* part_lists;  // [slices][nr][k]
   int* part_idx;      // knn: the lists' column indices, same shape (-1 pads a slice with fewer than k columns)
   // min edge
   const float* core;
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   [[maybe_unused]] int* extra_j = reinterpret_cast<int*>(extra) + ROWS * p.kl;  // knn: the lists' indices [ROWS][kl]
   const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
   const int lq = (t & 7) * 4, lr = t >> 3;  // staging: float4 at feature lq of row lr (+ 32 per pass)
-  const int n = p.n, d = p.d;
+  const int n = p.n, nr = p.nr, d = p.d;
   const int i0 = blockIdx.x * ROWS;
   const int tile0 = blockIdx.y * p.tiles_per_slice;
   const int tile1 = min(tile0 + p.tiles_per_slice, p.col_tiles);
@@ -116,8 +120,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
 #pragma unroll
     for (int r = 0; r < TM; ++r) {
       const int i = i0 + ty + 16 * r;
-      ci[r] = i < n ? p.core[i] : 0.f;
-      cpi[r] = i < n ? p.comp[i] : 0;
+      ci[r] = i < nr ? p.core[i] : 0.f;
+      cpi[r] = i < nr ? p.comp[i] : 0;
       bw[r] = INFINITY;
       bj[r] = -1;
     }
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
 #pragma unroll
       for (int s = 0; s < APASS; ++s) {
         const int row = i0 + lr + 32 * s;
-        ra[s] = (row < n && kq < d) ? *reinterpret_cast<const float4*>(p.x + (size_t)row * d + kq)
+        ra[s] = (row < nr && kq < d) ? *reinterpret_cast<const float4*>(p.xr + (size_t)row * d + kq)
                                     : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
@@ -200,7 +204,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       }
 #pragma unroll
       for (int r = 0; r < TM; ++r) {
-        const bool iv = i0 + ty + 16 * r < n;
+        const bool iv = i0 + ty + 16 * r < nr;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int j = j0 + tx + 16 * c;
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       __syncthreads();
       // (the next write of Dt / the labels lies behind the next tile's chunk barriers, which the owners reach only
       // after this scan)
-      if (t < ROWS && i0 + t < n) {
+      if (t < ROWS && i0 + t < nr) {
         const float* row = Dt + t * CL_LDD;
         if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
           float* L = extra + t * p.kl;
@@ -264,16 +268,16 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
 
   // ---- the slice's result
   if constexpr (MODE == CL_SUMS) {
-    if (t < ROWS && i0 + t < n && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
+    if (t < ROWS && i0 + t < nr && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
   }
   if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
-    if (t < ROWS && i0 + t < n) {
+    if (t < ROWS && i0 + t < nr) {
       const float* L = extra + t * p.kl;
-      float* o = p.part_lists + ((size_t)blockIdx.y * n + i0 + t) * p.k;
+      float* o = p.part_lists + ((size_t)blockIdx.y * nr + i0 + t) * p.k;
       for (int q = 0; q < p.k; ++q) o[q] = L[q];
       if constexpr (MODE == CL_KNN) {
         const int* J = extra_j + t * p.kl;
-        int* oj = p.part_idx + ((size_t)blockIdx.y * n + i0 + t) * p.k;
+        int* oj = p.part_idx + ((size_t)blockIdx.y * nr + i0 + t) * p.k;
         for (int q = 0; q < p.k; ++q) oj[q] = J[q];
       }
     }
@@ -288,7 +292,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       rj[(ty + 16 * r) * 17 + tx] = bj[r];
     }
     __syncthreads();
-    if (t < ROWS && i0 + t < n) {
+    if (t < ROWS && i0 + t < nr) {
       float w = rw[t * 17];
       int j = rj[t * 17];
       for (int q = 1; q < 16; ++q) {
@@ -299,8 +303,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
           j = jq;
         }
       }
-      p.part_w[(size_t)blockIdx.y * n + i0 + t] = w;
-      p.part_j[(size_t)blockIdx.y * n + i0 + t] = j;
+      p.part_w[(size_t)blockIdx.y * nr + i0 + t] = w;
+      p.part_j[(size_t)blockIdx.y * nr + i0 + t] = j;
     }
   }
 }
@@ -330,7 +334,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_core_merge(const float* __restr
 // The k smallest of the slices' k-lists of a row under (distance, index), in that order: one wave per row, a lane per
 // candidate.  Every list is sorted by (distance, index), so a candidate's rank is the sum over the lists of the number
 // of entries before it (a binary search each); the -1 pads of a short slice sit at +inf behind every row index and are
-// told apart by their position.  The n >= k real candidates fill the ranks 0 .. k-1, each exactly once.
+// told apart by their position.  The at least k real candidates fill the ranks 0 .. k-1, each exactly once.  n: the
+// number of rows of the lists (the row operand's).
 __global__ __launch_bounds__(CL_THREADS) void cl_knn_merge(const float* __restrict__ pd, const int* __restrict__ pj,
                                                            int slices, int n, int k, float* __restrict__ out_d,
                                                            int* __restrict__ out_j) {
@@ -386,10 +391,11 @@ __global__ __launch_bounds__(CL_THREADS) void cl_minedge_merge(const float* __re
 struct ClGrid {
   int row_tiles, col_tiles, slices, tiles_per_slice;
 };
-// Column slices so that about a thousand workgroups exist (four per CU); every slice holds at least one tile.
-inline ClGrid cl_grid(int n, int rows, bool sliced) {
+// Column slices so that about a thousand workgroups exist (four per CU); every slice holds at least one tile.  m rows
+// (the row operand) against n columns; the square modes pass n for both.
+inline ClGrid cl_grid(int m, int n, int rows, bool sliced) {
   ClGrid g;
-  g.row_tiles = wm_cdiv(n, rows);
+  g.row_tiles = wm_cdiv(m, rows);
   g.col_tiles = wm_cdiv(n, CL_COLS);
   int want = sliced ? wm_cdiv(1024, g.row_tiles) : 1;
   if (want > g.col_tiles) want = g.col_tiles;
@@ -426,7 +432,7 @@ constexpr int CL_MAX_N = 1 << 24;  // (row * d and slice * n + row stay far insi
 
 extern "C" size_t wm_core_distance_workspace_bytes(int n, int d, int k) {
   if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  return (size_t)cl_grid(n, 128, true).slices * n * k * sizeof(float) + 256;
+  return (size_t)cl_grid(n, n, 128, true).slices * n * k * sizeof(float) + 256;
 }
 
 extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k, float* out, void* workspace,
@@ -435,12 +441,12 @@ extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k,
   WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
   WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
   WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, 128, true);
+  const ClGrid g = cl_grid(n, n, 128, true);
   WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * k * sizeof(float), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClArgs a = {};
-  a.x = x;
-  a.n = n;
+  a.x = a.xr = x;
+  a.n = a.nr = n;
   a.d = d;
   a.tiles_per_slice = g.tiles_per_slice;
   a.col_tiles = g.col_tiles;
@@ -456,7 +462,7 @@ extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k,
 
 extern "C" size_t wm_knn_graph_workspace_bytes(int n, int d, int k) {
   if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  return (size_t)cl_grid(n, 128, true).slices * n * k * 8 + 256;
+  return (size_t)cl_grid(n, n, 128, true).slices * n * k * 8 + 256;
 }
 
 extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
@@ -465,13 +471,13 @@ extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, flo
   WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
   WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
   WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, 128, true);
+  const ClGrid g = cl_grid(n, n, 128, true);
   const size_t entries = (size_t)g.slices * n * k;
   WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClArgs a = {};
-  a.x = x;
-  a.n = n;
+  a.x = a.xr = x;
+  a.n = a.nr = n;
   a.d = d;
   a.tiles_per_slice = g.tiles_per_slice;
   a.col_tiles = g.col_tiles;
@@ -486,9 +492,45 @@ extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, flo
   return WM_OK;
 }
 
+extern "C" size_t wm_knn_query_workspace_bytes(int m, int n, int d, int k) {
+  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
+  return (size_t)cl_grid(m, n, 128, true).slices * m * k * 8 + 256;
+}
+
+extern "C" int wm_knn_query(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(xq && x && dist && idx && workspace, WM_EINVAL);
+  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+             WM_EALIGN);
+  const ClGrid g = cl_grid(m, n, 128, true);
+  const size_t entries = (size_t)g.slices * m * k;
+  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.xr = xq;
+  a.nr = m;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.k = k;
+  a.kl = k | 1;
+  a.part_lists = static_cast<float*>(workspace);
+  a.part_idx = reinterpret_cast<int*>(a.part_lists + entries);
+  const int rc = cl_launch<CL_KNN, 8>(a, g, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_knn_merge<<<wm_cdiv(m, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, g.slices, m, k, dist, idx);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
 extern "C" size_t wm_mreach_min_edge_workspace_bytes(int n, int d) {
   if (n <= 0 || n > CL_MAX_N || d <= 0) return 0;
-  return (size_t)cl_grid(n, 128, true).slices * n * 8 + 256;
+  return (size_t)cl_grid(n, n, 128, true).slices * n * 8 + 256;
 }
 
 extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32_t* comp, int n, int d, int metric,
@@ -498,12 +540,12 @@ extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32
   WM_REQUIRE(n > 0 && d > 0 && inv_alpha > 0.f, WM_EINVAL);
   WM_REQUIRE(n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
   WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, 128, true);
+  const ClGrid g = cl_grid(n, n, 128, true);
   WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * 8, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClArgs a = {};
-  a.x = x;
-  a.n = n;
+  a.x = a.xr = x;
+  a.n = a.nr = n;
   a.d = d;
   a.tiles_per_slice = g.tiles_per_slice;
   a.col_tiles = g.col_tiles;
@@ -528,10 +570,10 @@ extern "C" int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = wm_zero_async(out, (size_t)n * n_clusters * sizeof(double), st);
   if (e != hipSuccess) return (int)e;
-  const ClGrid g = cl_grid(n, 64, false);
+  const ClGrid g = cl_grid(n, n, 64, false);
   ClArgs a = {};
-  a.x = x;
-  a.n = n;
+  a.x = a.xr = x;
+  a.n = a.nr = n;
   a.d = d;
   a.tiles_per_slice = g.tiles_per_slice;
   a.col_tiles = g.col_tiles;

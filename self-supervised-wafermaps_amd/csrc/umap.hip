@@ -2,7 +2,9 @@
 // 3.2-Embeddings-SSL-categories and the 2.0 figure notebooks: umap.UMAP(...).fit_transform(data)):
 //   wm_umap_smooth_knn   per row of the kNN graph (csrc/cluster.hip: wm_knn_graph) the fuzzy-simplicial-set parameters
 //                        rho, sigma and the membership weights;
-//   wm_umap_layout       the layout optimisation, the hot path: one launch per epoch over every graph entry.
+//   wm_umap_layout       the layout optimisation, the hot path: one launch per epoch over every graph entry;
+//   wm_umap_label_intersect, wm_umap_smooth_knn_query, wm_umap_transform_layout
+//                        semi-supervised fits (y=) and the transform of new rows: stated at the end of this comment.
 // The symmetrisation between the two (G = P + P^T - P o P^T as CSR) is a one-off index build in torch (manifold.py).
 //
 // ---- smooth kNN (umap-learn's smooth_knn_dist + compute_membership_strengths, local_connectivity = 1)
@@ -82,6 +84,50 @@
 //   [64, 4160)     double slots[4][128]: partial sums of mu_tot, re, (re - mean)^2, re R
 //   [4160, +16 n)  float32 [n][4]: 1 / D, 1 / (eps + N / D), W, re
 //   then           double re[n], D[n], N / D [n]
+//
+// ---- label intersection (umap-learn's discrete_metric_simplicial_set_intersection + reset_local_connectivity for a
+// categorical target; manifold.InductiveUMAP.fit(x, y)).  G is the symmetric-pattern CSR of the union above, labels
+// int32 [n] with -1 = unknown, f_far = exp(-far_dist), f_unk = exp(-unknown_dist) formed by the host in double:
+//   f_e   = f_unk if either label of e = (i -> j) is -1, f_far if the labels differ, else 1;   v_e = double(w_e) f_e
+//   max_i = max_e v_e over row i;   m_e = v_e / max_i, 0 when max_i = 0          (normalize(norm="max"): a zero row stays
+//           zero, no NaN appears)
+//   g_e   = (m_e + m_t) - m_e m_t in double, t the entry (j -> i), found by binary search in row j's sorted columns
+//           (m_t = 0 if absent); rounded once to float32.
+// Both directions evaluate the same expression on the same two numbers (sum and product commute; contraction is
+// switched off so that neither direction fuses what the other does not): the result is symmetric in bits.  The
+// pattern is unchanged: an entry that becomes 0 stays as an explicit zero whose rate is 0.  Two kernels of one thread
+// per row, no atomics; the workspace is max_i, one double per row.
+//
+// ---- memberships of new rows (umap-learn's smooth_knn_dist(local_connectivity = 0) + compute_membership_strengths
+// (bipartite=True) as UMAP.transform calls them).  Row i holds the k distances of a new row to its nearest fitted rows:
+//   rho_i = 0;   sigma_i: the bisection above on S(s) = sum_{j >= 1} (d_j > 0 ? exp(-d_j / s) : 1) (the first neighbour
+//   is skipped exactly as umap-learn skips it), then s >= 1e-3 * the mean of all m k distances;
+//   w_ij = 1 where d_j <= 0, else exp(-d_j / sigma_i); there is no self test.
+// In double; sigma is rounded to float32 and the weights are computed from the rounded value.
+//
+// ---- transform layout (umap-learn's optimize_layout_euclidean(move_other=False) of UMAP.transform, restated as above)
+// y_train float32 [n][dim] are the fitted positions, read only; new point i has k entries e = i k + j with neighbour
+// idx_e in [0, n) and rate q_e.  With sampled, att, rep, clip and mix of the layout above:
+//   y_i'      = y_i + alpha_ep * sum_{sampled e} [att(y_i, Y[idx_e]) + sum_{t < R} rep(y_i, Y[k(e, ep, t)])]
+//   alpha_ep  = float32((learning_rate / 4) * (1 - ep / n_epochs)), in double exactly as written, in the kernel;
+//   k(e, ep, t) = (uint64(h) * n) >> 32,  h = mix(mix(mix(seed ^ ep * 0x9e3779b9) + e) + t).
+// The attraction counts once: only the head moves.  Negatives are drawn from the n fitted points; the force is 0 at
+// r = 0 (umap-learn's j == k skip compares a new index with a fitted one and is not restated).  All terms of an epoch read
+// the position from before that epoch.
+// No new point reads another new point, so nothing orders the epochs of different points: ONE launch runs all epochs
+// of [epoch_begin, epoch_end), one wave per new point with the slot layout of the layout kernel (EPP = 64 / DP entry
+// slots of DP component lanes), y_i in registers throughout (every slot holds the same bits of it), the epoch key and
+// alpha_ep computed in the kernel, the point's idx / q rows staged once in a strip of LDS that only this wave touches,
+// the result written once at the end.  No block barrier, no atomics, no traffic between waves.  An epoch of a wave is
+// bound by the vector ALU (one powf per term on all 64 lanes) like the fit kernel's: fetching the rows of a pass's
+// 1 + R terms together before using the first, and one-wave workgroups, were tried and were no faster
+// (profiles/umap_transform.md).
+// Order of the additions of an epoch: every lane adds the terms of its entries in entry order (per entry the
+// attraction, then the R repulsions); then the EPP slots of a component are added by an xor butterfly over the lane
+// strides DP, 2 DP, ..., 32 in that order (strides 1 and 2: quad_perm; 4 and 8: __shfl_xor; 16 and 32:
+// v_permlane16/32_swap) -- true xor exchanges, so both partners add the same two numbers and, float addition being
+// commutative, every slot ends with the same bits; log2(EPP) additions.  An epoch without a sampled entry leaves y_i as
+// it is.
 #include "common.h"
 
 namespace {
@@ -450,6 +496,175 @@ inline int dm_blocks(long long count) {
   return nb < 1 ? 1 : (nb > DM_SLOTS ? DM_SLOTS : nb);
 }
 
+// ---- label intersection
+
+__device__ __forceinline__ double um_label_factor(int li, int lj, double f_far, double f_unk) {
+  return (li < 0 || lj < 0) ? f_unk : (li != lj ? f_far : 1.0);
+}
+
+// ws[i] = max_e double(w_e) f_e over row i
+__global__ __launch_bounds__(UM_THREADS) void umap_label_max_kernel(const int* __restrict__ indptr, const int* __restrict__ indices,
+                                                                    const float* __restrict__ data, const int* __restrict__ labels,
+                                                                    int n, double f_far, double f_unk, double* __restrict__ ws) {
+  const int i = blockIdx.x * UM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int li = labels[i];
+  double mx = 0.0;
+  for (int e = indptr[i]; e < indptr[i + 1]; ++e) {
+    const double v = (double)data[e] * um_label_factor(li, labels[indices[e]], f_far, f_unk);
+    mx = v > mx ? v : mx;
+  }
+  ws[i] = mx;
+}
+
+__global__ __launch_bounds__(UM_THREADS) void umap_label_intersect_kernel(const int* __restrict__ indptr,
+                                                                          const int* __restrict__ indices,
+                                                                          const float* __restrict__ data,
+                                                                          const int* __restrict__ labels, int n, double f_far,
+                                                                          double f_unk, const double* __restrict__ ws,
+                                                                          float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * UM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int li = labels[i];
+  const double mi = ws[i];
+  for (int e = indptr[i]; e < indptr[i + 1]; ++e) {
+    const int j = indices[e];
+    const double f = um_label_factor(li, labels[j], f_far, f_unk);
+    const double me = mi > 0.0 ? ((double)data[e] * f) / mi : 0.0;
+    int lo = indptr[j], hi = indptr[j + 1];  // the first entry of row j whose column is not below i
+    const int end = hi;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (indices[mid] < i) lo = mid + 1; else hi = mid;
+    }
+    const double mj = ws[j];
+    const double mt = (lo < end && indices[lo] == i && mj > 0.0) ? ((double)data[lo] * f) / mj : 0.0;
+    out[e] = (float)((me + mt) - me * mt);
+  }
+}
+
+// ---- memberships of new rows: one thread per row, in double
+
+__global__ __launch_bounds__(UM_THREADS) void umap_smooth_knn_query_kernel(const float* __restrict__ dist, int m, int k,
+                                                                           const double* __restrict__ mean_all,
+                                                                           float* __restrict__ sigma, float* __restrict__ w) {
+  const int i = blockIdx.x * UM_THREADS + threadIdx.x;
+  if (i >= m) return;
+  const float* dr = dist + (size_t)i * k;
+  const double target = log2((double)k);
+  double lo = 0.0, hi = INFINITY, mid = 1.0;
+  for (int it = 0; it < 64; ++it) {
+    double psum = 0.0;
+    for (int j = 1; j < k; ++j) {
+      const double d = (double)dr[j];
+      psum += d > 0.0 ? exp(-d / mid) : 1.0;
+    }
+    if (fabs(psum - target) < 1e-5) break;
+    if (psum > target) {
+      hi = mid;
+      mid = 0.5 * (lo + hi);
+    } else {
+      lo = mid;
+      mid = hi == INFINITY ? 2.0 * mid : 0.5 * (lo + hi);
+    }
+  }
+  const double floor_s = 1e-3 * *mean_all;
+  if (mid < floor_s) mid = floor_s;
+  const float sg = (float)mid;
+  sigma[i] = sg;
+  for (int j = 0; j < k; ++j) {
+    const double d = (double)dr[j];
+    w[(size_t)i * k + j] = (float)((d <= 0.0 || sg == 0.f) ? 1.0 : exp(-d / (double)sg));
+  }
+}
+
+// ---- transform layout
+
+struct UmTransformArgs {
+  const float* y_in;
+  float* y_out;
+  const float* y_train;
+  const int* idx;
+  const uint32_t* q;
+  int m, n, k, dim, neg_rate;
+  uint32_t seed;
+  int ep_begin, ep_end;
+  double lr4, n_epochs;  // learning_rate / 4 and n_epochs, as alpha_ep reads them
+  float a, b, c_att, c_rep;
+};
+
+// The sum over the EPP slots of a component, the same bits in every slot: xor exchanges at the strides DP .. 32.
+template <int DP>
+__device__ __forceinline__ float um_slot_sum(float v) {
+  if constexpr (DP <= 1) v += wm_dpp<0xB1>(v);
+  if constexpr (DP <= 2) v += wm_dpp<0x4E>(v);
+  if constexpr (DP <= 4) v += __shfl_xor(v, 4, 64);
+  if constexpr (DP <= 8) v += __shfl_xor(v, 8, 64);
+  if constexpr (DP <= 16) v = wm_xor16_sum(v);
+  if constexpr (DP <= 32) v = wm_xor32_sum(v);
+  return v;
+}
+
+template <int DP>
+__global__ __launch_bounds__(UM_THREADS) void umap_transform_kernel(const UmTransformArgs p) {
+  constexpr int EPP = 64 / DP;
+  constexpr int WAVES = UM_THREADS / 64;
+  __shared__ int s_idx[WAVES][64];
+  __shared__ uint32_t s_q[WAVES][64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = lane & (DP - 1), es = lane / DP;
+  const int i = blockIdx.x * WAVES + wave;
+  if (i >= p.m) return;  // (a whole wave at once; the kernel has no barrier)
+  const bool comp = c < p.dim;
+  const int k = p.k;
+  // the point's entries: written and read by this wave alone, whose LDS operations execute in order
+  s_idx[wave][lane] = lane < k ? p.idx[(size_t)i * k + lane] : 0;
+  s_q[wave][lane] = lane < k ? p.q[(size_t)i * k + lane] : 0u;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float yi = comp ? p.y_in[(size_t)i * p.dim + c] : 0.f;
+  const uint32_t e_base = (uint32_t)i * (uint32_t)k;
+  for (int ep = p.ep_begin; ep < p.ep_end; ++ep) {
+    const uint32_t uep = (uint32_t)ep;
+    const uint32_t ep_key = lowbias32(p.seed ^ (uep * 0x9e3779b9U));
+    float acc = 0.f;
+    bool any = false;
+    for (int j0 = 0; j0 < k; j0 += EPP) {
+      const int jl = j0 + es;
+      const uint32_t qe = jl < k ? s_q[wave][jl] : 0u;
+      const bool hit = (((uint64_t)(uep + 1u) * qe) >> 16) > (((uint64_t)uep * qe) >> 16);
+      if (__ballot(hit) == 0ull) continue;
+      any = true;
+      {
+        const int j = hit ? s_idx[wave][jl] : 0;
+        const float yj = comp ? p.y_train[(size_t)j * p.dim + c] : 0.f;
+        const float d = yi - yj;
+        const float r = group_sum<DP>(d * d);
+        const float pb = powf(r, p.b);
+        const float coef = (p.c_att * pb) / (r * (p.a * pb + 1.f));
+        if (hit && r > 0.f) acc += um_clip(coef * d);
+      }
+      const uint32_t key = lowbias32(ep_key + e_base + (uint32_t)jl);
+      for (int t = 0; t < p.neg_rate; ++t) {
+        const uint32_t h = lowbias32(key + (uint32_t)t);
+        const int kk = hit ? (int)(((uint64_t)h * (uint32_t)p.n) >> 32) : 0;
+        const float yk = comp ? p.y_train[(size_t)kk * p.dim + c] : 0.f;
+        const float d = yi - yk;
+        const float r = group_sum<DP>(d * d);
+        const float pb = powf(r, p.b);
+        const float coef = p.c_rep / ((0.001f + r) * (p.a * pb + 1.f));
+        if (hit && r > 0.f) acc += um_clip(coef * d);
+      }
+    }
+    if (!any) continue;  // (wave-uniform)
+    const float alpha = (float)(p.lr4 * (1.0 - (double)ep / p.n_epochs));
+    yi = yi + alpha * um_slot_sum<DP>(acc);
+  }
+  if (es == 0 && comp) p.y_out[(size_t)i * p.dim + c] = yi;
+}
+
 inline uint32_t um_mix_host(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352dU;
@@ -609,5 +824,76 @@ extern "C" int wm_densmap_layout(float* y_a, float* y_b, const int32_t* indptr, 
     nxt = sw;
   }
   *result_buffer = cur == y_a ? 0 : 1;
+  return WM_OK;
+}
+
+extern "C" int wm_umap_label_intersect(const int32_t* indptr, const int32_t* indices, const float* data, const int32_t* labels,
+                                       int n, double f_far, double f_unk, float* out, double* workspace, void* stream) {
+  WM_REQUIRE(indptr && indices && data && labels && out && workspace && out != data, WM_EINVAL);
+  WM_REQUIRE(n > 0 && f_far >= 0.0 && f_far <= 1.0 && f_unk >= 0.0 && f_unk <= 1.0, WM_EINVAL);
+  WM_REQUIRE(n <= (1 << 24), WM_EUNSUPPORTED);
+  WM_REQUIRE(((uintptr_t)workspace & 7u) == 0, WM_EALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  umap_label_max_kernel<<<wm_cdiv(n, UM_THREADS), UM_THREADS, 0, st>>>(indptr, indices, data, labels, n, f_far, f_unk, workspace);
+  WM_LAUNCH_CHECK();
+  umap_label_intersect_kernel<<<wm_cdiv(n, UM_THREADS), UM_THREADS, 0, st>>>(indptr, indices, data, labels, n, f_far, f_unk,
+                                                                            workspace, out);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_umap_smooth_knn_query(const float* dist, int m, int k, const double* mean_dist, float* sigma, float* weights,
+                                        void* stream) {
+  WM_REQUIRE(dist && mean_dist && sigma && weights, WM_EINVAL);
+  WM_REQUIRE(m > 0 && k > 0, WM_EINVAL);
+  WM_REQUIRE(k <= 64 && m <= (1 << 24), WM_EUNSUPPORTED);
+  umap_smooth_knn_query_kernel<<<wm_cdiv(m, UM_THREADS), UM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(dist, m, k, mean_dist,
+                                                                                                         sigma, weights);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_umap_transform_layout(const float* y_in, float* y_out, const float* y_train, const int32_t* idx,
+                                        const uint32_t* q, int m, int n, int k, int dim, double a, double b, double gamma,
+                                        double learning_rate, uint32_t seed, int epoch_begin, int epoch_end, int n_epochs,
+                                        int neg_rate, void* stream) {
+  WM_REQUIRE(y_in && y_out && y_train && idx && q && y_out != y_train, WM_EINVAL);
+  WM_REQUIRE(m > 0 && n > 0 && k > 0 && dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end &&
+                 epoch_end <= n_epochs,
+             WM_EINVAL);
+  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
+  WM_REQUIRE(k <= 64 && dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG && m <= (1 << 24) && n <= (1 << 24), WM_EUNSUPPORTED);
+  UmTransformArgs p = {};
+  p.y_in = y_in;
+  p.y_out = y_out;
+  p.y_train = y_train;
+  p.idx = idx;
+  p.q = q;
+  p.m = m;
+  p.n = n;
+  p.k = k;
+  p.dim = dim;
+  p.neg_rate = neg_rate;
+  p.seed = seed;
+  p.ep_begin = epoch_begin;
+  p.ep_end = epoch_end;
+  p.lr4 = learning_rate / 4.0;
+  p.n_epochs = (double)n_epochs;
+  p.a = (float)a;
+  p.b = (float)b;
+  p.c_att = (float)(-2.0 * a * b);
+  p.c_rep = (float)(2.0 * gamma * b);
+  const int grid = wm_cdiv(m, UM_THREADS / 64);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define UM_TRANSFORM(DP) umap_transform_kernel<DP><<<grid, UM_THREADS, 0, st>>>(p)
+  if (dim == 1) UM_TRANSFORM(1);
+  else if (dim == 2) UM_TRANSFORM(2);
+  else if (dim <= 4) UM_TRANSFORM(4);
+  else if (dim <= 8) UM_TRANSFORM(8);
+  else if (dim <= 16) UM_TRANSFORM(16);
+  else if (dim <= 32) UM_TRANSFORM(32);
+  else UM_TRANSFORM(64);
+#undef UM_TRANSFORM
+  WM_LAUNCH_CHECK();
   return WM_OK;
 }

@@ -24,7 +24,17 @@ the same three steps, plus
      terms by fixed-order kernels, then the layout kernel with the term compiled in (wm_densmap_layout).
 `UMAP(densmap=True)` itself keeps raising and names `DensMAP`.
 
-Not built (NotImplementedError naming the feature): y= (semi-supervised fits), transform of new rows.
+Semi-supervised fits and the transform of new rows (`reducer.fit(x, y=labels); reducer.transform(x)` of notebooks
+3.0-Embeddings-inference and 2.0-Figures-MixedWM38, labels -1 where unknown) are the estimators `InductiveUMAP` and
+`InductiveDensMAP`: the parents' steps, plus
+  5. with y: the categorical-target intersection of the fuzzy graph (csrc/umap.hip: wm_umap_label_intersect), applied
+     between `fuzzy_simplicial_set` and the initialisation;
+  6. transform: the exact kNN of the new rows among the fitted ones (csrc/cluster.hip: wm_knn_query), their
+     memberships (wm_umap_smooth_knn_query), the weighted-average start, and the layout in which only the new points
+     move -- all epochs in one launch, one wave per point (wm_umap_transform_layout).
+`UMAP` and `DensMAP` themselves keep raising for y= and transform and name these classes.
+
+Not built: target_metric other than "categorical", inverse_transform, update (NotImplementedError naming the feature).
 Only local_connectivity = 1 and set_op_mix_ratio = 1 are supported.
 """
 from __future__ import annotations
@@ -130,6 +140,53 @@ def smooth_knn(dist, idx):
     return rho, sigma, w
 
 
+def knn_query(xq, x, k: int, metric: str = "euclidean"):
+    """The k nearest rows of x [n, d] for every row of xq [m, d] (device tensors): (dist float32 [m, k], idx int32
+    [m, k]) on the device, every row ordered by (distance, index), by `knn_graph`'s distance function (a query equal to
+    a row of x leads with exactly 0).  1 <= k <= min(n, 64), m >= 1.  `knn_query(x, x, k)` is `knn_graph(x, k)` in bits."""
+    import torch
+
+    code = metric_code(metric)
+    xq, x = _prep(xq), _prep(x)
+    if xq.shape[1] != x.shape[1]:
+        raise ValueError(f"xq has {xq.shape[1]} features, x has {x.shape[1]}")
+    (m, d), n = xq.shape, x.shape[0]
+    k = int(k)
+    if m < 1:
+        raise ValueError("at least one query row expected")
+    if not 1 <= k <= n:
+        raise ValueError(f"k ({k}) must be in [1, n_samples = {n}]")
+    lib = _lib.load()
+    need = lib.wm_knn_query_workspace_bytes(m, n, d, k)
+    if need == 0:
+        raise ValueError(f"knn_query: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    dist = torch.empty((m, k), dtype=torch.float32, device=x.device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
+    check(lib.wm_knn_query(ptr(xq), m, ptr(x), n, d, code, k, ptr(dist), ptr(idx), ptr(ws), need, stream_ptr()), "wm_knn_query")
+    return dist, idx
+
+
+def smooth_knn_query(dist):
+    """(sigma [m], weights [m, k]) float32 of the distances of new rows to their nearest fitted rows as `knn_query`
+    returns them: umap-learn's smooth_knn_dist with local_connectivity = 0 (rho = 0) and
+    compute_membership_strengths(bipartite=True), as UMAP.transform calls them."""
+    import torch
+
+    require_gpu(dist)
+    if dist.dim() != 2 or dist.dtype != torch.float32:
+        raise ValueError("dist float32 [m, k] expected")
+    m, k = dist.shape
+    if m < 1 or not 1 <= k <= MAX_NEIGHBORS:
+        raise ValueError(f"m >= 1 and k in [1, {MAX_NEIGHBORS}] expected")
+    mean = dist.double().mean().reshape(1).contiguous()
+    sigma = torch.empty(m, dtype=torch.float32, device=dist.device)
+    w = torch.empty((m, k), dtype=torch.float32, device=dist.device)
+    check(_lib.load().wm_umap_smooth_knn_query(ptr(dist), m, k, ptr(mean), ptr(sigma), ptr(w), stream_ptr()),
+          "wm_umap_smooth_knn_query")
+    return sigma, w
+
+
 class CSR(NamedTuple):
     """A square sparse matrix on the device: indptr int32 [n + 1], indices int32 [nnz] (columns sorted within a row),
     data float32 [nnz]."""
@@ -197,6 +254,45 @@ def fuzzy_simplicial_set(x, n_neighbors: int, metric: str = "euclidean", return_
     return fuzzy_union(idx, w, dist if return_dists else None)
 
 
+def far_distance(target_weight: float) -> float:
+    """umap-learn's far_dist of a categorical target: 2.5 / (1 - target_weight), 1e12 at target_weight = 1."""
+    return 2.5 / (1.0 - target_weight) if target_weight < 1.0 else 1.0e12
+
+
+def label_intersect(graph: CSR, labels, far_dist: float, unknown_dist: float = 1.0) -> CSR:
+    """umap-learn's discrete_metric_simplicial_set_intersection + reset_local_connectivity of the symmetric-pattern
+    CSR `graph` (`fuzzy_union`) with `labels` int32 [n] on the device (-1: unknown): entries across two labels are
+    scaled by exp(-far_dist), entries with an unknown end by exp(-unknown_dist), rows are divided by their maximum and
+    the result is symmetrised again (csrc/umap.hip: wm_umap_label_intersect).  Same pattern, symmetric in bits; an
+    entry that becomes 0 stays as an explicit zero."""
+    import math
+
+    import torch
+
+    require_gpu(graph.indptr, graph.indices, graph.data, labels)
+    n = graph.shape[0]
+    if graph.indptr.dtype != torch.int32 or graph.indices.dtype != torch.int32 or graph.data.dtype != torch.float32:
+        raise ValueError("graph: indptr, indices int32 and data float32 expected")
+    if graph.indices.shape != graph.data.shape or graph.indices.dim() != 1:
+        raise ValueError("graph: indices [nnz] and data [nnz] expected")
+    if labels.dtype != torch.int32 or labels.shape != (n,):
+        raise ValueError(f"labels int32 [{n}] expected")
+    if n < 1 or not (far_dist >= 0 and unknown_dist >= 0):
+        raise ValueError("a graph of at least one vertex and far_dist, unknown_dist >= 0 expected")
+    # the kernel trusts the graph: check once here that no entry points outside it
+    ip = graph.indptr.long()
+    if int(ip[0]) != 0 or int(ip[-1]) != graph.indices.numel() or bool((ip[1:] < ip[:-1]).any()):
+        raise ValueError("indptr must rise from 0 to nnz")
+    if graph.indices.numel() and (int(graph.indices.min()) < 0 or int(graph.indices.max()) >= n):
+        raise ValueError("indices must lie in [0, n)")
+    out = torch.empty_like(graph.data)
+    ws = torch.empty(n, dtype=torch.float64, device=graph.data.device)
+    check(_lib.load().wm_umap_label_intersect(ptr(graph.indptr), ptr(graph.indices), ptr(graph.data), ptr(labels), n,
+                                              math.exp(-float(far_dist)), math.exp(-float(unknown_dist)), ptr(out), ptr(ws),
+                                              stream_ptr()), "wm_umap_label_intersect")
+    return CSR(graph.indptr, graph.indices, out)
+
+
 def sample_rates(data):
     """q_e = rint(65536 w_e / max w) of the graph's weights, in float64, as the int32 tensor the layout kernel reads
     (0 <= q_e <= 65536)."""
@@ -256,6 +352,44 @@ def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, ep
                                      int(n_epochs), int(negative_sample_rate), ctypes.addressof(which), stream_ptr()),
           "wm_umap_layout")
     return bufs[which.value]
+
+
+def optimize_transform(y_new, y_train, idx, q, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
+                       epoch_end: Optional[int] = None, gamma: float = 1.0, learning_rate: float = 1.0, seed: int = 42,
+                       negative_sample_rate: int = 5):
+    """Epochs [epoch_begin, epoch_end) of `n_epochs` of the transform layout (csrc/umap.hip: wm_umap_transform_layout):
+    the new points y_new float32 [m, dim] move among the fixed y_train float32 [n, dim] along their entries idx int32
+    [m, k] in [0, n) with rates q int32 [m, k] in [0, 65536]; k <= 64.  All epochs of the call run in one launch.  Returns
+    the new positions; both inputs are left unchanged.  Splitting the epoch range over several calls changes no bit."""
+    import torch
+
+    require_gpu(y_new, y_train, idx, q)
+    epoch_end = n_epochs if epoch_end is None else epoch_end
+    if y_new.dim() != 2 or y_train.dim() != 2 or y_new.dtype != torch.float32 or y_train.dtype != torch.float32:
+        raise ValueError("y_new float32 [m, dim] and y_train float32 [n, dim] expected")
+    (m, dim), n = y_new.shape, y_train.shape[0]
+    if y_train.shape[1] != dim or not 1 <= dim <= MAX_COMPONENTS:
+        raise ValueError(f"y_new and y_train must share 1 <= dim <= {MAX_COMPONENTS}")
+    if m < 1 or n < 1:
+        raise ValueError("at least one new and one fitted point expected")
+    if idx.dtype != torch.int32 or q.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != m or q.shape != idx.shape:
+        raise ValueError("idx int32 [m, k] and q int32 [m, k] expected")
+    k = idx.shape[1]
+    if not 1 <= k <= MAX_NEIGHBORS:
+        raise ValueError(f"1 <= k <= {MAX_NEIGHBORS} expected ({k} given)")
+    # the kernel trusts the entries: check once here that none points outside y_train
+    if int(idx.min()) < 0 or int(idx.max()) >= n or int(q.min()) < 0 or int(q.max()) > 65536:
+        raise ValueError("idx must lie in [0, n) and q in [0, 65536]")
+    if not 0 <= epoch_begin <= epoch_end <= n_epochs or n_epochs < 1:
+        raise ValueError("0 <= epoch_begin <= epoch_end <= n_epochs expected")
+    if not (a > 0 and b > 0 and gamma >= 0 and learning_rate >= 0 and 0 <= int(negative_sample_rate) <= 64):
+        raise ValueError("a, b > 0, gamma, learning_rate >= 0 and 0 <= negative_sample_rate <= 64 expected")
+    out = torch.empty_like(y_new)
+    check(_lib.load().wm_umap_transform_layout(ptr(y_new), ptr(out), ptr(y_train), ptr(idx), ptr(q), m, n, k, dim, float(a),
+                                               float(b), float(gamma), float(learning_rate), int(seed) & _MASK32,
+                                               int(epoch_begin), int(epoch_end), int(n_epochs), int(negative_sample_rate),
+                                               stream_ptr()), "wm_umap_transform_layout")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ DensMAP steps
@@ -352,8 +486,9 @@ def optimize_layout_densmap(y, indptr, indices, q, data, R, a: float, b: float, 
         raise ValueError("at least 2 vertices expected")
     if data.dtype != torch.float32 or R.dtype != torch.float32 or data.shape != indices.shape or R.shape != (n,):
         raise ValueError("data float32 [nnz] and R float32 [n] expected")
-    if data.numel() and not bool((torch.isfinite(data) & (data > 0)).all()):
-        raise ValueError("data must be positive and finite")
+    # (an explicit zero of a label-intersected graph has rate 0: it is never sampled and never live, so never divided by)
+    if data.numel() and not bool((torch.isfinite(data) & ((data > 0) | ((data == 0) & (q == 0)))).all()):
+        raise ValueError("data must be positive and finite (0 only where the rate is 0)")
     if not bool(torch.isfinite(R).all()):
         raise ValueError("R must be finite")
     if not (dens_lambda >= 0 and 0 <= dens_frac <= 1 and dens_var_shift >= 0):
@@ -394,6 +529,7 @@ def _spectral_init(graph: CSR, dim: int):
     import scipy.sparse.linalg
 
     g = graph.to_scipy().astype(np.float64)
+    g.eliminate_zeros()  # (the explicit zeros a label intersection leaves are no edges)
     n = g.shape[0]
     if n <= dim + 1 or scipy.sparse.csgraph.connected_components(g, directed=False)[0] != 1:
         return None
@@ -490,16 +626,20 @@ class UMAP:
 
     def _checked(self, x, y):
         if y is not None:
-            raise NotImplementedError("y= (semi-supervised UMAP) is not implemented")
+            raise NotImplementedError(f"y= (semi-supervised UMAP) is not implemented by this class: use manifold.Inductive{type(self).__name__}")
         x = _prep(x)
         if x.shape[0] < 2:
             raise ValueError("UMAP needs at least 2 rows")
         return x
 
+    def _target_graph(self, graph: CSR) -> CSR:
+        """The graph the layout sees: the fuzzy simplicial set itself (the Inductive classes intersect it with y)."""
+        return graph
+
     def fit(self, x, y=None) -> "UMAP":
         x = self._checked(x, y)
         n = x.shape[0]
-        graph = fuzzy_simplicial_set(x, min(self.n_neighbors, n), self.metric)
+        graph = self._target_graph(fuzzy_simplicial_set(x, min(self.n_neighbors, n), self.metric))
         n_epochs = self.n_epochs if self.n_epochs is not None else (500 if n <= 10000 else 200)
         self.graph_ = graph
         self.embedding_ = optimize_layout(self._initial(x, graph), graph.indptr, graph.indices, sample_rates(graph.data),
@@ -512,7 +652,8 @@ class UMAP:
         return self.fit(x, y).embedding_
 
     def transform(self, x):
-        raise NotImplementedError("transform of new rows is not implemented (fit_transform embeds the fitted rows)")
+        raise NotImplementedError("transform of new rows is not implemented by this class (fit_transform embeds the fitted "
+                                  f"rows): use manifold.Inductive{type(self).__name__}")
 
 
 class DensMAP(UMAP):
@@ -538,6 +679,7 @@ class DensMAP(UMAP):
         x = self._checked(x, y)
         n = x.shape[0]
         graph, dists = fuzzy_simplicial_set(x, min(self.n_neighbors, n), self.metric, return_dists=True)
+        graph = self._target_graph(graph)  # (the pattern is kept: dists stay aligned)
         n_epochs = self.default_epochs(n)
         q = sample_rates(graph.data)
         self.graph_ = graph
@@ -549,3 +691,108 @@ class DensMAP(UMAP):
             dens_var_shift=self.dens_var_shift)
         self.rad_emb_ = embedding_radii(self.embedding_, graph.indptr, graph.indices, q, self.a_, self.b_, n_epochs)[0]
         return self
+
+
+# ------------------------------------------------------------------------------------------------ y= and transform
+
+
+def _checked_labels(y, n: int):
+    """y= of a fit as an int32 [n] tensor where it lives: a numpy array or a tensor (host or device) of integer values
+    >= -1."""
+    import torch
+
+    t = y.detach() if isinstance(y, torch.Tensor) else None
+    if t is None:
+        arr = np.asarray(y)
+        if arr.dtype.kind not in "iu":
+            raise ValueError(f"y must hold integers (-1: unknown), not {arr.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(arr.astype(np.int64)))
+    elif t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"y must hold integers (-1: unknown), not {t.dtype}")
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError(f"y must have one label per row ([{n}]), not {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    if n and (int(t.min()) < -1 or int(t.max()) > 2 ** 31 - 1):
+        raise ValueError("labels must be >= -1 (-1: unknown) and fit int32")
+    return t.to(torch.int32).contiguous()
+
+
+class _Inductive:
+    """What `InductiveUMAP` and `InductiveDensMAP` add to their parents (mixed in before them): the target arguments,
+    the label intersection of the graph that the parents' `fit(x, y)` lays out, and `transform`."""
+
+    def __init__(self, *args, target_weight: float = 0.5, target_metric: str = "categorical", transform_seed: int = 42, **kwargs):
+        super().__init__(*args, **kwargs)
+        if target_metric != "categorical":
+            raise NotImplementedError(f"target_metric {target_metric!r} is not implemented (available: 'categorical')")
+        if not 0.0 <= float(target_weight) <= 1.0:
+            raise ValueError("0 <= target_weight <= 1 required")
+        self.target_weight, self.target_metric, self.transform_seed = float(target_weight), target_metric, int(transform_seed)
+        self._labels = self._train = None
+
+    def _checked(self, x, y):
+        # labels first: a bad y is a ValueError whatever x is; an x that is no 2-D device tensor is refused right after
+        labels = _checked_labels(y, x.shape[0]) if y is not None and getattr(x, "ndim", 0) == 2 else None
+        x = super()._checked(x, None)
+        self._labels = None if labels is None else labels.to(x.device)
+        self._train = x
+        return x
+
+    def _target_graph(self, graph: CSR) -> CSR:
+        if self._labels is None:
+            return graph
+        return label_intersect(graph, self._labels, far_distance(self.target_weight))
+
+    def transform_epochs(self, m: int) -> int:
+        if self.n_epochs is not None:
+            return max(1, self.n_epochs // 3)
+        return 100 if m <= 10000 else 30
+
+    def transform_graph(self, x):
+        """(idx int32 [m, k], weights float32 [m, k]) of the new rows x among the fitted rows."""
+        if self.embedding_ is None or self._train is None:
+            raise ValueError("transform needs a fitted model: call fit first")
+        if not hasattr(x, "is_cuda") or not x.is_cuda:
+            raise ValueError("transform needs a device tensor")
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError("expected [n_samples >= 1, n_features]")
+        x = _prep(x)
+        if x.shape[1] != self._train.shape[1]:
+            raise ValueError(f"x has {x.shape[1]} (padded) features, the model was fitted on {self._train.shape[1]}")
+        dist, idx = knn_query(x, self._train, min(self.n_neighbors, self._train.shape[0]), self.metric)
+        return idx, smooth_knn_query(dist)[1]
+
+    def transform_init(self, idx, w):
+        """umap-learn 0.5.3's init_transform: sum_j w_j Y_j / sum_j w_j, in double, rounded once (the plain mean of the
+        neighbours where every weight underflowed to 0)."""
+        import torch
+
+        wd = w.double()
+        tot = wd.sum(dim=1, keepdim=True)
+        wd = torch.where(tot > 0, wd / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.full_like(wd, 1.0 / w.shape[1]))
+        return (wd.unsqueeze(2) * self.embedding_.double()[idx.long()]).sum(dim=1).float().contiguous()
+
+    def transform(self, x):
+        """Positions float32 [m, n_components] of new rows x [m, d] (device tensor) in the fitted embedding, which does
+        not move: umap-learn's UMAP.transform (exact kNN among the fitted rows, rho = 0 memberships, weighted-average
+        start, n_epochs // 3 -- or 100, 30 above 10 000 rows -- layout epochs at a quarter of the learning rate with
+        seed `transform_seed`).  Two calls give the same bits."""
+        idx, w = self.transform_graph(x)
+        return optimize_transform(self.transform_init(idx, w), self.embedding_, idx, sample_rates(w), self.a_, self.b_,
+                                  self.transform_epochs(idx.shape[0]), gamma=self.repulsion_strength,
+                                  learning_rate=self.learning_rate, seed=self.transform_seed,
+                                  negative_sample_rate=self.negative_sample_rate)
+
+
+class InductiveUMAP(_Inductive, UMAP):
+    """`UMAP` with `fit(x, y)` and `transform(x)`: `UMAP`'s arguments plus umap-learn's target_weight = 0.5,
+    target_metric = "categorical" and transform_seed = 42.  y: one integer label per row, -1 where unknown (numpy array
+    or tensor); the fuzzy graph is intersected with the labels (`label_intersect`) before the initialisation, so the
+    spectral start and the layout see the intersected graph.  With y=None the fit is `UMAP`'s bit for bit."""
+
+
+class InductiveDensMAP(_Inductive, DensMAP):
+    """`DensMAP` with `fit(x, y)` and `transform(x)` (see `InductiveUMAP`); the graph distances stay aligned with the
+    intersected graph because its pattern is kept.  `transform` places new rows into the DensMAP embedding by the plain
+    transform layout, without a density term: recent umap-learn releases refuse transform for densmap=True, but notebook
+    3.0-Embeddings-inference calls it on such a model, so it is provided."""

@@ -2,7 +2,8 @@
 simplicial set and the layout epochs at the golden 12 449 x 512 embeddings and at a synthetic 172 950 x 512 matrix
 (the size of the reference's full WM-811K dump), on one MI355X.
 
-    python tools/bench_umap.py [--out profiles/umap_bench.md] [--densmap-out FILE] [--reps 5] [--sizes golden synthetic]
+    python tools/bench_umap.py [--out profiles/umap_bench.md] [--densmap-out FILE] [--transform-out FILE] [--reps 5]
+                               [--sizes golden synthetic]
 
 Device events around the Python calls, one warm-up call per shape, then --reps calls: median (min .. max).  The kNN
 pass is set next to wm_core_distance on the same rows and k: both are one all-pairs pass of 3 n^2 d float32 operations
@@ -12,7 +13,12 @@ appended when the parity log of tests/parity_log.py exists (tests/test_gpu_umap.
 
 With --densmap-out the DensMAP density phase (manifold.optimize_layout_densmap, wm_densmap_layout) is timed at the same
 shapes and written to that file: 50 epochs that are all in the phase (dens_frac = 1) next to the same 50 epochs of the
-plain layout from the same positions, per epoch, and the once-per-fit graph radii."""
+plain layout from the same positions, per epoch, and the once-per-fit graph radii.
+
+With --transform-out the semi-supervised fit and the transform of new rows (manifold.InductiveUMAP) are timed on the
+golden rows and written to that file: `fit(x, y)` next to the plain `fit(x)`, and `transform(x)` of all rows split by
+step (kNN query, memberships, start, layout: one launch for all epochs), in 2-D and 50-D.  The cost of an epoch inside
+the launch is the difference to a call of ten times the epochs, which leaves the call's validation out."""
 import argparse
 import json
 import statistics
@@ -126,6 +132,47 @@ def bench_shape(name, x, k, reps, lines, dens_lines=None):
     return rec
 
 
+def bench_transform(name, x, labels, reps, lines):
+    """fit(x, y) next to fit(x), and transform(x) by step, with init="random" (no host eigensolver in the timing)."""
+    n, d = x.shape
+    k = 15
+    y = torch.from_numpy(labels.astype(np.int32)).to(DEV)
+    rec = {"shape": name, "n": n, "d": d, "k": k, "dims": []}
+    t_g, (dist, idx) = timed(lambda: manifold.knn_graph(x, k), reps)
+    t_q, (qd, qi) = timed(lambda: manifold.knn_query(x, x, k), reps)
+    assert torch.equal(dist, qd) and torch.equal(idx, qi)
+    graph = manifold.fuzzy_union(idx, manifold.smooth_knn(dist, idx)[2])
+    t_i, _ = timed(lambda: manifold.label_intersect(graph, y, manifold.far_distance(0.5)), reps)
+    t_w, w = timed(lambda: manifold.smooth_knn_query(qd)[1], reps)
+    lines += [f"## {name}: {n} x {d}, k = {k}, all {n} rows labelled ({int(y.max()) + 1} classes)", "",
+              "| step | time |", "|---|---|",
+              f"| kNN graph (`wm_knn_graph`), for comparison | {fmt(t_g)} |",
+              f"| kNN query of the same rows (`wm_knn_query`; equal to the graph in bits) | {fmt(t_q)} |",
+              f"| memberships of the queries (`wm_umap_smooth_knn_query`) | {fmt(t_w)} |",
+              f"| label intersection of the graph's {int(graph.indices.numel())} entries (`wm_umap_label_intersect`) | {fmt(t_i)} |", ""]
+    rec.update(knn_graph_ms=t_g[0], knn_query_ms=t_q[0], memberships_ms=t_w[0], label_intersect_ms=t_i[0])
+    lines += ["| components | `UMAP.fit(x)` | `InductiveUMAP.fit(x, y)` | start (torch, double) | transform layout (`wm_umap_transform_layout`) "
+              "| epochs | per further epoch | `transform(x)` whole |", "|---|---|---|---|---|---|---|---|"]
+    for dim in (2, 50):
+        kw = dict(n_neighbors=k, n_components=dim, init="random", random_state=0)
+        t_plain, _ = timed(lambda: manifold.UMAP(**kw).fit(x), max(2, reps // 2))
+        t_sup, model = timed(lambda: manifold.InductiveUMAP(**kw).fit(x, y), max(2, reps // 2))
+        t_s, start = timed(lambda: model.transform_init(qi, w), reps)
+        q = manifold.sample_rates(w)
+        epochs = model.transform_epochs(n)
+        t_l, _ = timed(lambda: manifold.optimize_transform(start, model.embedding_, qi, q, model.a_, model.b_, epochs), reps)
+        # the cost of an epoch inside the launch, without the call's validation: ten times the epochs against the above
+        t_x, _ = timed(lambda: manifold.optimize_transform(start, model.embedding_, qi, q, model.a_, model.b_, 10 * epochs), reps)
+        per_epoch = (t_x[0] - t_l[0]) / (9 * epochs)
+        t_t, _ = timed(lambda: model.transform(x), reps)
+        lines.append(f"| {dim} | {fmt(t_plain)} | {fmt(t_sup)} | {fmt(t_s)} | {fmt(t_l)} | {epochs} | {per_epoch * 1e3:.1f} us | {fmt(t_t)} |")
+        rec["dims"].append({"dim": dim, "fit_ms": t_plain[0], "fit_y_ms": t_sup[0], "start_ms": t_s[0], "layout_ms": t_l[0],
+                            "epochs": epochs, "per_further_epoch_us": per_epoch * 1e3, "transform_ms": t_t[0]})
+    lines.append("")
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def parity_section(lines):
     sys.path.insert(0, str(ROOT / "tests"))
     from parity_log import _PATH  # (relative to the directory the tests ran from: the repository root)
@@ -157,6 +204,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=str(ROOT / "profiles" / "umap_bench.md"))
     ap.add_argument("--densmap-out", default="", help="also time the DensMAP density phase and write it to this file")
+    ap.add_argument("--transform-out", default="", help="also time fit(x, y) and transform(x) on the golden rows and write them to this file")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", nargs="+", default=["golden", "synthetic"], choices=["golden", "synthetic"])
     a = ap.parse_args(argv)
@@ -178,8 +226,20 @@ def main(argv=None):
                       "plain epoch plus one gather pass over all live entries in double, three small reduction launches and the",
                       "density term's 16-byte gather per sampled entry.", ""]
     if "golden" in a.sizes:
-        emb = np.load(ROOT / "tests" / "golden" / "simsiam_preds_subset.npz")["embeddings"].astype(np.float32)
+        z = np.load(ROOT / "tests" / "golden" / "simsiam_preds_subset.npz")
+        emb = z["embeddings"].astype(np.float32)
         x = StandardScaler().fit_transform(torch.from_numpy(emb).to(DEV))
+        if a.transform_out:
+            tlines = ["# Semi-supervised fit and transform of new rows", "",
+                      "Scope: `csrc/cluster.hip` (`wm_knn_query`), `csrc/umap.hip` (`wm_umap_label_intersect`, `wm_umap_smooth_knn_query`,",
+                      "`wm_umap_transform_layout`), `manifold.py` (`InductiveUMAP`).  One MI355X.  Written by `tools/bench_umap.py",
+                      "--transform-out`: device events around the Python call (validation and allocation included), one warm-up call,",
+                      "then the median (min .. max) of the repeats; fits with `init=\"random\"`, default epochs.", ""]
+            recs.append(bench_transform("golden SimSiam embeddings, standardised", x, np.asarray(z["labels"]), a.reps, tlines))
+            tout = Path(a.transform_out)
+            tout.parent.mkdir(parents=True, exist_ok=True)
+            tout.write_text("\n".join(tlines) + "\n")
+            print(f"wrote {tout}")
         recs.append(bench_shape("golden SimSiam embeddings, standardised", x, 15, a.reps, lines, dens_lines))
     if "synthetic" in a.sizes:
         recs.append(bench_shape("synthetic mixture of 38 Gaussians", synthetic(172950, 512, 0), 15, max(2, a.reps // 2), lines,
