@@ -784,6 +784,16 @@ int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, i
 size_t wm_knn_query_workspace_bytes(int m, int n, int d, int k);
 int wm_knn_query(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
                  void* workspace, size_t workspace_bytes, void* stream);
+/* The fitted row nearest to a new row in mutual reachability (HDBSCAN's prediction for new rows): for every row i of
+ * xq float32 [m][d] with core distance core_q[i], over all rows c of x float32 [n][d] with core distances core[c],
+ * w_ic = max(core_q[i], core[c], dist(i, c) * inv_alpha) under the same distance function; the result is the c that
+ * minimises (w_ic, dist(i, c), c) lexicographically: out_w, out_dist float32 [m] and out_j int32 [m] in [0, n).  An exact
+ * search over all n rows.  m, n >= 1, inv_alpha > 0; xq, x and the workspace 16-byte aligned.  No atomics: two calls give
+ * the same bits. */
+size_t wm_mreach_query_workspace_bytes(int m, int n, int d);
+int wm_mreach_query(const float* xq, const float* core_q, int m, const float* x, const float* core, int n, int d, int metric,
+                    float inv_alpha, float* out_w, float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas

@@ -6,6 +6,7 @@ notebooks/3.1-Embeddings-clustering.ipynb and 3.2-Embeddings-SSL-categories.ipyn
     python scripts/embedding_clustering_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
                                                [--trials 30] [--design random|grid] [--seed 0] [--rows N]
                                                [--metrics euclidean manhattan] [--no-scale] [--out DIR]
+                                               [--holdout N]
 
 What the notebooks do, and where it is here:
   StandardScaler().fit_transform(embeddings)              -> retrieval.StandardScaler (skipped with --no-scale)
@@ -29,6 +30,12 @@ no kernel and are refused.
 
 Outputs under --out: trials.csv (parameters, n_clusters, n_noise, the four scores), pareto.csv, labels.npy (the
 chosen trial: the Pareto row with the best silhouette), summary.json.
+
+--holdout N keeps the last N rows out of the scaler and the sweep and asks the chosen trial's model about them
+(cluster.approximate_predict / approximate_predict_scores: which cluster, how surely, how anomalous):
+holdout_labels.npy, holdout_probabilities.npy, holdout_outlier_scores.npy, and in summary.json `holdout`,
+`holdout_noise` and `holdout_homogeneity` (truth against the predicted label over the held-out rows not labelled noise;
+null when there are none).
 """
 from __future__ import annotations
 
@@ -139,6 +146,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--no-scale", action="store_true")
     ap.add_argument("--out", default="clustering_out")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--holdout", type=int, default=0, help="keep the last N rows out of the sweep and predict them")
     a = ap.parse_args(argv)
 
     import torch
@@ -151,9 +159,17 @@ def main(argv=None) -> dict:
     emb, truth = load_embeddings(a.embeddings)
     if a.rows:
         emb, truth = emb[:a.rows], truth[:a.rows]
-    x = torch.from_numpy(emb).to(a.device)
+    if not 0 <= a.holdout < emb.shape[0]:
+        raise ValueError(f"--holdout ({a.holdout}) must be in [0, rows = {emb.shape[0]})")
+    n_fit = emb.shape[0] - a.holdout
+    x, x_hold = torch.from_numpy(emb[:n_fit]).to(a.device), None
+    if a.holdout:
+        x_hold, truth_hold, truth = torch.from_numpy(emb[n_fit:]).to(a.device), truth[n_fit:], truth[:n_fit]
     if not a.no_scale:
-        x = StandardScaler().fit_transform(x)
+        scaler = StandardScaler()
+        x = scaler.fit_transform(x)
+        if a.holdout:
+            x_hold = scaler.transform(x_hold)
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
 
@@ -164,7 +180,7 @@ def main(argv=None) -> dict:
         key = (p["metric"], p["min_samples"])
         if key not in trees:
             trees[key] = cluster.HDBSCAN(min_cluster_size=p["min_cluster_size"], min_samples=p["min_samples"],
-                                         metric=p["metric"]).fit(x)
+                                         metric=p["metric"], prediction_data=a.holdout > 0).fit(x)
         model = trees[key].refit(min_cluster_size=p["min_cluster_size"],
                                  cluster_selection_epsilon=p["cluster_selection_epsilon"])
         labels = model.labels_.copy()
@@ -185,6 +201,8 @@ def main(argv=None) -> dict:
     chosen = max(front, key=lambda i: rows[i]["silhouette"]) if front else None
     summary = {"n": int(x.shape[0]), "d": int(x.shape[1]), "trials": len(rows), "n_trees": len(trees),
                "sweep_seconds": wall, "pareto": front, "chosen": chosen}
+    if a.holdout:
+        summary.update(holdout=int(a.holdout), holdout_noise=None, holdout_homogeneity=None)  # (filled for a chosen trial)
     if chosen is not None:
         labels = all_labels[chosen]
         np.save(out / "labels.npy", labels)
@@ -195,6 +213,20 @@ def main(argv=None) -> dict:
         for c, (m, dr, ir) in enumerate(zip(members, dist.cpu().tolist(), idx.cpu().tolist())):
             near = [(j, round(dd, 4), int(truth[j])) for j, dd in zip(ir, dr) if j != m][:5]
             print(f"cluster {c}: member {m} (failure code {int(truth[m])}); nearest (row, L2, failure code): {near}")
+        if a.holdout:
+            p = trials[chosen]
+            model = trees[(p["metric"], p["min_samples"])].refit(min_cluster_size=p["min_cluster_size"],
+                                                                 cluster_selection_epsilon=p["cluster_selection_epsilon"])
+            h_labels, h_prob = cluster.approximate_predict(model, x_hold)
+            h_scores = cluster.approximate_predict_scores(model, x_hold)
+            np.save(out / "holdout_labels.npy", h_labels)
+            np.save(out / "holdout_probabilities.npy", h_prob)
+            np.save(out / "holdout_outlier_scores.npy", h_scores)
+            keep = h_labels != -1
+            summary.update(holdout_noise=int((~keep).sum()),
+                           holdout_homogeneity=cluster.homogeneity_score(truth_hold[keep], h_labels[keep]) if keep.any() else None)
+            print(f"held-out rows: {int(keep.sum())} of {a.holdout} assigned to a cluster, homogeneity "
+                  f"{summary['holdout_homogeneity']}")
     (out / "summary.json").write_text(json.dumps(summary, indent=1))
     print(f"{len(rows)} trials on {x.shape[0]} x {x.shape[1]} in {wall:.2f} s with {len(trees)} spanning trees; "
           f"{len(front)} Pareto-optimal rows -> {out}")

@@ -18,6 +18,11 @@ Semantics follow `sklearn.cluster.HDBSCAN`: `min_samples` counts the point itsel
 `min_samples`-th smallest distance with the zero self-distance as the first), which is one neighbour fewer than the
 generic path of the `hdbscan` package uses for the same number.  `alpha` divides the pairwise distance inside the
 mutual reachability, max(core_i, core_j, dist_ij / alpha), with the core distances unscaled.
+
+New rows (`HDBSCAN(prediction_data=True)`, `approximate_predict`, `approximate_predict_scores`): one more all-pairs
+pass (wm_mreach_query) finds, for every new row, the fitted row nearest in mutual reachability; the walk from that
+row through the condensed tree to a label, a membership strength and a GLOSH outlier score is host code
+(`assign_from_tree`), as is `outlier_scores_` of the fitted rows (`glosh`).
 """
 from __future__ import annotations
 
@@ -123,13 +128,18 @@ def mutual_reachability_mst(x, min_samples: int, metric: str = "euclidean", alph
     the host takes the per-component minimum under the total order (w, min(i, j), max(i, j)) -- which the lowest-j
     rule agrees with, and under which no round can close a cycle since an edge has the same weight bits from both
     ends -- merges, and renumbers the components.  At most ceil(log2 n) rounds."""
-    import torch
-
     if not alpha > 0:
         raise ValueError("alpha must be positive")
     x = _prep(x)
+    out = _boruvka(x, core_distances(x, min_samples, metric), metric, alpha)
+    return out if return_rounds else out[:3]
+
+
+def _boruvka(x, core, metric: str, alpha: float):
+    """mutual_reachability_mst's rounds on a prepared matrix and its core distances: (u, v, w, rounds)."""
+    import torch
+
     n = x.shape[0]
-    core = core_distances(x, min_samples, metric)
     parent = np.arange(n, dtype=np.int64)
     eu, ev, ew = [], [], []
     n_comp, rounds = n, 0
@@ -164,8 +174,7 @@ def mutual_reachability_mst(x, min_samples: int, metric: str = "euclidean", alph
         n_comp = int(np.unique(comp).size)
     u, v, wt = np.asarray(eu, dtype=np.int64), np.asarray(ev, dtype=np.int64), np.asarray(ew, dtype=np.float64)
     order = np.lexsort((v, u, wt))
-    out = (u[order], v[order], wt[order])
-    return out + (rounds,) if return_rounds else out
+    return u[order], v[order], wt[order], rounds
 
 
 # ------------------------------------------------------------------------------------------------ host: tree -> labels
@@ -244,15 +253,17 @@ def _condense(left, right, value, size, n, min_cluster_size):
 
 
 def labels_from_mst(u, v, w, n: int, min_cluster_size: int, cluster_selection_epsilon: float = 0.0,
-                    cluster_selection_method: str = "eom", allow_single_cluster: bool = False
-                    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                    cluster_selection_method: str = "eom", allow_single_cluster: bool = False,
+                    return_selected: bool = False) -> Tuple[np.ndarray, ...]:
     """Flat HDBSCAN clustering from the n - 1 spanning-tree edges (u, v, w), sorted by weight: single-linkage tree,
     condensed tree, stabilities, excess-of-mass or leaf selection, epsilon merge.  Pure numpy / Python on float64.
 
     Returns (labels int64 [n] with -1 for noise, probabilities float64 [n], condensed_tree): the condensed tree is
     a structured array (parent, child, lambda_val, child_size) in sklearn's row order.  Semantics are
     sklearn.cluster.HDBSCAN's (_tree.pyx) with one deliberate difference in `probabilities`: a cluster's death is
-    the largest lambda over ALL its condensed rows, where sklearn takes the last contiguous run of them."""
+    the largest lambda over ALL its condensed rows, where sklearn takes the last contiguous run of them.  With
+    `return_selected` a fourth value follows: the condensed-tree ids of the selected clusters, sorted, so that a
+    cluster's position is its label."""
     u, v = np.asarray(u, dtype=np.int64), np.asarray(v, dtype=np.int64)
     w = np.asarray(w, dtype=np.float64)
     n, mcs = int(n), int(min_cluster_size)
@@ -386,7 +397,115 @@ def labels_from_mst(u, v, w, n: int, min_cluster_size: int, cluster_selection_ep
     with np.errstate(invalid="ignore", divide="ignore"):
         val = np.where((death == 0.0) | np.isinf(lam_h), 1.0, np.minimum(lam_h, death) / death)
     prob[p_child[has]] = val
+    if return_selected:
+        return labels, prob, tree, np.asarray(clusters, dtype=np.int64)
     return labels, prob, tree
+
+
+# ------------------------------------------------------------------------------------------------ host: outliers, new rows
+
+
+def _tree_tables(tree, n: int):
+    """Per-node tables of a condensed tree: (n_nodes, cluster parent [n_nodes] (the root is its own), birth lambda
+    [n_nodes] (0 at the root), death [n_nodes] = the largest lambda over the cluster's own rows, D [n_nodes] = the
+    death propagated upwards over cluster children, per point its parent [n] and its lambda [n])."""
+    parent, child, lam, csize = tree["parent"], tree["child"], tree["lambda_val"], tree["child_size"]
+    n_nodes = int(parent.max()) + 1
+    is_cl = csize > 1
+    cl_parent = np.arange(n_nodes, dtype=np.int64)
+    cl_parent[child[is_cl]] = parent[is_cl]
+    birth = np.zeros(n_nodes)
+    birth[child[is_cl]] = lam[is_cl]
+    death = np.zeros(n_nodes)
+    np.maximum.at(death, parent, lam)
+    spread = death.copy()
+    for c in range(n_nodes - 1, n, -1):  # (ids grow downwards: every child is visited before its parent)
+        spread[cl_parent[c]] = max(spread[cl_parent[c]], spread[c])
+    pt_parent, pt_lam = np.full(n, n, dtype=np.int64), np.zeros(n)
+    pt_parent[child[~is_cl]], pt_lam[child[~is_cl]] = parent[~is_cl], lam[~is_cl]
+    return n_nodes, cl_parent, birth, death, spread, pt_parent, pt_lam
+
+
+def _glosh_ratio(spread, lam):
+    """(spread - lam) / spread, clipped below at 0: 0 where spread == 0 or lam is not finite, and the limit 1 where
+    only spread is infinite (a cluster that holds exact duplicates)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        val = np.maximum((spread - lam) / spread, 0.0)
+    val = np.where(np.isinf(spread), 1.0, val)
+    return np.where((spread == 0.0) | ~np.isfinite(lam), 0.0, val)
+
+
+def glosh(condensed_tree, n: int) -> np.ndarray:
+    """GLOSH outlier scores of the n fitted rows (the `hdbscan` package's `outlier_scores_`), float64 [n] in [0, 1].
+    D[c] is the largest lambda among cluster c's own condensed rows, propagated upwards so that a parent's D is at
+    least each cluster child's; a point that leaves cluster P at lambda l scores (D[P] - l) / D[P], and 0 where
+    D[P] == 0 or l is not finite."""
+    n = int(n)
+    _, _, _, _, spread, pt_parent, pt_lam = _tree_tables(condensed_tree, n)
+    return _glosh_ratio(spread[pt_parent], pt_lam)
+
+
+def assign_from_tree(condensed_tree, n: int, selected, neighbor, weight, cluster_selection_epsilon: float = 0.0,
+                     allow_single_cluster: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Labels, membership strengths and outlier scores of new rows from the fitted condensed tree: (labels int64 [m],
+    probabilities float64 [m], outlier_scores float64 [m]).  Pure numpy on float64.
+
+    `selected`: the sorted condensed-tree ids of the flat clustering (labels_from_mst(..., return_selected=True));
+    `neighbor` [m]: per new row the fitted row nearest in mutual reachability; `weight` [m]: that mutual
+    reachability.  Per row, with lam = 1 / weight (inf at weight 0) and (P, l_nb) the neighbour's condensed row: the
+    row joins C = P when l_nb <= lam (the neighbour has left P before the row would), otherwise the first cluster
+    on the way up from P that was born before lam (or the root).  The label is that of S, the nearest selected
+    cluster on the way up from C, C included; none: -1 with probability 0.  Where the root itself is the selected
+    cluster (allow_single_cluster) a row that ends at it belongs when lam reaches the threshold of labels_from_mst's
+    branch for that case: 1 / epsilon, or without an epsilon the largest lambda among the root's own rows.  The
+    probability is min(lam, death[S]) / death[S] with labels_from_mst's death, and 1 where death[S] == 0 or lam is
+    infinite; the outlier score is max(0, (D[C] - lam) / D[C]) with glosh's D, and 0 where D[C] == 0 or lam is
+    infinite."""
+    n = int(n)
+    selected = np.asarray(selected, dtype=np.int64)
+    neighbor = np.asarray(neighbor, dtype=np.int64)
+    weight = np.asarray(weight, dtype=np.float64)
+    if neighbor.ndim != 1 or weight.shape != neighbor.shape:
+        raise ValueError("neighbor [m] and weight [m] expected")
+    if neighbor.size and (neighbor.min() < 0 or neighbor.max() >= n):
+        raise ValueError("neighbor must lie in [0, n)")
+    if np.isnan(weight).any() or (weight < 0).any():
+        raise ValueError("weight must not be negative")
+    if (np.diff(selected) <= 0).any():
+        raise ValueError("selected must be sorted condensed-tree ids")
+    eps = float(cluster_selection_epsilon)
+    n_nodes, cl_parent, birth, death, spread, pt_parent, pt_lam = _tree_tables(condensed_tree, n)
+    root = n
+    if selected.size and (selected.min() < root or selected.max() >= n_nodes):
+        raise ValueError("selected must hold cluster ids of the condensed tree")
+    with np.errstate(divide="ignore"):
+        lam = 1.0 / weight
+    # ---- C: the cluster the row would fall out of
+    at = pt_parent[neighbor]
+    climb = pt_lam[neighbor] > lam
+    while True:
+        move = climb & (at != root) & (birth[at] >= lam)
+        if not move.any():
+            break
+        at = np.where(move, cl_parent[at], at)
+    # ---- S: the nearest selected cluster from C upwards (the root stands for "none", as in labels_from_mst)
+    label_at = np.full(n_nodes, -1, dtype=np.int64)
+    label_at[selected] = np.arange(selected.size)
+    top = np.full(n_nodes, root, dtype=np.int64)
+    for c in range(root + 1, n_nodes):
+        top[c] = c if label_at[c] >= 0 else top[cl_parent[c]]
+    s = top[at]
+    labels = np.where(s != root, label_at[s], -1)
+    if selected.size == 1 and selected[0] == root and allow_single_cluster:
+        tree = condensed_tree
+        threshold = 1.0 / eps if eps != 0.0 else float(tree["lambda_val"][tree["parent"] == root].max())
+        labels = np.where(lam >= threshold, 0, -1)  # (every walk ends at the root here: nothing else is selected)
+    has = labels >= 0
+    d_s = death[s]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prob = np.where((d_s == 0.0) | np.isinf(lam), 1.0, np.minimum(lam, d_s) / d_s)
+    prob = np.where(has, prob, 0.0)
+    return labels.astype(np.int64), prob, _glosh_ratio(spread[at], lam)
 
 
 class HDBSCAN:
@@ -394,11 +513,13 @@ class HDBSCAN:
     `condensed_tree_` and `minimum_spanning_tree_` (numpy [n - 1, 3]: u, v, weight; kept whether or not
     `gen_min_span_tree` is set, since `refit` needs it).  `min_samples=None` means `min_cluster_size`.
     `refit(min_cluster_size=..., cluster_selection_epsilon=...)` relabels from the stored tree: the tree depends on
-    (metric, min_samples, alpha) only."""
+    (metric, min_samples, alpha) only.  `fit` and `refit` also set `selected_clusters_` (the sorted condensed-tree ids
+    of the clusters: position = label) and `outlier_scores_` (`glosh`).  With `prediction_data=True`, `fit` keeps the
+    prepared device matrix and the device core distances, which `approximate_predict` needs."""
 
     def __init__(self, min_cluster_size: int = 5, min_samples: Optional[int] = None, cluster_selection_epsilon: float = 0.0,
                  metric: str = "euclidean", alpha: float = 1.0, cluster_selection_method: str = "eom",
-                 allow_single_cluster: bool = False, gen_min_span_tree: bool = False):
+                 allow_single_cluster: bool = False, gen_min_span_tree: bool = False, prediction_data: bool = False):
         metric_code(metric)
         if cluster_selection_method not in ("eom", "leaf"):
             raise ValueError("cluster_selection_method must be 'eom' or 'leaf'")
@@ -411,16 +532,20 @@ class HDBSCAN:
         self.min_cluster_size, self.min_samples = int(min_cluster_size), min_samples
         self.cluster_selection_epsilon, self.metric, self.alpha = float(cluster_selection_epsilon), metric, float(alpha)
         self.cluster_selection_method, self.allow_single_cluster = cluster_selection_method, bool(allow_single_cluster)
-        self.gen_min_span_tree = bool(gen_min_span_tree)
+        self.gen_min_span_tree, self.prediction_data = bool(gen_min_span_tree), bool(prediction_data)
         self.labels_ = self.probabilities_ = self.condensed_tree_ = self.minimum_spanning_tree_ = None
-        self._n = None
+        self.selected_clusters_ = self.outlier_scores_ = None
+        self._n = self._k = self._train = self._core = None
 
     def fit(self, x) -> "HDBSCAN":
         k = self.min_cluster_size if self.min_samples is None else int(self.min_samples)
         if k > x.shape[0]:
             raise ValueError(f"min_samples ({k}) must be at most the number of samples ({x.shape[0]})")
-        u, v, w = mutual_reachability_mst(x, k, self.metric, self.alpha)
-        self._n = int(x.shape[0])
+        xp = _prep(x)
+        core = core_distances(xp, k, self.metric)
+        u, v, w, _ = _boruvka(xp, core, self.metric, self.alpha)
+        self._n, self._k = int(x.shape[0]), k
+        self._train, self._core = (xp, core) if self.prediction_data else (None, None)
         self.minimum_spanning_tree_ = np.stack([u.astype(np.float64), v.astype(np.float64), w], axis=1)
         return self._label()
 
@@ -435,13 +560,103 @@ class HDBSCAN:
 
     def _label(self) -> "HDBSCAN":
         t = self.minimum_spanning_tree_
-        self.labels_, self.probabilities_, self.condensed_tree_ = labels_from_mst(
+        self.labels_, self.probabilities_, self.condensed_tree_, self.selected_clusters_ = labels_from_mst(
             t[:, 0].astype(np.int64), t[:, 1].astype(np.int64), t[:, 2], self._n, self.min_cluster_size,
-            self.cluster_selection_epsilon, self.cluster_selection_method, self.allow_single_cluster)
+            self.cluster_selection_epsilon, self.cluster_selection_method, self.allow_single_cluster, return_selected=True)
+        self.outlier_scores_ = glosh(self.condensed_tree_, self._n)
         return self
 
     def fit_predict(self, x) -> np.ndarray:
         return self.fit(x).labels_
+
+
+# ------------------------------------------------------------------------------------------------ GPU: new rows
+
+
+def query_core_distances(xq, x, min_samples: int, metric: str = "euclidean"):
+    """Core distances of new rows xq [m, d] against the fitted rows x [n, d] (device tensors) under this module's
+    convention, the row counting itself: the `min_samples`-th smallest of {0} and the distances to the fitted rows,
+    that is the distance to the (min_samples - 1)-th nearest fitted row (wm_knn_query with min_samples - 1
+    neighbours).  float32 [m] on the device; min_samples == 1 gives zeros and launches nothing."""
+    import torch
+
+    from .manifold import knn_query  # (manifold imports this module)
+
+    metric_code(metric)
+    xq, x = _prep(xq), _prep(x)
+    m, n = xq.shape[0], x.shape[0]
+    k = int(min_samples) - 1
+    if not 0 <= k <= n:
+        raise ValueError(f"min_samples ({k + 1}) must be in [1, n_samples + 1 = {n + 1}]")
+    if k == 0 or m == 0:
+        return torch.zeros(m, dtype=torch.float32, device=xq.device)
+    return knn_query(xq, x, k, metric)[0][:, k - 1].contiguous()
+
+
+def mreach_query(xq, core_q, x, core, metric: str = "euclidean", alpha: float = 1.0):
+    """Per row of xq [m, d] the fitted row of x [n, d] nearest in mutual reachability
+    max(core_q[i], core[c], dist_ic / alpha), equal weights resolved by the smaller distance and then the lower
+    index: (weight float32 [m], dist float32 [m], j int32 [m]) on the device (wm_mreach_query; an exact search over
+    all fitted rows)."""
+    import torch
+
+    code = metric_code(metric)
+    if not alpha > 0:
+        raise ValueError("alpha must be positive")
+    xq, x = _prep(xq), _prep(x)
+    require_gpu(core_q, core)
+    (m, d), n = xq.shape, x.shape[0]
+    if x.shape[1] != d:
+        raise ValueError(f"the new rows have {d} features (padded), the fitted rows {x.shape[1]}")
+    if core_q.shape != (m,) or core.shape != (n,) or core_q.dtype != torch.float32 or core.dtype != torch.float32:
+        raise ValueError("core_q float32 [m] and core float32 [n] expected")
+    if m < 1 or n < 1:
+        raise ValueError("mreach_query needs at least one row on either side")
+    lib = _lib.load()
+    need = lib.wm_mreach_query_workspace_bytes(m, n, d)
+    if need == 0:
+        raise ValueError(f"mreach_query: unsupported sizes m={m} n={n} d={d}")
+    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    w = torch.empty(m, dtype=torch.float32, device=xq.device)
+    dist = torch.empty(m, dtype=torch.float32, device=xq.device)
+    j = torch.empty(m, dtype=torch.int32, device=xq.device)
+    check(lib.wm_mreach_query(ptr(xq), ptr(core_q), m, ptr(x), ptr(core), n, d, code, 1.0 / float(alpha), ptr(w), ptr(dist),
+                              ptr(j), ptr(ws), need, stream_ptr()), "wm_mreach_query")
+    return w, dist, j
+
+
+def _predict(model: "HDBSCAN", rows):
+    if model.minimum_spanning_tree_ is None:
+        raise RuntimeError("HDBSCAN prediction before fit")
+    if model._train is None or model._core is None:
+        raise ValueError("this model keeps no prediction data: construct it with HDBSCAN(..., prediction_data=True)")
+    xq = _prep(rows)
+    if xq.shape[1] != model._train.shape[1]:
+        raise ValueError(f"rows have {rows.shape[1]} features, the model was fitted on {model._train.shape[1]} (after padding)")
+    if xq.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0)
+    core_q = query_core_distances(xq, model._train, model._k, model.metric)
+    w, _, j = mreach_query(xq, core_q, model._train, model._core, model.metric, model.alpha)
+    return assign_from_tree(model.condensed_tree_, model._n, model.selected_clusters_, j.cpu().numpy().astype(np.int64),
+                            w.cpu().numpy().astype(np.float64), model.cluster_selection_epsilon, model.allow_single_cluster)
+
+
+def approximate_predict(model: "HDBSCAN", rows) -> Tuple[np.ndarray, np.ndarray]:
+    """Cluster labels and membership strengths of new rows [m, d] (device tensor with the fitted feature count) under
+    a model fitted with `prediction_data=True`: (labels int64 [m], probabilities float64 [m]), numpy like `labels_`.
+    The fitted clustering does not change.  The name is the `hdbscan` package's; two deliberate differences:
+    the nearest fitted row in mutual reachability is found by an exact search over all fitted rows (wm_mreach_query)
+    where `hdbscan` looks among the 2 * min_samples nearest only; and the core distance of a new row counts the row
+    itself, as `fit` does here (the min_samples-th smallest of zero and the distances to the fitted rows), where
+    `hdbscan` counts one neighbour further.  A model that follows a `refit` predicts under the relabelling."""
+    labels, prob, _ = _predict(model, rows)
+    return labels, prob
+
+
+def approximate_predict_scores(model: "HDBSCAN", rows) -> np.ndarray:
+    """GLOSH outlier scores of new rows under a model fitted with `prediction_data=True`: float64 [m] in [0, 1]
+    (see `assign_from_tree`; the search and the core-distance convention are `approximate_predict`'s)."""
+    return _predict(model, rows)[2]
 
 
 # ------------------------------------------------------------------------------------------------ scores

@@ -8,9 +8,12 @@
 //                         itself among its candidates (the exact kNN graph that manifold.UMAP starts from);
 //   wm_knn_query          the same for the rows of a second matrix against x (the rectangular form that the transform of
 //                         new rows starts from): cl_pairs takes its rows from a row operand of its own (xr, nr), which
-//                         every square mode sets to (x, n).
+//                         every square mode sets to (x, n);
+//   wm_mreach_query       for the rows of a second matrix the row of x nearest in mutual reachability
+//                         max(core_q[i], core[c], dist * inv_alpha), equal weights resolved by the plain distance and then
+//                         by the index (what HDBSCAN's prediction for new rows starts from).
 //
-// ONE distance function serves all four (cl_accum / cl_finish below): the float32 differences a_k - b_k are
+// ONE distance function serves all of them (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
 // correctly rounded square root; Manhattan: acc + |t|).  Not ||a||^2 + ||b||^2 - 2ab: wafer embeddings contain
 // near-duplicates, whose distance that form cancels away.  Two properties the host code and the tests rely on:
@@ -32,9 +35,10 @@
 //   knn       the same with the column index carried next to the distance; a slice scans its columns in ascending
 //             order and a candidate goes behind its equals, so a list is ordered by (distance, index);
 //   min edge  every thread keeps the best (w, j) of its TM rows in registers; one LDS reduction at the end;
+//   query     the same without the component filter and with the plain distance carried between w and j;
 //   sums      distances -> LDS tile; the row's owner adds them in column order, in double, and flushes the running sum
 //             to out[i][label] whenever the label changes (rows sorted by label: once per cluster).
-// Core, knn and min edge split the columns into slices (grid.y) whose partial results a second small kernel combines in a
+// Core, knn, min edge and query split the columns into slices (grid.y) whose partial results a second small kernel combines in a
 // fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
 // atomics anywhere: two calls give the same bits.
 // Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
@@ -49,7 +53,9 @@ constexpr int CL_KC = 32;            // features per staged chunk
 constexpr int CL_LDK = CL_KC + 4;    // LDS row pitch of a staged chunk (floats)
 constexpr int CL_LDD = CL_COLS + 1;  // LDS row pitch of a distance tile (floats)
 constexpr int CL_MAXK = 64;
-constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3;
+constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3, CL_MREACHQ = 4;
+// the modes whose per-row best stays in registers (no distance tile in LDS)
+constexpr bool cl_keeps_best(int mode) { return mode == CL_MINEDGE || mode == CL_MREACHQ; }
 
 template <int METRIC>
 __device__ __forceinline__ float cl_accum(float a, float b, float acc) {
@@ -75,8 +81,11 @@ struct ClArgs {
   const float* core;
   const int* comp;
   float inv_alpha;
-  float* part_w;  // [slices][n]
+  float* part_w;  // [slices][nr]
   int* part_j;
+  // query (with core, inv_alpha, part_w, part_j)
+  const float* core_q;  // [nr]
+  float* part_d;        // [slices][nr]
   // sums
   const int* labels;
   int n_clusters;
@@ -86,7 +95,7 @@ struct ClArgs {
 template <int MODE, int TM>
 constexpr size_t cl_lds_bytes(int kl) {
   size_t f = (size_t)(16 * TM + CL_COLS) * CL_LDK;
-  if (MODE != CL_MINEDGE) f += (size_t)16 * TM * CL_LDD;
+  if (!cl_keeps_best(MODE)) f += (size_t)16 * TM * CL_LDD;
   if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
   if (MODE == CL_KNN) f += (size_t)2 * 16 * TM * kl;
   if (MODE == CL_SUMS) f += CL_COLS;
@@ -113,7 +122,9 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
 
   // ---- per-mode state
   float ci[TM], bw[TM];
-  int cpi[TM], bj[TM];
+  [[maybe_unused]] float bd[TM];  // query: the plain distance of the best
+  [[maybe_unused]] int cpi[TM];
+  int bj[TM];
   int cur = -1;
   double run = 0.0;
   if constexpr (MODE == CL_MINEDGE) {
@@ -123,6 +134,15 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       ci[r] = i < nr ? p.core[i] : 0.f;
       cpi[r] = i < nr ? p.comp[i] : 0;
       bw[r] = INFINITY;
+      bj[r] = -1;
+    }
+  }
+  if constexpr (MODE == CL_MREACHQ) {
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      const int i = i0 + ty + 16 * r;
+      ci[r] = i < nr ? p.core_q[i] : 0.f;
+      bw[r] = bd[r] = INFINITY;
       bj[r] = -1;
     }
   }
@@ -211,6 +231,29 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
           const float w = fmaxf(fmaxf(ci[r], cj[c]), cl_finish<METRIC>(acc[r][c]) * p.inv_alpha);
           if (iv && j < n && cpj[c] != cpi[r] && (w < bw[r] || (w == bw[r] && j < bj[r]))) {
             bw[r] = w;
+            bj[r] = j;
+          }
+        }
+      }
+    } else if constexpr (MODE == CL_MREACHQ) {
+      float cj[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = j0 + tx + 16 * c;
+        cj[c] = j < n ? p.core[j] : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < TM; ++r) {
+        const bool iv = i0 + ty + 16 * r < nr;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int j = j0 + tx + 16 * c;
+          const float dist = cl_finish<METRIC>(acc[r][c]);
+          const float w = fmaxf(fmaxf(ci[r], cj[c]), dist * p.inv_alpha);
+          // (a thread meets its columns in ascending j, so a full tie keeps the earlier one)
+          if (iv && j < n && (w < bw[r] || (w == bw[r] && dist < bd[r]))) {
+            bw[r] = w;
+            bd[r] = dist;
             bj[r] = j;
           }
         }
@@ -307,6 +350,37 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       p.part_j[(size_t)blockIdx.y * nr + i0 + t] = j;
     }
   }
+  if constexpr (MODE == CL_MREACHQ) {
+    static_assert(3 * ROWS * 17 <= (ROWS + CL_COLS) * CL_LDK, "the reduction scratch must fit the staging buffers");
+    __syncthreads();  // the staging buffers become the reduction scratch: [ROWS][17] weights, distances, indices
+    float* rw = cl_smem;
+    float* rd = cl_smem + ROWS * 17;
+    int* rj = reinterpret_cast<int*>(cl_smem + 2 * ROWS * 17);
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      rw[(ty + 16 * r) * 17 + tx] = bw[r];
+      rd[(ty + 16 * r) * 17 + tx] = bd[r];
+      rj[(ty + 16 * r) * 17 + tx] = bj[r];
+    }
+    __syncthreads();
+    if (t < ROWS && i0 + t < nr) {
+      float w = rw[t * 17], dist = rd[t * 17];
+      int j = rj[t * 17];
+      for (int q = 1; q < 16; ++q) {
+        const float wq = rw[t * 17 + q], dq = rd[t * 17 + q];
+        const int jq = rj[t * 17 + q];
+        if (jq >= 0 && (j < 0 || wq < w || (wq == w && (dq < dist || (dq == dist && jq < j))))) {
+          w = wq;
+          dist = dq;
+          j = jq;
+        }
+      }
+      const size_t at = (size_t)blockIdx.y * nr + i0 + t;
+      p.part_w[at] = w;
+      p.part_d[at] = dist;
+      p.part_j[at] = j;
+    }
+  }
 }
 
 // k-th smallest of the slices' k-lists of a row, by rank counting (ties ordered by position, so exactly one candidate
@@ -385,6 +459,29 @@ __global__ __launch_bounds__(CL_THREADS) void cl_minedge_merge(const float* __re
     }
   }
   out_w[i] = j < 0 ? INFINITY : w;
+  out_j[i] = j;
+}
+
+// The slices' best (w, dist, j) of a query row in the fixed slice order, lexicographic.
+__global__ __launch_bounds__(CL_THREADS) void cl_mreach_query_merge(const float* __restrict__ pw, const float* __restrict__ pd,
+                                                                    const int* __restrict__ pj, int slices, int m,
+                                                                    float* __restrict__ out_w, float* __restrict__ out_d,
+                                                                    int* __restrict__ out_j) {
+  const int i = blockIdx.x * CL_THREADS + threadIdx.x;
+  if (i >= m) return;
+  float w = INFINITY, dist = INFINITY;
+  int j = -1;
+  for (int s = 0; s < slices; ++s) {
+    const float ws = pw[(size_t)s * m + i], ds = pd[(size_t)s * m + i];
+    const int js = pj[(size_t)s * m + i];
+    if (js >= 0 && (j < 0 || ws < w || (ws == w && (ds < dist || (ds == dist && js < j))))) {
+      w = ws;
+      dist = ds;
+      j = js;
+    }
+  }
+  out_w[i] = j < 0 ? INFINITY : w;
+  out_d[i] = j < 0 ? INFINITY : dist;
   out_j[i] = j;
 }
 
@@ -557,6 +654,46 @@ extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32
   const int rc = cl_launch<CL_MINEDGE, 8>(a, g, metric, st);
   if (rc != WM_OK) return rc;
   cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, g.slices, n, out_w, out_j);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_mreach_query_workspace_bytes(int m, int n, int d) {
+  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0) return 0;
+  return (size_t)cl_grid(m, n, 128, true).slices * m * 12 + 256;
+}
+
+extern "C" int wm_mreach_query(const float* xq, const float* core_q, int m, const float* x, const float* core, int n, int d,
+                               int metric, float inv_alpha, float* out_w, float* out_dist, int32_t* out_j, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(xq && core_q && x && core && out_w && out_dist && out_j && workspace, WM_EINVAL);
+  WM_REQUIRE(m > 0 && n > 0 && d > 0 && inv_alpha > 0.f, WM_EINVAL);
+  WM_REQUIRE(m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+             WM_EALIGN);
+  const ClGrid g = cl_grid(m, n, 128, true);
+  const size_t entries = (size_t)g.slices * m;
+  WM_REQUIRE(workspace_bytes >= entries * 12, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.xr = xq;
+  a.nr = m;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.core = core;
+  a.core_q = core_q;
+  a.inv_alpha = inv_alpha;
+  a.part_w = static_cast<float*>(workspace);
+  a.part_d = a.part_w + entries;
+  a.part_j = reinterpret_cast<int*>(a.part_d + entries);
+  const int rc = cl_launch<CL_MREACHQ, 8>(a, g, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_mreach_query_merge<<<wm_cdiv(m, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_d, a.part_j, g.slices, m, out_w, out_dist,
+                                                                      out_j);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

@@ -16,4 +16,4 @@ for line in r.stderr.splitlines():
 demangle = subprocess.run(["c++filt"], input="\n".join(x["name"] for x in rows), capture_output=True, text=True).stdout.splitlines()
 for x, d in zip(rows, demangle):
     d = re.sub(r"\(anonymous namespace\)::", "", d); d = d.split("(")[0][:70]
-    print(f"{d:70s} vgpr={x.get('VGPRs','?'):>4} agpr={x.get('AGPRs','?'):>3} spill={x.get('VGPR Spill','?'):>3} scratch={x.get('ScratchSize [bytes/lane]','?'):>5} lds={x.get('LDS Size [bytes/block]','?'):>6} occ={x.get('Occupancy [waves/SIMD]','?')}")
+    print(f"{d:70s} vgpr={x.get('VGPRs','?'):>4} agpr={x.get('AGPRs','?'):>3} spill={x.get('VGPRs Spill', x.get('VGPR Spill','?')):>3} scratch={x.get('ScratchSize [bytes/lane]','?'):>5} lds={x.get('LDS Size [bytes/block]','?'):>6} occ={x.get('Occupancy [waves/SIMD]','?')}")
