@@ -257,6 +257,41 @@ int wm_conv2d_dgrad_bnstat(const void* dy, const void* w_crsk, const void* resid
 int wm_conv2d_wgrad_splits(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad);
 int wm_conv2d_wgrad(const void* dy, const void* x, float* dw_slabs, int N, int H, int W, int C, int K,
                     int R, int S, int P, int Q, int stride, int pad, void* stream);
+/* Which kernel serves a launch: the code of the kernel instantiation that the entry points above launch for this
+ * pass (0 forward, 1 input gradient, 2 weight gradient), geometry and operand set, or a negative WM_E* where they
+ * would refuse it.  The launches choose through the same function and switch on its answer, as the weight-gradient
+ * launch and wm_conv2d_wgrad_splits share one plan.  It launches nothing and touches no device.
+ *   flags      WM_ROUTE_F_STATS     forward with statistics slots (wm_conv2d_fwd_stats), group_arg = rows_per_group
+ *              WM_ROUTE_F_RESIDUAL  a residual / shortcut-gradient operand (fwd_bias_res, dgrad_add, dgrad_bnstat)
+ *              WM_ROUTE_F_BIAS      a bias (forward) or a bias gradient (weight gradient)
+ *              WM_ROUTE_F_BNB       the BatchNorm-backward epilogue (wm_conv2d_dgrad_bnstat), group_arg = G
+ *              WM_ROUTE_F_ACT       the GELU forms (wm_linear_bias_gelu_fwd, wm_linear_dgrad_gelu)
+ *   group_arg  rows per statistics group (STATS) or the number of groups G (BNB); else ignored
+ * Codes, one per instantiation the host can launch:
+ *   WM_ROUTE_PANEL                              the 192-wide panel kernel (panel.hip)
+ *   WM_ROUTE_STEM_PATCH                         conv_stem_patch
+ *   WM_ROUTE_WGRAD_PATCH64                      conv_wgrad_patch64
+ *   WM_ROUTE_PATCH(MODE, BNB)                   conv3x3_patch<MODE, BNB>: (0, 0) forward, (1, 0) and (1, 1) input gradient
+ *   WM_ROUTE_IGEMM(BN, CPT, MODE, EPI, BNB)     conv_igemm<128, BN, CPT, MODE, EPI, BNB>, BN 64 or 128:
+ *        forward (2, 0, 0, 0) the stem, (8, 0, 0, 0), (8, 0, 1, 0) with bias / residual / GELU;
+ *        input gradient (8, 3, 0, 0) stride 1, (8, 2, 0, 0) stride 2 by parity class, (8, 1, 0, 0) any other stride 2,
+ *        (8, 3, 1, 0) times gelu', (8, 3, 0, 1) and (8, 2, 0, 1) with the BatchNorm-backward epilogue
+ *   WM_ROUTE_WGRAD(BMO, CPT, NT, BIAS)          conv_wgrad<BMO, CPT, NT, BIAS>: (64, 8, 3 | 1), (128, 8, 3 | 2 | 1), each
+ *        with BIAS 0 or 1; the stem forms (64, 2, 4 | 1, 0) and (128, 2, 2 | 1, 0) */
+#define WM_ROUTE_F_STATS 1
+#define WM_ROUTE_F_RESIDUAL 2
+#define WM_ROUTE_F_BIAS 4
+#define WM_ROUTE_F_BNB 8
+#define WM_ROUTE_F_ACT 16
+#define WM_ROUTE_PANEL 1
+#define WM_ROUTE_STEM_PATCH 2
+#define WM_ROUTE_WGRAD_PATCH64 3
+#define WM_ROUTE_PATCH(MODE, BNB) (10 + 2 * (MODE) + ((BNB) ? 1 : 0))
+#define WM_ROUTE_IGEMM(BN, CPT, MODE, EPI, BNB) \
+  (10000 + ((BN) / 64) * 1000 + (CPT) * 100 + (MODE) * 10 + ((EPI) ? 2 : 0) + ((BNB) ? 1 : 0))
+#define WM_ROUTE_WGRAD(BMO, CPT, NT, BIAS) (20000 + ((BMO) / 64) * 1000 + (CPT) * 100 + (NT) * 10 + ((BIAS) ? 1 : 0))
+int wm_conv2d_route(int pass, int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad,
+                    int flags, int group_arg);
 /* Forward with y = conv(x) + bias[k] (+ residual, same shape as y), both optional, added in the
  * epilogue: a Linear layer's bias and the residual add of a transformer block cost no extra pass. */
 int wm_conv2d_fwd_bias_res(const void* x, const void* w_krsc, const float* bias, const void* residual, void* y,

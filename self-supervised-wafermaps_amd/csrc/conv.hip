@@ -1533,6 +1533,53 @@ inline int dgrad_mode(const ConvGeom& g) {
 }
 // rows of the space the statistics groups of the BatchNorm-backward epilogue divide: all of them, or one parity class
 inline long long dgrad_stat_rows(const ConvGeom& g, int mode) { return mode == 2 ? dgrad_class_rows(g) : g.rows_x(); }
+// can the BatchNorm-backward epilogue serve this dgrad with G statistics groups (wm_conv2d_dgrad_bnstat_ok)
+inline bool dgrad_bnstat_ok(const ConvGeom& g, int G) {
+  if (g.C % 64 != 0 || G <= 0 || g.N % G != 0) return false;
+  const int mode = dgrad_mode(g);
+  return mode != 1 && (dgrad_stat_rows(g, mode) / G) % 128 == 0;
+}
+
+// ---- the route: the WM_ROUTE_* code (wafer_hip.h) of the kernel instantiation that serves a checked geometry and
+// operand set, or a negative WM_E*.  conv_fwd_impl / conv_dgrad_impl / the wgrad launch and wm_conv2d_route all ask
+// here, and the launches switch on the answer: query and launch agree by construction.
+// 128 output channels per block where they divide the layer's, else 64
+inline int route_igemm(int DC, int cpt, int mode, bool epi, bool bnb) {
+  return WM_ROUTE_IGEMM(DC % 128 == 0 ? 128 : 64, cpt, mode, epi, bnb);
+}
+// forward; stat_rpg: rows per statistics group, 0 without statistics; has_act: the GELU form (pre_out)
+inline int conv_fwd_route(const ConvGeom& g, int stat_rpg, bool has_bias, bool has_res, bool has_act) {
+  if (has_act && (has_res || g.R != 1 || g.S != 1)) return WM_EUNSUPPORTED;
+  if (g.C == 16) {
+    if (has_bias || has_res) return WM_EUNSUPPORTED;
+    if (stem_patch_ok(g, false, false, stat_rpg)) return WM_ROUTE_STEM_PATCH;
+    // (256-pixel tiles for the 64-channel stem are 7 % faster alone but 10 % slower inside the training
+    // step, where the epilogue also accumulates the BatchNorm statistics: 564 vs 509 us)
+    return route_igemm(g.K, 2, 0, false, false);
+  }
+  // Linear with a 192-wide input (ViT-Tiny): token rows resident in registers, weight tiles streamed (panel.hip)
+  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && stat_rpg == 0 && wm_panel_ok(g.rows_y(), g.C, g.K, has_res))
+    return WM_ROUTE_PANEL;
+  if (!has_res && conv_patch_ok(g, has_bias, stat_rpg)) return WM_ROUTE_PATCH(0, false);
+  return route_igemm(g.K, 8, 0, has_bias || has_res || has_act, false);
+}
+// input gradient; has_act: times gelu'(pre_in); G: statistics groups of the BatchNorm-backward epilogue, 0 without it
+inline int conv_dgrad_route(const ConvGeom& g, bool has_res, bool has_act, int G) {
+  if (has_act && (has_res || g.R != 1 || g.S != 1 || g.stride != 1)) return WM_EUNSUPPORTED;
+  if (g.C % 64 != 0) return WM_EUNSUPPORTED;  // the stem needs no input gradient
+  const int mode = dgrad_mode(g);
+  if (G > 0) {  // (mode 3 or 2: wm_conv2d_dgrad_bnstat_ok)
+    if (has_act) return WM_EUNSUPPORTED;
+    if (mode == 3 && conv_patch_ok(g, false, (int)(dgrad_stat_rows(g, mode) / G))) return WM_ROUTE_PATCH(1, true);
+    return route_igemm(g.C, 8, mode == 3 ? 3 : 2, false, true);
+  }
+  // input gradient of a Linear with 192 OUTPUT features: dx = dy [rows][192] . w_crsk^T, w_crsk [C][192]
+  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && wm_panel_ok(g.rows_x(), g.K, g.C, has_res || has_act))
+    return WM_ROUTE_PANEL;
+  if (has_act) return route_igemm(g.C, 8, 3, true, false);  // (stride 1: checked above)
+  if (conv_patch_ok(g, false, 0)) return WM_ROUTE_PATCH(1, false);
+  return route_igemm(g.C, 8, mode, false, false);
+}
 
 // ---- launches
 template <int BM, int BN, int CPT, int MODE, bool EPI, bool BNB>
@@ -1548,13 +1595,6 @@ int launch_igemm_tile(const ConvArgs& a, hipStream_t st) {
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
-// 128 output channels per block where they divide the layer's, else 64
-template <int CPT, int MODE, bool EPI = false, bool BNB = false>
-int launch_igemm(const ConvArgs& a, hipStream_t st) {
-  return a.DC % 128 == 0 ? launch_igemm_tile<128, 128, CPT, MODE, EPI, BNB>(a, st)
-                         : launch_igemm_tile<128, 64, CPT, MODE, EPI, BNB>(a, st);
-}
-
 template <int MODE, bool BNB = false>
 int launch_patch(const ConvArgs& a, hipStream_t st) {
   static_assert(128 * (64 * 2 + 16) + 2 * CV_THREADS * 4 <= PT_LDS, "epilogue LDS");
@@ -1604,6 +1644,32 @@ int launch_stem_patch(const ConvArgs& a, hipStream_t st) {
     WM_LAUNCH_CHECK();
   }
   return WM_OK;
+}
+
+// The conv_igemm / conv3x3_patch / conv_stem_patch launch of a route code (the panel kernel takes other arguments: the
+// callers launch it themselves).  The cases stand in the order in which the instantiations have always been first
+// named: hipcc emits the kernels in that order, and the code object stays byte-identical across host-side changes.
+int launch_conv_route(int route, const ConvArgs& a, hipStream_t st) {
+#define WM_IGEMM_CASE(CPT, MODE, EPI, BNB)                                                                      \
+  case WM_ROUTE_IGEMM(128, CPT, MODE, EPI, BNB): return launch_igemm_tile<128, 128, CPT, MODE, EPI, BNB>(a, st); \
+  case WM_ROUTE_IGEMM(64, CPT, MODE, EPI, BNB): return launch_igemm_tile<128, 64, CPT, MODE, EPI, BNB>(a, st);
+  switch (route) {
+    case WM_ROUTE_STEM_PATCH: return launch_stem_patch(a, st);
+    WM_IGEMM_CASE(2, 0, false, false)
+    case WM_ROUTE_PATCH(0, false): return launch_patch<0>(a, st);
+    WM_IGEMM_CASE(8, 0, true, false)
+    WM_IGEMM_CASE(8, 0, false, false)
+    case WM_ROUTE_PATCH(1, true): return launch_patch<1, true>(a, st);
+    WM_IGEMM_CASE(8, 3, false, true)
+    WM_IGEMM_CASE(8, 2, false, true)
+    WM_IGEMM_CASE(8, 3, true, false)
+    case WM_ROUTE_PATCH(1, false): return launch_patch<1>(a, st);
+    WM_IGEMM_CASE(8, 3, false, false)
+    WM_IGEMM_CASE(8, 2, false, false)
+    WM_IGEMM_CASE(8, 1, false, false)
+    default: return route < 0 ? route : WM_EUNSUPPORTED;
+  }
+#undef WM_IGEMM_CASE
 }
 
 // ---- weight gradient: the kernel, its tile shape and its split-K plan, chosen in one place: the launch and
@@ -1684,12 +1750,6 @@ int launch_wgrad_impl(const WgradArgs& a, int nsplit, hipStream_t st) {
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
-template <int BMO, int CPT, int NT>
-int launch_wgrad(const WgradArgs& a, int nsplit, hipStream_t st) {
-  if (a.dbias == nullptr) return launch_wgrad_impl<BMO, CPT, NT, false>(a, nsplit, st);
-  if constexpr (CPT == 8) return launch_wgrad_impl<BMO, CPT, NT, true>(a, nsplit, st);
-  return WM_EUNSUPPORTED;  // no bias gradient on the space-to-depth stem form
-}
 int launch_wgrad_patch(const WgradArgs& a, int nsplit, hipStream_t st) {
   const int rc = ensure_lds<&conv_wgrad_patch64>(WP_LDS);
   if (rc != WM_OK) return rc;
@@ -1697,6 +1757,30 @@ int launch_wgrad_patch(const WgradArgs& a, int nsplit, hipStream_t st) {
   conv_wgrad_patch64<<<nsplit, CV_THREADS, WP_LDS, st>>>(a, wm_div_make((uint32_t)tpi), wm_div_make((uint32_t)tiles_w));
   WM_LAUNCH_CHECK();
   return WM_OK;
+}
+
+// route code of a weight-gradient choice; has_bias: with a bias gradient (Linear layers only: no such form of the
+// patch-resident kernel, whose split plan differs, and none on the space-to-depth stem)
+inline int wgrad_route(const WgradChoice& c, bool has_bias) {
+  if (c.patch) return has_bias ? WM_EUNSUPPORTED : WM_ROUTE_WGRAD_PATCH64;
+  if (c.cpt == 2 && has_bias) return WM_EUNSUPPORTED;
+  return WM_ROUTE_WGRAD(c.bmo, c.cpt, c.nt, has_bias);
+}
+int launch_wgrad_route(int route, const WgradArgs& a, int nsplit, hipStream_t st) {
+#define WM_WGRAD_CASE(BMO, CPT, NT, BIAS) \
+  case WM_ROUTE_WGRAD(BMO, CPT, NT, BIAS): return launch_wgrad_impl<BMO, CPT, NT, BIAS>(a, nsplit, st);
+  switch (route) {
+    case WM_ROUTE_WGRAD_PATCH64: return launch_wgrad_patch(a, nsplit, st);
+    WM_WGRAD_CASE(128, 2, 2, false) WM_WGRAD_CASE(128, 2, 1, false)
+    WM_WGRAD_CASE(64, 2, 4, false) WM_WGRAD_CASE(64, 2, 1, false)
+    WM_WGRAD_CASE(128, 8, 3, false) WM_WGRAD_CASE(128, 8, 3, true)
+    WM_WGRAD_CASE(128, 8, 2, false) WM_WGRAD_CASE(128, 8, 2, true)
+    WM_WGRAD_CASE(128, 8, 1, false) WM_WGRAD_CASE(128, 8, 1, true)
+    WM_WGRAD_CASE(64, 8, 3, false) WM_WGRAD_CASE(64, 8, 3, true)
+    WM_WGRAD_CASE(64, 8, 1, false) WM_WGRAD_CASE(64, 8, 1, true)
+    default: return route < 0 ? route : WM_EUNSUPPORTED;
+  }
+#undef WM_WGRAD_CASE
 }
 
 // ---- forward
@@ -1717,22 +1801,12 @@ int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const ConvGeom& g,
   a.pre_out = static_cast<uint16_t*>(pre_out);
   a.act = pre_out != nullptr ? 1 : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rpg = stat != nullptr ? stat_rpg : 0;
-  if (g.C == 16) {
-    WM_REQUIRE(bias == nullptr && residual == nullptr, WM_EUNSUPPORTED);
-    if (stem_patch_ok(g, false, false, rpg)) return launch_stem_patch(a, st);
-    // (256-pixel tiles for the 64-channel stem are 7 % faster alone but 10 % slower inside the training
-    // step, where the epilogue also accumulates the BatchNorm statistics: 564 vs 509 us)
-    return launch_igemm<2, 0>(a, st);
-  }
-  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && stat == nullptr && wm_panel_ok(a.M, g.C, g.K, residual != nullptr)) {
-    // Linear with a 192-wide input (ViT-Tiny): token rows resident in registers, weight tiles streamed (panel.hip)
+  const int route = conv_fwd_route(g, stat != nullptr ? stat_rpg : 0, bias != nullptr, residual != nullptr, pre_out != nullptr);
+  if (route == WM_ROUTE_PANEL) {
     WmPanelArgs pa{a.src, a.wt, bias, a.res, nullptr, a.pre_out, a.dst, a.M, g.K, a.act, 0, nullptr, nullptr, 0.f};
     return wm_panel_launch(pa, st);
   }
-  if (residual == nullptr && conv_patch_ok(g, bias != nullptr, rpg)) return launch_patch<0>(a, st);
-  if (bias != nullptr || residual != nullptr || pre_out != nullptr) return launch_igemm<8, 0, true>(a, st);
-  return launch_igemm<8, 0>(a, st);
+  return launch_conv_route(route, a, st);
 }
 
 // ---- input gradient
@@ -1762,27 +1836,21 @@ int conv_dgrad_impl(const void* dy, const void* w_crsk, void* dx, const void* re
   a.pre_in = static_cast<const uint16_t*>(pre_in);
   a.act = pre_in != nullptr ? 2 : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int mode = dgrad_mode(g);
-  if (bnb != nullptr) {  // (mode 3 or 2: wm_conv2d_dgrad_bnstat_ok)
+  const int route = conv_dgrad_route(g, residual != nullptr, pre_in != nullptr, bnb != nullptr ? bnb->G : 0);
+  if (bnb != nullptr) {
     WM_REQUIRE(pre_in == nullptr, WM_EUNSUPPORTED);
     a.bn_y = static_cast<const uint16_t*>(bnb->bn_y);
     a.bn_x = static_cast<const uint16_t*>(bnb->bn_x);
     a.bn_mask = static_cast<const uint8_t*>(bnb->bn_mask);
     a.bn_mean = bnb->mean; a.bn_invstd = bnb->invstd; a.bn_gamma = bnb->gamma; a.bn_beta = bnb->beta;
     a.stat = bnb->stat; a.stat_nb = bnb->stat_nb;
-    a.stat_rpg = (int)(dgrad_stat_rows(g, mode) / bnb->G);
-    if (mode == 3 && conv_patch_ok(g, false, a.stat_rpg)) return launch_patch<1, true>(a, st);
-    return mode == 3 ? launch_igemm<8, 3, false, true>(a, st) : launch_igemm<8, 2, false, true>(a, st);
+    a.stat_rpg = (int)(dgrad_stat_rows(g, dgrad_mode(g)) / bnb->G);
   }
-  if (g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && wm_panel_ok(a.M, g.K, g.C, residual != nullptr || pre_in != nullptr)) {
-    // input gradient of a Linear with 192 OUTPUT features: dx = dy [rows][192] . w_crsk^T, w_crsk [C][192]
+  if (route == WM_ROUTE_PANEL) {
     WmPanelArgs pa{a.src, a.wt, nullptr, a.res, a.pre_in, nullptr, a.dst, a.M, g.C, a.act, 0, nullptr, nullptr, 0.f};
     return wm_panel_launch(pa, st);
   }
-  if (pre_in != nullptr) return launch_igemm<8, 3, true>(a, st);  // (stride 1: checked above)
-  if (conv_patch_ok(g, false, 0)) return launch_patch<1>(a, st);
-  if (mode == 3) return launch_igemm<8, 3>(a, st);
-  return mode == 2 ? launch_igemm<8, 2>(a, st) : launch_igemm<8, 1>(a, st);
+  return launch_conv_route(route, a, st);
 }
 
 }  // namespace
@@ -1855,9 +1923,7 @@ extern "C" int wm_conv2d_dgrad_add(const void* dy, const void* w_crsk, const voi
 extern "C" int wm_conv2d_dgrad_bnstat_ok(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride,
                                          int pad, int G) {
   const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
-  if (conv_check(g) != WM_OK || C % 64 != 0 || G <= 0 || N % G != 0) return 0;
-  const int mode = dgrad_mode(g);
-  return mode != 1 && (dgrad_stat_rows(g, mode) / G) % 128 == 0 ? 1 : 0;
+  return conv_check(g) == WM_OK && dgrad_bnstat_ok(g, G) ? 1 : 0;
 }
 
 extern "C" int wm_conv2d_dgrad_bnstat(const void* dy, const void* w_crsk, const void* residual, void* dx, int N, int H,
@@ -1908,17 +1974,7 @@ extern "C" int wm_conv2d_wgrad_bias(const void* dy, const void* x, float* dw_krs
   a.stride = stride; a.pad = pad; a.M = N * P * Q;
   a.chunks_per_split = c.chunks_per_split; a.total_chunks = c.total_chunks;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (c.patch) return launch_wgrad_patch(a, c.nsplit, st);
-  if (c.cpt == 2) {
-    if (c.bmo == 128) return c.nt == 2 ? launch_wgrad<128, 2, 2>(a, c.nsplit, st) : launch_wgrad<128, 2, 1>(a, c.nsplit, st);
-    return c.nt == 4 ? launch_wgrad<64, 2, 4>(a, c.nsplit, st) : launch_wgrad<64, 2, 1>(a, c.nsplit, st);
-  }
-  if (c.bmo == 128) {
-    if (c.nt == 3) return launch_wgrad<128, 8, 3>(a, c.nsplit, st);
-    if (c.nt == 2) return launch_wgrad<128, 8, 2>(a, c.nsplit, st);
-    return launch_wgrad<128, 8, 1>(a, c.nsplit, st);
-  }
-  return c.nt == 3 ? launch_wgrad<64, 8, 3>(a, c.nsplit, st) : launch_wgrad<64, 8, 1>(a, c.nsplit, st);
+  return launch_wgrad_route(wgrad_route(c, dbias != nullptr), a, c.nsplit, st);
 }
 
 extern "C" int wm_conv2d_wgrad_splits(int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad) {
@@ -1926,4 +1982,34 @@ extern "C" int wm_conv2d_wgrad_splits(int N, int H, int W, int C, int K, int R, 
   const int rc = conv_check(g);
   if (rc != WM_OK) return rc;
   return wgrad_choice(g).nsplit;
+}
+
+extern "C" int wm_conv2d_route(int pass, int N, int H, int W, int C, int K, int R, int S, int P, int Q, int stride, int pad,
+                               int flags, int group_arg) {
+  const ConvGeom g{N, H, W, C, K, R, S, P, Q, stride, pad};
+  const int rc = conv_check(g);
+  if (rc != WM_OK) return rc;
+  const bool stats = flags & WM_ROUTE_F_STATS, res = flags & WM_ROUTE_F_RESIDUAL, bias = flags & WM_ROUTE_F_BIAS;
+  const bool bnb = flags & WM_ROUTE_F_BNB, act = flags & WM_ROUTE_F_ACT;
+  WM_REQUIRE((flags & ~31) == 0, WM_EINVAL);
+  if (pass == 0) {
+    WM_REQUIRE(!bnb && !(stats && (res || bias || act)), WM_EINVAL);  // (no entry point takes statistics with an epilogue operand)
+    if (stats) {  // wm_conv2d_fwd_stats
+      WM_REQUIRE(group_arg > 0, WM_EINVAL);
+      WM_REQUIRE(group_arg % 128 == 0 && g.rows_y() % group_arg == 0, WM_EUNSUPPORTED);
+    }
+    return conv_fwd_route(g, stats ? group_arg : 0, bias, res, act);
+  }
+  if (pass == 1) {
+    WM_REQUIRE(!stats && !bias, WM_EINVAL);
+    if (bnb) {  // wm_conv2d_dgrad_bnstat
+      WM_REQUIRE(group_arg > 0, WM_EINVAL);
+      WM_REQUIRE(dgrad_bnstat_ok(g, group_arg), WM_EUNSUPPORTED);
+    }
+    return conv_dgrad_route(g, res, act, bnb ? group_arg : 0);
+  }
+  WM_REQUIRE(pass == 2 && !stats && !res && !bnb && !act, WM_EINVAL);
+  // (wm_conv2d_wgrad_bias: the kernel forms element offsets in 32 bits)
+  WM_REQUIRE(g.rows_x() * C < (1ll << 32) - (1 << 20) && g.rows_y() * K < (1ll << 32) - (1 << 20), WM_EUNSUPPORTED);
+  return wgrad_route(wgrad_choice(g), bias);
 }

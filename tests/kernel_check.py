@@ -18,7 +18,8 @@ FACTOR = 2 covers what the emulation does not model: float32 summation order, __
 ulp, three orders below a bf16 rounding) and the fluctuation of a maximum over a different set of rounding events.  A
 tensor that needs more is a finding; a call that passes a wider factor says next to it what was measured and why.
 
-The module also holds the emulations (attention, LayerNorm, bias / activation, Linear and the GELU MLP), each with
+The module also holds the emulations (attention, LayerNorm, bias / activation, Linear, the GELU MLP, the convolutions
+of csrc/conv.hip with their fused statistics and BatchNorm-backward epilogue), each with
 switches that seed one wrong computation, and the input families.  tests/test_kernel_check_cpu.py proves on the CPU
 that every seeded error is rejected by `check` on these families; the GPU tests feed the kernels the same families.
 """
@@ -413,3 +414,315 @@ def mlp_ref(x, w1, b1, w2, b2, res=None, dy=None, emulate=False, ln=None):
         out.update(dx=rnd(dpre @ w1), dw1=dpre.t() @ xin, db1=dpre.sum(0), dw2=dy.t() @ hid, db2=dy.sum(0), dpre=dpre,
                    hid=hid)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ convolution
+# Layouts are the kernels' own: x [N, H, W, C], w [K, R, S, C], y / dy [N, P, Q, K], dW [K, R, S, C]; "rows" are pixels
+# in (n, h, w) order.  Everything is an im2col product in float64; tests/test_kernel_check_cpu.py holds it against
+# torch's own conv2d and autograd.
+def route_igemm(bn, cpt, mode, epi=False, bnb=False):
+    """WM_ROUTE_IGEMM of include/wafer_hip.h (and the other codes below): what wm_conv2d_route answers"""
+    return 10000 + (bn // 64) * 1000 + cpt * 100 + mode * 10 + (2 if epi else 0) + (1 if bnb else 0)
+
+
+def route_wgrad(bmo, cpt, nt, bias=False):
+    return 20000 + (bmo // 64) * 1000 + cpt * 100 + nt * 10 + (1 if bias else 0)
+
+
+def route_patch(mode, bnb=False):
+    return 10 + 2 * mode + (1 if bnb else 0)
+
+
+ROUTE_PANEL, ROUTE_STEM_PATCH, ROUTE_WGRAD_PATCH64 = 1, 2, 3
+ROUTE_F_STATS, ROUTE_F_RESIDUAL, ROUTE_F_BIAS, ROUTE_F_BNB, ROUTE_F_ACT = 1, 2, 4, 8, 16
+
+
+def conv_out_hw(h, w, r, s, stride, pad):
+    return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+
+
+def conv_gather(n, h, w, r, s, p, q, stride, pad, seed_error=None):
+    """[N P Q, R S] long: the row of x (pixel index in (n, h, w) order) that tap (r, s) of an output pixel reads; -1 = the
+    zero padding.  seed_error "wrap_border": a tap left or right of the image reads the flattened neighbour pixel (the
+    end of the previous / start of the next image row) instead of zero; "image_bleed": a tap above row 0 of image n > 0
+    reads the last rows of image n - 1."""
+    ih = (torch.arange(p) * stride - pad).view(p, 1, 1, 1) + torch.arange(r).view(1, 1, r, 1)
+    iw = (torch.arange(q) * stride - pad).view(1, q, 1, 1) + torch.arange(s).view(1, 1, 1, s)
+    ih, iw = ih.expand(p, q, r, s), iw.expand(p, q, r, s)
+    okh, okw = (ih >= 0) & (ih < h), (iw >= 0) & (iw < w)
+    flat = ih * w + iw
+    g = (torch.arange(n) * (h * w)).view(n, 1, 1, 1, 1) + flat.unsqueeze(0)
+    ok = (okh & okw).unsqueeze(0).expand_as(g)
+    if seed_error == "wrap_border":
+        ok = (okh & (okw | ((flat >= 0) & (flat < h * w)))).unsqueeze(0).expand_as(g)
+    elif seed_error == "image_bleed":
+        ok = ok | (((ih < 0) & okw).unsqueeze(0) & (g >= 0))
+    return torch.where(ok, g, torch.full_like(g, -1)).reshape(n * p * q, r * s)
+
+
+def conv_im2col(x_rows, idx):
+    """[M, R S C] float64: the gathered operand of the implicit GEMM (zero where idx is -1)"""
+    z = torch.cat([x_rows.double(), torch.zeros(1, x_rows.shape[1], dtype=torch.float64)])
+    return z[idx].reshape(idx.shape[0], -1)
+
+
+def row_tiles(rows, size=128):
+    """Statistics tiles of conv_igemm: runs of 128 rows (a ragged last run is no tile: statistics need whole tiles)"""
+    return [torch.arange(t * size, (t + 1) * size) for t in range(rows // size)]
+
+
+def pair_tiles(n, h, w):
+    """... of the tile-pair kernels: pair b = the 8 x 8 tiles 2 b and 2 b + 1 in (image, tile row, tile column) order,
+    rows tile * 64 + ty * 8 + tx (conv3x3_patch: pair_pixel)"""
+    th, tw = h // 8, w // 8
+    org = [(i * h + a * 8) * w + b * 8 for i in range(n) for a in range(th) for b in range(tw)]
+    inner = (torch.arange(8).view(8, 1) * w + torch.arange(8).view(1, 8)).reshape(-1)
+    return [torch.cat([org[2 * b] + inner, org[2 * b + 1] + inner]) for b in range(len(org) // 2)]
+
+
+def stem_tiles(n, h, w, groups, slots):
+    """... of conv_stem_patch: one launch per group, block b of min(pairs, slots) blocks sums over the pairs b, b + blocks, ...
+    of its group and owns slot b"""
+    pairs = pair_tiles(n, h, w)
+    per = len(pairs) // groups
+    out = []
+    for g in range(groups):
+        blocks = min(per, slots)
+        out += [torch.cat(pairs[g * per + b:(g + 1) * per:blocks]) for b in range(blocks)]
+    return out
+
+
+def class_tiles(n, h, w, groups):
+    """... of the MODE 2 input gradient: dx pixels ordered by parity class pc = 2 (h & 1) + (w & 1), inside a class in (n, h / 2,
+    w / 2) order; a group's slots run class by class (conv_igemm: stat_slot(a, m0 - pc * cls, pc * (stat_rpg / BM)))"""
+    nn, hh, ww = torch.meshgrid(torch.arange(n), torch.arange(h // 2), torch.arange(w // 2), indexing="ij")
+    cls = [((nn * h + 2 * hh + ph) * w + 2 * ww + pw).reshape(-1) for ph in (0, 1) for pw in (0, 1)]
+    rpg = cls[0].numel() // groups
+    return [c[g * rpg + t * 128:g * rpg + (t + 1) * 128] for g in range(groups) for c in cls for t in range(rpg // 128)]
+
+
+def tile_sums(vals, tiles):
+    """[T, C] float64 column sums of vals [rows, C] over each tile's rows"""
+    v = vals.double()
+    return torch.stack([v[t].sum(0) for t in tiles]) if tiles else v.new_zeros(0, v.shape[1])
+
+
+def tile_sums_f32(vals, tiles):
+    """the float32 row-order restatement of tile_sums (colsum_f32 per tile): yardstick of the float32 slots"""
+    v = vals.float()
+    return torch.stack([colsum_f32(v[t]) for t in tiles])
+
+
+def _mm(a, b, chunk=16384):
+    return torch.cat([a[i:i + chunk] @ b for i in range(0, a.shape[0], chunk)])
+
+
+def conv_ref(x, w, stride, pad, dy=None, res=None, dres=None, emulate=False, seed_error=None, out_hw=None, tiles=None):
+    """Convolution in float64 -> dict(y, dx, dw, stats [T, 2, K], and the pieces the float32 yardsticks need: cols [M, R S C],
+    y_acc / dx_acc, the unrounded accumulators as rows).  res: added to y, dres: a shortcut gradient added to dx.
+    out_hw: (P, Q) where the caller crops the output (the space-to-depth stem: P = H with pad 2, R 4).
+    tiles: the rows of every statistics slot (row_tiles / pair_tiles / stem_tiles); default row_tiles.
+
+    emulate: rounds where csrc/conv.hip does --
+      * the accumulator tile is staged as bf16 (stage_acc_frag: pack_bf2 of every accumulator), y / dx are that;
+      * a residual / shortcut gradient is added to the ROUNDED tile and the sum rounded again (bf16x8_add in the store
+        loops of conv_igemm and conv3x3_patch);
+      * the statistics are the sums of the ROUNDED outputs (store_tile_with_stats reads the staged bf16 tile).
+    dw and stats stay float64 (the float32 restatements: matmul_tn_f32(dy rows, cols), tile_sums_f32).
+
+    seed_error (tests/test_kernel_check_cpu.py): "wrap_border", "image_bleed" (conv_gather; the input gradient is the
+    adjoint of the same wrong gather, the weight gradient uses it); "tap_transpose" (r and s of the weights swapped);
+    "drop_tail" (the last M mod 128 rows of y and of dx keep their previous content, 0; the weight gradient leaves out
+    the last partial 64-pixel chunk); "one_class_missing" (stride-2 dx without the parity class (1, 1));
+    "res_unrounded" (residual added before the rounding); "stats_unrounded" (statistics of the accumulators)."""
+    n, h, wd, c = x.shape
+    k, r, s, _ = w.shape
+    p, q = out_hw if out_hw is not None else conv_out_hw(h, wd, r, s, stride, pad)
+    rnd = bf if emulate else (lambda t: t)
+    ws = w.transpose(1, 2) if seed_error == "tap_transpose" else w
+    wm = ws.double().reshape(k, r * s * c)
+    idx = conv_gather(n, h, wd, r, s, p, q, stride, pad, seed_error)
+    cols = conv_im2col(x.reshape(-1, c), idx)
+    m = n * p * q
+    acc = _mm(cols, wm.t())
+    if seed_error == "drop_tail":
+        acc[m - m % 128:] = 0.0
+    y = rnd(acc)
+    src = acc if seed_error == "stats_unrounded" else y
+    if res is not None:
+        rr = res.double().reshape(m, k)
+        y = rnd(acc + rr) if seed_error == "res_unrounded" else rnd(y + rr)
+    tiles = row_tiles(m) if tiles is None else tiles
+    out = {"y": y.reshape(n, p, q, k), "y_acc": acc, "cols": cols,
+           "stats": torch.stack([tile_sums(src, tiles), tile_sums(src * src, tiles)], 1)}
+    if dy is None:
+        return out
+    dyr = dy.double().reshape(m, k)
+    mx = n * h * wd
+    d = _mm(dyr, wm).reshape(m * r * s, c)
+    fi = idx.reshape(-1)
+    dacc = torch.zeros(mx + 1, c, dtype=torch.float64).index_add_(0, torch.where(fi >= 0, fi, torch.full_like(fi, mx)), d)[:mx]
+    if seed_error == "one_class_missing":
+        dacc.view(n, h, wd, c)[:, 1::2, 1::2] = 0.0
+    if seed_error == "drop_tail":
+        dacc[mx - mx % 128:] = 0.0
+    dx = rnd(dacc)
+    if dres is not None:
+        dr = dres.double().reshape(mx, c)
+        dx = rnd(dacc + dr) if seed_error == "res_unrounded" else rnd(dx + dr)
+    keep = m - m % 64 if seed_error == "drop_tail" else m
+    dw = (dyr[:keep].t() @ cols[:keep]).reshape(k, r, s, c)
+    if seed_error == "tap_transpose":
+        dw = dw.transpose(1, 2)
+    out.update(dx=dx.reshape(n, h, wd, c), dx_acc=dacc, dw=dw)
+    return out
+
+
+def bn_dgrad_epilogue_ref(dx_acc, res, bn_y, mean, invstd, gamma, beta, form, relu_x=None, mask=None, tiles=None,
+                          emulate=False, seed_error=None):
+    """The BatchNorm-backward epilogue of wm_conv2d_dgrad_bnstat in float64 on rows [rows, C]:
+        g = (dgrad (+ residual)) * mask -> dx;  per tile (sum g, sum g (bn_y - mean)) per channel -> stats [T, 2, C]
+    dx_acc: the unrounded input gradient (conv_ref "dx_acc"); mean / invstd [G, C] over G equal runs of images (= of rows).
+    form "x": mask = relu_x > 0; "bits": bit c & 7 of mask[row, c >> 3]; "recompute": bn_y gamma invstd + beta - mean gamma
+    invstd > 0.  tiles: rows of every slot (row_tiles, pair_tiles, class_tiles).
+    emulate (bnb_epilogue): the staged bf16 gradient tile plus the residual in float32 WITHOUT a second rounding, masked;
+    the sums are taken from that float32 value, dx is its bf16 rounding; the recomputed mask is fmaf(bn_y, scale, shift) > 0
+    with the float32 scale = gamma invstd and shift = beta - mean scale of the BatchNorm forward.
+    Returns dict(dx, stats, g [rows, C], gy [rows, C]: the summed terms).
+    seed_error: "mask_off_by_channel" (the bit mask read one bit over), "stat_uncentred" (sum g bn_y)."""
+    rows, c = dx_acc.shape
+    groups = mean.shape[0]
+    grp = torch.arange(rows) // (rows // groups)
+    y = bn_y.double().reshape(rows, c)
+    mu = mean.double()[grp]
+    v = bf(dx_acc) if emulate else dx_acc.clone()
+    if res is not None:
+        v = (v.float() + res.reshape(rows, c).float()).double() if emulate else v + res.double().reshape(rows, c)
+    if form == "x":
+        keep = relu_x.reshape(rows, c) > 0
+    elif form == "bits":
+        e = torch.arange(c) & 7
+        if seed_error == "mask_off_by_channel":
+            e = (e + 1) & 7
+        keep = ((mask.reshape(rows, c // 8).long()[:, torch.arange(c) >> 3] >> e) & 1) != 0
+    elif emulate:
+        sc = gamma.float() * invstd.float()
+        sh = beta.float() - mean.float() * sc
+        keep = (y * sc.double()[grp] + sh.double()[grp]).float() > 0    # (one rounding: fmaf)
+    else:
+        sc = gamma.double() * invstd.double()
+        keep = y * sc[grp] + (beta.double() - mean.double() * sc)[grp] > 0
+    g = v * keep
+    gy = g * (y if seed_error == "stat_uncentred" else y - mu)
+    tiles = row_tiles(rows) if tiles is None else tiles
+    return {"dx": rnd_or(g, emulate), "stats": torch.stack([tile_sums(g, tiles), tile_sums(gy, tiles)], 1), "g": g, "gy": gy}
+
+
+def rnd_or(t, emulate):
+    return bf(t) if emulate else t
+
+
+CONV_FAMILIES = ("lattice", "randn", "offset", "big_pixel")
+
+
+def conv_inputs(family, n, h, w, c, k, r, s, p, q, seed):
+    """dict(x [N, H, W, C], w [K, R, S, C], dy [N, P, Q, K], dres [N, H, W, C]) of bf16-exact float32 values.
+    randn: unit normal activations, He-scaled weights.  offset: x = 8 + randn and dy = 8 + randn (every accumulator carries
+    a large common term).  big_pixel: one pixel of x and of dy times 1e4.  lattice: x, dy, dres integers in -2 .. 2, weights
+    in {-1, 0, 1} with about 96 non-zeros per output channel (and per input channel), every (tap, input channel) and every
+    (tap, output channel) used: every product, every partial sum in any order and every rounded output is exact
+    (lattice_exact asserts it), so kernel and float64 agree bit for bit."""
+    g = torch.Generator().manual_seed(seed)
+    if family == "lattice":
+        x = torch.randint(-2, 3, (n, h, w, c), generator=g).float()
+        dy = torch.randint(-2, 3, (n, p, q, k), generator=g).float()
+        dres = torch.randint(-2, 3, (n, h, w, c), generator=g).float()
+        dens = 1.0 if c == 3 else min(1.0, 96.0 / max(c * r * s, k * r * s))   # (the 3-channel stem: dense +-1)
+        sign = torch.randint(0, 2, (k, r, s, c), generator=g).float() * 2 - 1
+        wt = sign * (torch.rand(k, r, s, c, generator=g) < dens)
+        # a (tap, channel) position no output (input) channel uses would hide that tap's address from the test
+        for dim in (0, 3):
+            dead = (wt != 0).sum(dim) == 0
+            pick = torch.randint(0, wt.shape[dim], dead.shape, generator=g)
+            fix = torch.zeros_like(wt).scatter_(dim, pick.unsqueeze(dim), 1.0) * dead.unsqueeze(dim)
+            wt = torch.where(fix != 0, sign, wt)
+        assert bool(((wt != 0).sum(0) > 0).all()) and bool(((wt != 0).sum(3) > 0).all())
+        return {"x": x, "w": wt, "dy": dy, "dres": dres}
+    x = torch.randn(n, h, w, c, generator=g)
+    dy = torch.randn(n, p, q, k, generator=g)
+    dres = torch.randn(n, h, w, c, generator=g)
+    wt = torch.randn(k, r, s, c, generator=g) * (2.0 / (c * r * s)) ** 0.5
+    if family == "offset":
+        x, dy = x + 8.0, dy + 8.0
+    elif family == "big_pixel":
+        x[n // 2, h // 2, w // 2] *= 1e4
+        dy[n // 2, p // 2, q // 2] *= 1e4
+    elif family != "randn":
+        raise ValueError(family)
+    return {"x": bf(x), "w": bf(wt), "dy": bf(dy), "dres": bf(dres)}
+
+
+def bn_inputs(family, rows, c, groups, seed):
+    """Operands of the BatchNorm-backward epilogue: dict(bn_y, relu_x [rows, C] bf16-exact, mask [rows, C / 8] uint8,
+    mean, invstd [G, C], gamma, beta [C]).
+    lattice: bn_y integers in -2 .. 2, mean and beta integers, gamma and invstd powers of two.  offset: channel mean 50
+    with spread 1 (|mean| >> std: an uncentred sum g bn_y cancels).  randn: bn_y is built FROM its pre-activation z,
+    |z| >= 0.5, so that no pre-activation lies near zero and the recomputed mask does not hang on a rounding
+    (bn_preact_margin asserts it on the float64 reference; nothing is excluded)."""
+    g = torch.Generator().manual_seed(seed)
+    relu_x = torch.randn(rows, c, generator=g)
+    mask = torch.randint(0, 256, (rows, c // 8), generator=g, dtype=torch.uint8)
+    grp = torch.arange(rows) // (rows // groups)
+    if family == "lattice":
+        mean = torch.randint(-2, 3, (groups, c), generator=g).float()
+        beta = torch.randint(-2, 3, (c,), generator=g).float()
+        gamma = 2.0 ** torch.randint(-1, 2, (c,), generator=g).float()
+        invstd = 2.0 ** torch.randint(-1, 2, (groups, c), generator=g).float()
+        bn_y = torch.randint(-2, 3, (rows, c), generator=g).float()
+        # an integer pre-activation of exactly 0 is masked by both sides (0 > 0 is false): nothing hangs on a rounding
+        relu_x = torch.randint(-2, 3, (rows, c), generator=g).float()
+    elif family == "offset":
+        mean = 50.0 + torch.randn(groups, c, generator=g)
+        invstd, gamma, beta = torch.rand(groups, c, generator=g) + 0.5, torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.1
+        bn_y = bf(mean[grp] + torch.randn(rows, c, generator=g))
+    else:
+        mean, beta = torch.rand(groups, c, generator=g) * 0.6 - 0.3, torch.rand(c, generator=g) * 0.6 - 0.3
+        invstd, gamma = torch.rand(groups, c, generator=g) * 0.5 + 0.75, torch.rand(c, generator=g) * 0.5 + 0.75
+        z = torch.randn(rows, c, generator=g)
+        z = torch.sign(z) * (0.5 + z.abs()).clamp_max(4.0)
+        bn_y = bf(mean[grp] + (z - beta) / (gamma * invstd[grp]))
+    return {"bn_y": bn_y, "relu_x": bf(relu_x), "mask": mask, "mean": mean, "invstd": invstd, "gamma": gamma, "beta": beta}
+
+
+def bn_preact_margin(b):
+    """min over elements of |pre-activation| / (|bn_y scale| + |shift|) in float64: the recomputed mask is safe while this
+    stays far above a bf16 ulp (2^-8)"""
+    rows = b["bn_y"].shape[0]
+    grp = torch.arange(rows) // (rows // b["mean"].shape[0])
+    sc = (b["gamma"].double() * b["invstd"].double())[grp]
+    sh = b["beta"].double() - b["mean"].double()[grp] * sc
+    t = b["bn_y"].double() * sc
+    return float(((t + sh).abs() / (t.abs() + sh.abs()).clamp_min(1e-300)).min())
+
+
+def lattice_exact(out, f32_keys=("dw", "stats")):
+    """Preconditions of the exact tier on a float64 result dict: every bf16 output equals its own bf16 rounding, every
+    float32 output is an integer (or dyadic) sum below 2^24 in magnitude"""
+    for key, t in out.items():
+        if key in ("cols", "y_acc", "dx_acc", "g", "gy") or t is None or t.numel() == 0:
+            continue
+        if key in f32_keys:
+            assert float(t.abs().max()) < 2.0 ** 24 and torch.equal(t, t.float().double()), key
+        else:
+            assert torch.equal(t, t.float().bfloat16().double()), f"{key}: not bf16-exact (max {float(t.abs().max())})"
+
+
+def f32_sum_bound(vals, tiles):
+    """(bound of sum, bound of sum of squares) [T, C]: what ANY order of float32 additions of a tile's n values (fmaf for the
+    squares: one rounding per term) can miss the exact sums by -- gamma_(n-1) sum |v| and gamma_n sum v^2, gamma_j = j u /
+    (1 - j u), u = 2^-24 (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2).  Derived, not measured."""
+    u = 2.0 ** -24
+    v = vals.double()
+    gam = lambda j: j * u / (1.0 - j * u)  # noqa: E731
+    return (torch.stack([gam(len(t) - 1) * v[t].abs().sum(0) for t in tiles]),
+            torch.stack([gam(len(t)) * (v[t] * v[t]).sum(0) for t in tiles]))

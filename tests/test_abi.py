@@ -77,6 +77,59 @@ def test_argument_validation_needs_no_gpu(lib):
     assert lib.wm_ntxent_fwd(None, None, 4, 4, 0, 128, 0.5, None, None, None) == -1
 
 
+def test_conv_route_query_needs_no_gpu(lib, monkeypatch):
+    """wm_conv2d_route names the kernel instantiation of every shape of tests/conv_cases.py (the GPU tests of
+    csrc/conv.hip ask it again before they launch), refuses what the entry points refuse, and launches nothing."""
+    import conv_cases as cc
+    import kernel_check as kc
+
+    monkeypatch.delenv("WM_WGRAD_PATCH", raising=False)
+    for route, shape in cc.FWD:
+        assert lib.wm_conv2d_route(0, *cc.geom(shape), 0, 0) == route, ("fwd", shape)
+    for route, shape, groups in cc.FWD_STATS:
+        g = cc.geom(shape)
+        assert lib.wm_conv2d_route(0, *g, kc.ROUTE_F_STATS, g[0] * g[7] * g[8] // groups) == route, ("fwd stats", shape)
+    for route, shape in cc.DGRAD:
+        for flags in (0, kc.ROUTE_F_RESIDUAL):
+            assert lib.wm_conv2d_route(1, *cc.geom(shape), flags, 0) == route, ("dgrad", shape, flags)
+    for route, shape, groups in cc.DGRAD_BNB:
+        for flags in (kc.ROUTE_F_BNB, kc.ROUTE_F_BNB | kc.ROUTE_F_RESIDUAL):
+            assert lib.wm_conv2d_dgrad_bnstat_ok(*cc.geom(shape), groups) == 1
+            assert lib.wm_conv2d_route(1, *cc.geom(shape), flags, groups) == route, ("dgrad bnb", shape, flags)
+    assert lib.wm_conv2d_dgrad_bnstat_ok(*cc.geom(cc.BNB_REFUSED), 1) == 0
+    assert lib.wm_conv2d_route(1, *cc.geom(cc.BNB_REFUSED), kc.ROUTE_F_BNB, 1) == -2
+    for route, g, splits in cc.WGRAD:
+        assert lib.wm_conv2d_route(2, *g, 0, 0) == route, ("wgrad", g)
+        assert splits is None or lib.wm_conv2d_wgrad_splits(*g) == splits, ("wgrad splits", g)
+    for route, shape in cc.WGRAD_STEM:
+        assert lib.wm_conv2d_route(2, *cc.geom(shape), 0, 0) == route, ("stem wgrad", shape)
+    monkeypatch.setenv("WM_WGRAD_PATCH", "0")
+    for route, g in cc.WGRAD_PATCH_OFF:
+        assert lib.wm_conv2d_route(2, *g, 0, 0) == route, ("wgrad, patch kernel off", g)
+    monkeypatch.delenv("WM_WGRAD_PATCH")
+    # the epilogue forms of the Linear layers and the hand-off to the panel kernel
+    lin = cc.linear_geom
+    assert lib.wm_conv2d_route(0, *lin(129, 64, 128), kc.ROUTE_F_BIAS | kc.ROUTE_F_RESIDUAL, 0) == kc.route_igemm(128, 8, 0, epi=True)
+    assert lib.wm_conv2d_route(0, *lin(129, 64, 192), kc.ROUTE_F_BIAS | kc.ROUTE_F_ACT, 0) == kc.route_igemm(64, 8, 0, epi=True)
+    assert lib.wm_conv2d_route(1, *lin(129, 64, 128), kc.ROUTE_F_ACT, 0) == kc.route_igemm(64, 8, 3, epi=True)
+    assert lib.wm_conv2d_route(0, *lin(129, 192, 384), kc.ROUTE_F_BIAS, 0) == kc.ROUTE_PANEL
+    assert lib.wm_conv2d_route(0, *lin(129, 192, 384), kc.ROUTE_F_RESIDUAL, 0) == kc.route_igemm(128, 8, 0, epi=True)
+    assert lib.wm_conv2d_route(1, *lin(129, 384, 192), 0, 0) == kc.ROUTE_PANEL
+    assert lib.wm_conv2d_route(2, *lin(129, 64, 128), kc.ROUTE_F_BIAS, 0) == kc.route_wgrad(128, 8, 1, bias=True)
+    # refused as the entry points refuse: bad sizes, channels, a bias gradient on the patch-resident or stem form,
+    # an input gradient of the stem, statistics groups that are no whole tiles, unknown passes and flags
+    g = cc.geom((2, 64, 8, 8, 64, 3, 1, 1))
+    assert lib.wm_conv2d_route(0, 0, *g[1:], 0, 0) == -1
+    assert lib.wm_conv2d_route(0, *cc.geom((1, 32, 8, 8, 64, 3, 1, 1)), 0, 0) == -2
+    assert lib.wm_conv2d_route(2, *g, kc.ROUTE_F_BIAS, 0) == -2
+    assert lib.wm_conv2d_route(2, *cc.geom(cc.STEM_PATCH_SHAPES[0]), kc.ROUTE_F_BIAS, 0) == -2
+    assert lib.wm_conv2d_route(1, *cc.geom(cc.STEM_PATCH_SHAPES[0]), 0, 0) == -2
+    assert lib.wm_conv2d_route(0, *g, kc.ROUTE_F_STATS, 100) == -2
+    assert lib.wm_conv2d_route(0, *g, kc.ROUTE_F_STATS, 0) == -1
+    assert lib.wm_conv2d_route(3, *g, 0, 0) == -1
+    assert lib.wm_conv2d_route(0, *g, 64, 0) == -1
+
+
 def test_product_path_fails_loudly_without_gpu_tensors():
     import torch
 

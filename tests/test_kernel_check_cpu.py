@@ -204,3 +204,194 @@ def test_float64_references_match_autograd():
     torch.testing.assert_close(rm["y"], ym.detach(), rtol=1e-12, atol=1e-14)
     for name, u in zip(("dx", "dw1", "db1", "dw2", "db2"), tt):
         torch.testing.assert_close(rm[name], u.grad, rtol=1e-10, atol=1e-12)
+
+
+# ---------------------------------------------------------------------------------------------------- convolution
+# (N, C, H, W, K, R, stride, pad): a ragged 3 x 3 / 1 with one row tile and a ragged chunk, and a 3 x 3 / 2 of two
+# images whose input gradient runs by parity class
+CONV_SHAPES = [(1, 64, 9, 11, 64, 3, 1, 1), (2, 64, 16, 16, 128, 3, 2, 1)]
+
+
+def _conv_case(family, shape, seed_error=None, emulate=False, res=True):
+    n, c, h, w, k, r, stride, pad = shape
+    p, q = kc.conv_out_hw(h, w, r, r, stride, pad)
+    i = kc.conv_inputs(family, n, h, w, c, k, r, r, p, q, seed=h)
+    tiles = kc.row_tiles(n * p * q) or [torch.arange(n * p * q)]   # (M = 99: one ragged tile stands in for the slot)
+    return i, kc.conv_ref(i["x"], i["w"], stride, pad, i["dy"], dres=i["dres"] if res else None, emulate=emulate,
+                          seed_error=seed_error, tiles=tiles)
+
+
+def _conv_f32(i, out, tiles_of="y"):
+    """the float32 restatements: dW by matmul_tn_f32 on the im2col, the statistics slot sums by colsum_f32"""
+    m = out["cols"].shape[0]
+    k = i["w"].shape[0]
+    dw = kc.matmul_tn_f32(i["dy"].reshape(m, k), out["cols"]).reshape(out["dw"].shape)
+    floor = float(2.0 ** -24 * (i["dy"].reshape(m, k).double().abs().t() @ out["cols"].abs()).max())
+    return dw, floor
+
+
+@pytest.mark.parametrize("shape", CONV_SHAPES)
+@pytest.mark.parametrize("family", kc.CONV_FAMILIES)
+def test_conv_honest_result_passes(family, shape):
+    i, ref = _conv_case(family, shape)
+    _, emul = _conv_case(family, shape, emulate=True)
+    with kc.jitter(4):
+        _, got = _conv_case(family, shape, emulate=True)
+    for key in ("y", "dx"):
+        _accept(got[key], ref[key], emul[key], f"conv {key} {family} {shape}")
+    dw32, floor = _conv_f32(i, ref)
+    rows, finite = kc.verdict(dw32 * (1 + 2.0 ** -24), ref["dw"], dw32, kc.F32_SUM_FACTOR, floor)
+    assert finite and all(m <= b for _, m, b in rows), rows
+    if family == "lattice":   # the exact tier: the emulation rounds nothing away, the float32 restatement is exact
+        kc.lattice_exact(ref)
+        for key in ("y", "dx", "dw", "stats"):
+            assert torch.equal(emul[key], ref[key]), key
+        assert torch.equal(dw32.double(), ref["dw"])
+
+
+def test_conv_ref_is_torch_conv2d():
+    F = torch.nn.functional
+    for n, c, h, w, k, r, stride, pad in CONV_SHAPES + [(1, 128, 5, 7, 64, 1, 2, 0), (2, 64, 10, 10, 64, 3, 1, 0)]:
+        i, ref = _conv_case("randn", (n, c, h, w, k, r, stride, pad), res=False)
+        x = i["x"].double().permute(0, 3, 1, 2).requires_grad_(True)
+        wt = i["w"].double().permute(0, 3, 1, 2).requires_grad_(True)
+        y = F.conv2d(x, wt, None, stride, pad)
+        y.backward(i["dy"].double().permute(0, 3, 1, 2))
+        torch.testing.assert_close(ref["y"].permute(0, 3, 1, 2), y.detach(), rtol=1e-12, atol=1e-13)
+        torch.testing.assert_close(ref["dx"].permute(0, 3, 1, 2), x.grad, rtol=1e-12, atol=1e-13)
+        torch.testing.assert_close(ref["dw"].permute(0, 3, 1, 2), wt.grad, rtol=1e-12, atol=1e-12)
+    # the cropped 4 x 4 / pad 2 form of the space-to-depth stem
+    g = torch.Generator().manual_seed(0)
+    x, wt = kc.bf(torch.randn(2, 8, 8, 16, generator=g)), kc.bf(torch.randn(64, 4, 4, 16, generator=g))
+    y = F.conv2d(x.double().permute(0, 3, 1, 2), wt.double().permute(0, 3, 1, 2), None, 1, 2)[:, :, :8, :8]
+    torch.testing.assert_close(kc.conv_ref(x, wt, 1, 2, out_hw=(8, 8))["y"].permute(0, 3, 1, 2), y, rtol=1e-12, atol=1e-13)
+
+
+# which tensors show each seeded error (a forward-only error leaves dx alone, and so on)
+CONV_ERRORS = [("wrap_border", ("y", "dx", "dw")), ("image_bleed", ("y", "dx", "dw")), ("tap_transpose", ("y", "dx", "dw")),
+               ("drop_tail", ("y", "dx", "dw")), ("one_class_missing", ("dx",)), ("res_unrounded", ("dx",)),
+               ("stats_unrounded", ("stats",))]
+
+
+def _conv_error_applies(error, shape, key):
+    n, c, h, w, k, r, stride, pad = shape
+    p, q = kc.conv_out_hw(h, w, r, r, stride, pad)
+    if error == "image_bleed":
+        return n > 1
+    if error == "one_class_missing":
+        return stride == 2
+    if error == "drop_tail":   # a tail exists: M mod 128 rows of y, N H W mod 128 rows of dx, M mod 64 pixels of the last chunk
+        return {"y": (n * p * q) % 128, "dx": (n * h * w) % 128, "dw": (n * p * q) % 64}[key] != 0
+    return True
+
+
+# big_pixel is there for what a huge value does to its neighbourhood (an overflow, a poisoned tile): the rounding error of
+# the outputs that pixel reaches IS the yardstick, and an error that lives at the image border or in the tail rows, away
+# from it, is below that.  Those three are asked of lattice, randn and offset.
+CONV_ERROR_CASES = [(f, e, k) for f in kc.CONV_FAMILIES for e, k in CONV_ERRORS
+                    if not (f == "big_pixel" and e in ("wrap_border", "image_bleed", "drop_tail"))]
+
+
+@pytest.mark.parametrize("shape", CONV_SHAPES)
+@pytest.mark.parametrize("family,error,keys", CONV_ERROR_CASES)
+def test_conv_seeded_errors_fail(family, shape, error, keys):
+    """Every seeded error is rejected by `check` on every family, and on `lattice` by plain equality with float64.
+    Two are invisible to the exact tier BY CONSTRUCTION and are asked of the other families only: on the lattice every
+    accumulator is bf16-exact, so rounding it before (res_unrounded) or after the residual add, or taking the
+    statistics from it (stats_unrounded), gives the same numbers.  stats_unrounded is also below what `check` can
+    promise on the tolerance tier (see test_conv_stats_from_accumulators_...)."""
+    i, ref = _conv_case(family, shape)
+    _, emul = _conv_case(family, shape, emulate=True)
+    _, bad = _conv_case(family, shape, seed_error=error, emulate=True)
+    dw32, floor = _conv_f32(i, ref)
+    _, bad_plain = _conv_case(family, shape, seed_error=error)
+    asked = 0
+    for key in keys:
+        if not _conv_error_applies(error, shape, key):
+            continue
+        if error in ("res_unrounded", "stats_unrounded"):
+            if family == "lattice":
+                assert torch.equal(bad[key], ref[key])   # provably invisible: see the docstring
+            continue
+        asked += 1
+        if family == "lattice":
+            assert not torch.equal(bad[key], ref[key]), f"{error} {key}: exact tier blind"
+        if key == "dw":
+            # the float32 restatement of the wrong computation (its own im2col)
+            m, k = bad["cols"].shape[0], i["w"].shape[0]
+            got = bad_plain["dw"].float()
+            rows, finite = kc.verdict(got, ref["dw"], dw32, kc.F32_SUM_FACTOR, floor)
+            assert any(mm > b for _, mm, b in rows), f"seeded error accepted -- {error} dw {family}: {rows}"
+        else:
+            _reject(bad[key], ref[key], emul[key], f"{error} {key} {family} {shape}")
+    if error not in ("res_unrounded", "stats_unrounded"):
+        assert asked or not any(_conv_error_applies(error, shape, k) for k in keys)
+
+
+@pytest.mark.parametrize("shape", CONV_SHAPES)
+@pytest.mark.parametrize("family", ["randn", "offset", "big_pixel"])
+def test_conv_rounding_place_errors(family, shape):
+    """res_unrounded and stats_unrounded differ from the honest kernel by ONE bf16 rounding per element, the size of
+    the yardstick's own error: a factor-2 bound on distribution criteria cannot tell them apart, and this test records
+    that instead of pretending.  What does see them: the statistics slots are compared with the float64 column sums of
+    the kernel's OWN stored tile under the float32 summation bound (tests/test_gpu_conv.py), which sums taken from
+    the accumulators miss by orders of magnitude -- asserted here on the same numbers."""
+    i, ref = _conv_case(family, shape)
+    _, emul = _conv_case(family, shape, emulate=True)
+    _, bad = _conv_case(family, shape, seed_error="stats_unrounded", emulate=True)
+    own = emul["stats"]                                   # float64 sums of the rounded (= stored) outputs
+    n, c, h, w, k, r, stride, pad = shape
+    m = emul["y"].numel() // k
+    tiles = kc.row_tiles(m) or [torch.arange(m)]
+    y = emul["y"].reshape(m, k)
+    bound = kc.f32_sum_bound(y, tiles)
+    assert bool(((bad["stats"][:, 0] - own[:, 0]).abs() > bound[0]).any()), "sums of the accumulators within the float32 bound"
+    _, bad = _conv_case(family, shape, seed_error="res_unrounded", emulate=True)
+    print("res_unrounded dx:", kc.verdict(bad["dx"], ref["dx"], emul["dx"])[0])
+
+
+# ---------------------------------------------------------------------------------------------------- BatchNorm-backward epilogue
+def _bnb_case(family, form, groups=2, seed_error=None, emulate=False, res=True):
+    shape = (4, 64, 8, 8, 64, 3, 1, 1)
+    n, c, h, w, k, r, stride, pad = shape
+    i = kc.conv_inputs(family, n, h, w, c, k, r, r, h, w, seed=7)
+    b = kc.bn_inputs(family, n * h * w, c, groups, seed=8)
+    conv = kc.conv_ref(i["x"], i["w"], stride, pad, i["dy"])
+    tiles = kc.pair_tiles(n, h, w)
+    out = kc.bn_dgrad_epilogue_ref(conv["dx_acc"], i["dres"] if res else None, b["bn_y"], b["mean"], b["invstd"], b["gamma"],
+                                   b["beta"], form, b["relu_x"], b["mask"], tiles, emulate=emulate, seed_error=seed_error)
+    return b, tiles, out
+
+
+# (the recomputed mask of the mean-50 `offset` rows hangs on float32 cancellation: that form is asked of lattice and randn)
+@pytest.mark.parametrize("family,form", [(f, m) for f in ("lattice", "randn", "offset") for m in ("x", "bits", "recompute")
+                                         if (f, m) != ("offset", "recompute")])
+def test_bn_dgrad_epilogue_honest_passes_and_errors_fail(family, form):
+    b, tiles, ref = _bnb_case(family, form)
+    _, _, emul = _bnb_case(family, form, emulate=True)
+    with kc.jitter(5):
+        _, _, got = _bnb_case(family, form, emulate=True)
+    if form == "recompute" and family == "randn":
+        assert kc.bn_preact_margin(b) > 8 * kc.BF16_ULP
+    _accept(got["dx"], ref["dx"], emul["dx"], f"bnb dx {family} {form}")
+    for j, key in enumerate(("g", "gy")):
+        yard = kc.tile_sums_f32(emul[key], tiles)
+        rows, finite = kc.verdict(yard * (1 + 2.0 ** -24), ref["stats"][:, j], yard, kc.F32_SUM_FACTOR,
+                                  max(kc.f32_sum_floor(emul[key][t]) for t in tiles))
+        assert finite and all(m <= bb for _, m, bb in rows), (key, rows)
+    if family == "lattice":
+        kc.lattice_exact({"dx": ref["dx"], "stats": ref["stats"]})
+        assert torch.equal(emul["dx"], ref["dx"]) and torch.equal(emul["stats"], ref["stats"])
+    errors = (["mask_off_by_channel"] if form == "bits" else []) + (["stat_uncentred"] if family != "randn" else [])
+    for error in errors:
+        _, _, bad = _bnb_case(family, form, seed_error=error, emulate=True)
+        j = 1 if error == "stat_uncentred" else 0
+        key = ("g", "gy")[j]
+        if family == "lattice":
+            assert not torch.equal(bad["stats"][:, j], ref["stats"][:, j]), error
+        yard = kc.tile_sums_f32(emul[key], tiles)
+        rows, finite = kc.verdict(kc.tile_sums_f32(bad[key], tiles), ref["stats"][:, j], yard, kc.F32_SUM_FACTOR,
+                                  max(kc.f32_sum_floor(emul[key][t]) for t in tiles))
+        assert any(m > bb for _, m, bb in rows), f"seeded error accepted -- {error} {family} {form}: {rows}"
+        if error == "mask_off_by_channel":
+            _reject(bad["dx"], ref["dx"], emul["dx"], f"{error} dx {family}")
