@@ -829,6 +829,19 @@ size_t wm_mreach_query_workspace_bytes(int m, int n, int d);
 int wm_mreach_query(const float* xq, const float* core_q, int m, const float* x, const float* core, int n, int d, int metric,
                     float inv_alpha, float* out_w, float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* Per group of columns the nearest one (HDBSCAN's soft clustering: the nearest exemplar of every cluster): for every row
+ * i of xq float32 [m][d] and every group c in [0, g), out_dist[i][c] = the smallest dist(xq_i, xe_j) over the rows j of
+ * xe float32 [e][d] with group[j] == c under the same distance function (bit-equal to what wm_knn_query returns for the
+ * pair; exactly 0 for a row bit-equal to xe_j) and out_j[i][c] = the lowest j that attains it; a group without a column
+ * gives +inf / -1.  Precondition: group int32 [e] is non-decreasing with values in [0, g); with a decreasing sequence or
+ * a value outside the range the outputs are unspecified (such a column is never used as an index: no access leaves the
+ * buffers).  out_dist float32 [m][g], out_j int32 [m][g].  m, e, g >= 1; xq, xe and the workspace 16-byte aligned.  The
+ * workspace is one [m][g] plane of (distance, index) per column slice, at most 16 slices (16 * m * g * 8 bytes) and
+ * nothing but padding when the rows alone fill the machine (m > 65 472).  No atomics, no memset: two calls give the same
+ * bits. */
+size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g);
+int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
+                      float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas

@@ -6,7 +6,7 @@ notebooks/3.1-Embeddings-clustering.ipynb and 3.2-Embeddings-SSL-categories.ipyn
     python scripts/embedding_clustering_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
                                                [--trials 30] [--design random|grid] [--seed 0] [--rows N]
                                                [--metrics euclidean manhattan] [--no-scale] [--out DIR]
-                                               [--holdout N]
+                                               [--holdout N] [--soft]
 
 What the notebooks do, and where it is here:
   StandardScaler().fit_transform(embeddings)              -> retrieval.StandardScaler (skipped with --no-scale)
@@ -36,6 +36,13 @@ chosen trial: the Pareto row with the best silhouette), summary.json.
 holdout_labels.npy, holdout_probabilities.npy, holdout_outlier_scores.npy, and in summary.json `holdout`,
 `holdout_noise` and `holdout_homogeneity` (truth against the predicted label over the held-out rows not labelled noise;
 null when there are none).
+
+--soft adds the soft clustering of the chosen trial (cluster.all_points_membership_vectors / membership_vector: how
+strongly every row, noise rows included, belongs to every cluster): membership.npy [n, n_clusters], exemplars.npz
+(`rows`: the exemplar rows of all clusters, `cluster`: the cluster of each), with --holdout also
+holdout_membership.npy [N, n_clusters]; and in summary.json `soft_noise_above_half` (the share of the noise rows whose
+largest membership exceeds 0.5; null without noise rows) and `soft_mean_row_sum` (the mean probability of belonging
+to any cluster).
 """
 from __future__ import annotations
 
@@ -147,6 +154,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--out", default="clustering_out")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--holdout", type=int, default=0, help="keep the last N rows out of the sweep and predict them")
+    ap.add_argument("--soft", action="store_true", help="write the chosen trial's membership vectors and exemplars")
     a = ap.parse_args(argv)
 
     import torch
@@ -180,7 +188,7 @@ def main(argv=None) -> dict:
         key = (p["metric"], p["min_samples"])
         if key not in trees:
             trees[key] = cluster.HDBSCAN(min_cluster_size=p["min_cluster_size"], min_samples=p["min_samples"],
-                                         metric=p["metric"], prediction_data=a.holdout > 0).fit(x)
+                                         metric=p["metric"], prediction_data=a.holdout > 0 or a.soft).fit(x)
         model = trees[key].refit(min_cluster_size=p["min_cluster_size"],
                                  cluster_selection_epsilon=p["cluster_selection_epsilon"])
         labels = model.labels_.copy()
@@ -213,10 +221,11 @@ def main(argv=None) -> dict:
         for c, (m, dr, ir) in enumerate(zip(members, dist.cpu().tolist(), idx.cpu().tolist())):
             near = [(j, round(dd, 4), int(truth[j])) for j, dd in zip(ir, dr) if j != m][:5]
             print(f"cluster {c}: member {m} (failure code {int(truth[m])}); nearest (row, L2, failure code): {near}")
-        if a.holdout:
+        if a.holdout or a.soft:
             p = trials[chosen]
             model = trees[(p["metric"], p["min_samples"])].refit(min_cluster_size=p["min_cluster_size"],
                                                                  cluster_selection_epsilon=p["cluster_selection_epsilon"])
+        if a.holdout:
             h_labels, h_prob = cluster.approximate_predict(model, x_hold)
             h_scores = cluster.approximate_predict_scores(model, x_hold)
             np.save(out / "holdout_labels.npy", h_labels)
@@ -227,6 +236,19 @@ def main(argv=None) -> dict:
                            holdout_homogeneity=cluster.homogeneity_score(truth_hold[keep], h_labels[keep]) if keep.any() else None)
             print(f"held-out rows: {int(keep.sum())} of {a.holdout} assigned to a cluster, homogeneity "
                   f"{summary['holdout_homogeneity']}")
+        if a.soft:
+            member = cluster.all_points_membership_vectors(model)
+            np.save(out / "membership.npy", member)
+            ex = model.exemplar_indices_
+            np.savez(out / "exemplars.npz", rows=np.concatenate(ex) if ex else np.zeros(0, dtype=np.int64),
+                     cluster=np.repeat(np.arange(len(ex)), [r.size for r in ex]).astype(np.int64))
+            if a.holdout:
+                np.save(out / "holdout_membership.npy", cluster.membership_vector(model, x_hold))
+            noise = labels == -1
+            summary.update(soft_noise_above_half=float((member[noise].max(axis=1) > 0.5).mean()) if noise.any() else None,
+                           soft_mean_row_sum=float(member.sum(axis=1).mean()))
+            print(f"soft clustering: {sum(r.size for r in ex)} exemplars; mean row sum {summary['soft_mean_row_sum']:.4f}; noise rows "
+                  f"with a membership above 0.5: {summary['soft_noise_above_half']}")
     (out / "summary.json").write_text(json.dumps(summary, indent=1))
     print(f"{len(rows)} trials on {x.shape[0]} x {x.shape[1]} in {wall:.2f} s with {len(trees)} spanning trees; "
           f"{len(front)} Pareto-optimal rows -> {out}")

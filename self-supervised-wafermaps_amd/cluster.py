@@ -23,6 +23,10 @@ New rows (`HDBSCAN(prediction_data=True)`, `approximate_predict`, `approximate_p
 pass (wm_mreach_query) finds, for every new row, the fitted row nearest in mutual reachability; the walk from that
 row through the condensed tree to a label, a membership strength and a GLOSH outlier score is host code
 (`assign_from_tree`), as is `outlier_scores_` of the fitted rows (`glosh`).
+
+Soft clustering (`exemplar_indices_`, `all_points_membership_vectors`, `membership_vector`): one rectangular pass
+(wm_group_min_dist) gives every row its distance to the nearest exemplar of every cluster; the merge heights in the
+condensed tree and the membership vectors themselves are host code (`exemplars_from_tree`, `membership_from_tree`).
 """
 from __future__ import annotations
 
@@ -445,6 +449,21 @@ def glosh(condensed_tree, n: int) -> np.ndarray:
     return _glosh_ratio(spread[pt_parent], pt_lam)
 
 
+def _walk(root, cl_parent, birth, pt_parent, pt_lam, neighbor, weight):
+    """The walk of a new row into the condensed tree (assign_from_tree states the rule): (C int64 [m], the cluster the
+    row would fall out of; lam float64 [m] = 1 / weight, inf at weight 0)."""
+    with np.errstate(divide="ignore"):
+        lam = 1.0 / weight
+    at = pt_parent[neighbor]
+    climb = pt_lam[neighbor] > lam
+    while True:
+        move = climb & (at != root) & (birth[at] >= lam)
+        if not move.any():
+            break
+        at = np.where(move, cl_parent[at], at)
+    return at, lam
+
+
 def assign_from_tree(condensed_tree, n: int, selected, neighbor, weight, cluster_selection_epsilon: float = 0.0,
                      allow_single_cluster: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Labels, membership strengths and outlier scores of new rows from the fitted condensed tree: (labels int64 [m],
@@ -478,16 +497,7 @@ def assign_from_tree(condensed_tree, n: int, selected, neighbor, weight, cluster
     root = n
     if selected.size and (selected.min() < root or selected.max() >= n_nodes):
         raise ValueError("selected must hold cluster ids of the condensed tree")
-    with np.errstate(divide="ignore"):
-        lam = 1.0 / weight
-    # ---- C: the cluster the row would fall out of
-    at = pt_parent[neighbor]
-    climb = pt_lam[neighbor] > lam
-    while True:
-        move = climb & (at != root) & (birth[at] >= lam)
-        if not move.any():
-            break
-        at = np.where(move, cl_parent[at], at)
+    at, lam = _walk(root, cl_parent, birth, pt_parent, pt_lam, neighbor, weight)
     # ---- S: the nearest selected cluster from C upwards (the root stands for "none", as in labels_from_mst)
     label_at = np.full(n_nodes, -1, dtype=np.int64)
     label_at[selected] = np.arange(selected.size)
@@ -506,6 +516,133 @@ def assign_from_tree(condensed_tree, n: int, selected, neighbor, weight, cluster
         prob = np.where((d_s == 0.0) | np.isinf(lam), 1.0, np.minimum(lam, d_s) / d_s)
     prob = np.where(has, prob, 0.0)
     return labels.astype(np.int64), prob, _glosh_ratio(spread[at], lam)
+
+
+def _checked_selected(selected, root: int, n_nodes: int) -> np.ndarray:
+    selected = np.asarray(selected, dtype=np.int64)
+    if selected.ndim != 1 or (np.diff(selected) <= 0).any():
+        raise ValueError("selected must be sorted condensed-tree ids")
+    if selected.size and (selected.min() < root or selected.max() >= n_nodes):
+        raise ValueError("selected must hold cluster ids of the condensed tree")
+    return selected
+
+
+def exemplars_from_tree(condensed_tree, n: int, selected) -> list:
+    """The exemplar rows of every selected cluster (the `hdbscan` package's `exemplars_`, as row indices): a list of
+    ascending int64 arrays, one per entry of `selected`.  For every leaf cluster L of the condensed tree below S (S
+    itself when it has no cluster child) the exemplars are L's own rows that leave last, those whose lambda equals
+    death[L], the largest lambda among L's rows.  A leaf counts for the nearest selected cluster from it upwards (the
+    flat clusterings of labels_from_mst never select a cluster below another one)."""
+    n = int(n)
+    n_nodes, cl_parent, _, death, _, pt_parent, pt_lam = _tree_tables(condensed_tree, n)
+    selected = _checked_selected(selected, n, n_nodes)
+    is_leaf = np.ones(n_nodes, dtype=bool)
+    is_leaf[cl_parent[n + 1:]] = False  # (the root is its own parent: only real children are listed)
+    cand = np.flatnonzero(is_leaf[pt_parent] & (pt_lam == death[pt_parent]))
+    under = np.full(n_nodes, -1, dtype=np.int64)  # position in `selected` of the nearest selected cluster from a node up
+    under[selected] = np.arange(selected.size)
+    for c in range(n + 1, n_nodes):  # (ids grow downwards: a parent is numbered before its children)
+        if under[c] < 0:
+            under[c] = under[cl_parent[c]]
+    owner = under[pt_parent[cand]]
+    return [cand[owner == s].astype(np.int64) for s in range(selected.size)]
+
+
+def membership_from_tree(condensed_tree, n: int, selected, at, lam, exemplar_dist, return_parts: bool = False):
+    """Soft-clustering membership vectors from the fitted condensed tree: float64 [m, C], one column per entry of
+    `selected`, every entry in [0, 1] and every row summing to the row's probability of belonging to any cluster.  Pure
+    numpy on float64; the formulas are the `hdbscan` package's prediction module's, with two deliberate differences
+    marked below.
+
+    `at` [m]: the condensed cluster a row sits in; `lam` [m]: the lambda at which it leaves it (an infinite one is
+    replaced by the largest lambda below `at`, or where that is infinite too by the largest finite lambda of the
+    tree); `exemplar_dist` [m, C]: the distance to the nearest exemplar of every selected cluster (inf: none).
+    Infinite lambdas of the tree itself (exact duplicates: a cluster that holds min_cluster_size of them has an
+    infinite death, and so have its ancestors) count as the largest finite lambda of the tree throughout, the value
+    an infinite `lam` gets: every score and probability stays a ratio of finite numbers, a duplicate is the last to
+    leave its cluster (p = 1 there), and the other rows of the model are scored against a finite depth.  (The limit of
+    the formulas at an infinite death would instead give every row under such a cluster p = 0.)  Per row i and selected
+    cluster S_c, with D = glosh's propagated death, capped so:
+      distance vector   a_c = 1 / exemplar_dist[i, c], normalised to sum 1; with a zero distance the indicator of the
+                        zero entries, normalised; 0 at an infinite distance;
+      merge height      h_c = lam_i when S_c is at_i, above it or below it; otherwise the lambda at which their lowest
+                        common ancestor split (the birth of its children);
+      score             s_c = m_c / (m_c - h_c) with m_c = max(lam_i, D[S_c]), +inf at a zero denominator (deliberate:
+                        the package adds a small constant to the denominator instead);
+      outlier vector    the softmax of s over c; with an infinite s the indicator of the infinite ones, normalised;
+      probability       p_i = h* / max(lam_i, D[S_c*]) with h* the largest h_c and c* the first cluster that attains
+                        it; 0 at a zero denominator;
+      result            a * outlier, normalised to sum 1, times p_i (deliberate: the same formula for fitted and for
+                        new rows, where the package raises the two factors to different powers in its two functions).
+    A row whose product vanishes everywhere (every distance infinite) is all zeros.  Where the root is the only selected
+    cluster (allow_single_cluster) the one column holds p_i = lam_i / max(lam_i, the largest lambda of the tree): how far
+    down the tree the row stays, 1 for the last rows to leave.  C == 0 gives [m, 0].  With `return_parts` a dict of the
+    intermediate arrays (a, h, s, outlier [m, C]; p, lam [m]) follows."""
+    n = int(n)
+    n_nodes, cl_parent, birth, _, spread, _, _ = _tree_tables(condensed_tree, n)
+    selected = _checked_selected(selected, n, n_nodes)
+    at = np.asarray(at, dtype=np.int64)
+    lam = np.asarray(lam, dtype=np.float64).copy()
+    dist = np.asarray(exemplar_dist, dtype=np.float64)
+    m, n_sel = at.shape[0], selected.size
+    if at.ndim != 1 or lam.shape != (m,) or dist.shape != (m, n_sel):
+        raise ValueError("at [m], lam [m] and exemplar_dist [m, C] expected")
+    if m and (at.min() < n or at.max() >= n_nodes):
+        raise ValueError("at must hold cluster ids of the condensed tree")
+    if np.isnan(lam).any() or (lam < 0).any() or np.isnan(dist).any() or (dist < 0).any():
+        raise ValueError("lam and exemplar_dist must not be negative")
+    if n_sel == 0:
+        out = np.zeros((m, 0))
+        return (out, {"a": out, "h": out, "s": out, "outlier": out, "p": np.zeros(m), "lam": lam}) if return_parts else out
+    all_lam = condensed_tree["lambda_val"]
+    top_lam = float(all_lam[np.isfinite(all_lam)].max()) if np.isfinite(all_lam).any() else 0.0
+    spread, birth = np.minimum(spread, top_lam), np.minimum(birth, top_lam)  # (unchanged where the tree is finite)
+    inf_lam = np.isinf(lam)
+    lam[inf_lam] = spread[at[inf_lam]]
+    # ---- per (tree cluster k, selected cluster c): on one lineage or not, and where not the split lambda of their
+    # lowest common ancestor.  Ids grow downwards, so one pass in id order sees every parent before its children.
+    k_nodes = n_nodes - n
+    par = cl_parent[n:] - n
+    sel = selected - n
+    above = np.zeros((k_nodes, n_sel), dtype=bool)  # S_c is k or an ancestor of k
+    above[sel, np.arange(n_sel)] = True
+    below = np.zeros((k_nodes, n_sel), dtype=bool)  # S_c is a descendant of k
+    for k in range(1, k_nodes):
+        above[k] |= above[par[k]]
+    for k in range(k_nodes - 1, 0, -1):
+        below[par[k]] |= below[k] | (sel == k)
+    lineage = above | below
+    split = np.zeros((k_nodes, n_sel))
+    for k in range(1, k_nodes):  # (off the lineage the parent is either the common ancestor or off it as well)
+        split[k] = np.where(lineage[par[k]], birth[n + k], split[par[k]])
+    big = spread[selected]  # D[S_c]
+    # ---- per row
+    lam_c = lam[:, None]
+    h = np.where(lineage[at - n], lam_c, split[at - n])
+    m_c = np.maximum(lam_c, big[None, :])
+    den = m_c - h
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.where(den == 0.0, np.inf, m_c / den)
+        inv = np.where(np.isinf(dist), 0.0, 1.0 / dist)
+    zero = dist == 0.0
+    a = np.where(zero.any(axis=1, keepdims=True), zero.astype(np.float64), inv)
+    a_sum = a.sum(axis=1, keepdims=True)
+    a = np.divide(a, a_sum, out=np.zeros_like(a), where=a_sum > 0)
+    s_inf = np.isinf(s)
+    with np.errstate(invalid="ignore", over="ignore"):
+        soft = np.exp(np.where(s_inf, -np.inf, s) - np.where(s_inf, -np.inf, s).max(axis=1, keepdims=True))
+    soft = np.where(s_inf.any(axis=1, keepdims=True), s_inf.astype(np.float64), soft)
+    outlier = soft / soft.sum(axis=1, keepdims=True)
+    c_star = np.argmax(h, axis=1)
+    h_star = h[np.arange(m), c_star]
+    p_den = np.maximum(lam, big[c_star])
+    p = np.divide(h_star, p_den, out=np.zeros(m), where=p_den != 0.0)
+    prod = a * outlier
+    p_sum = prod.sum(axis=1, keepdims=True)
+    out = np.divide(prod, p_sum, out=np.zeros_like(prod), where=p_sum > 0) * p[:, None]
+    if return_parts:
+        return out, {"a": a, "h": h, "s": s, "outlier": outlier, "p": p, "lam": lam}
+    return out
 
 
 class HDBSCAN:
@@ -535,7 +672,7 @@ class HDBSCAN:
         self.gen_min_span_tree, self.prediction_data = bool(gen_min_span_tree), bool(prediction_data)
         self.labels_ = self.probabilities_ = self.condensed_tree_ = self.minimum_spanning_tree_ = None
         self.selected_clusters_ = self.outlier_scores_ = None
-        self._n = self._k = self._train = self._core = None
+        self._n = self._k = self._train = self._core = self._exemplars = None
 
     def fit(self, x) -> "HDBSCAN":
         k = self.min_cluster_size if self.min_samples is None else int(self.min_samples)
@@ -564,7 +701,18 @@ class HDBSCAN:
             t[:, 0].astype(np.int64), t[:, 1].astype(np.int64), t[:, 2], self._n, self.min_cluster_size,
             self.cluster_selection_epsilon, self.cluster_selection_method, self.allow_single_cluster, return_selected=True)
         self.outlier_scores_ = glosh(self.condensed_tree_, self._n)
+        self._exemplars = None
         return self
+
+    @property
+    def exemplar_indices_(self):
+        """The exemplar rows of every cluster (`exemplars_from_tree`), a list in label order; None before `fit`.
+        Computed on first access after a `fit` / `refit`."""
+        if self.condensed_tree_ is None:
+            return None
+        if self._exemplars is None:
+            self._exemplars = exemplars_from_tree(self.condensed_tree_, self._n, self.selected_clusters_)
+        return self._exemplars
 
     def fit_predict(self, x) -> np.ndarray:
         return self.fit(x).labels_
@@ -625,20 +773,33 @@ def mreach_query(xq, core_q, x, core, metric: str = "euclidean", alpha: float = 
     return w, dist, j
 
 
-def _predict(model: "HDBSCAN", rows):
+def _require_prediction_data(model: "HDBSCAN"):
     if model.minimum_spanning_tree_ is None:
         raise RuntimeError("HDBSCAN prediction before fit")
     if model._train is None or model._core is None:
         raise ValueError("this model keeps no prediction data: construct it with HDBSCAN(..., prediction_data=True)")
+
+
+def _nearest_fitted(model: "HDBSCAN", rows):
+    """What every prediction for new rows starts from: (prepared rows, neighbor int64 [m], weight float64 [m]), the
+    fitted row nearest in mutual reachability and that mutual reachability; (rows, None, None) when there are none."""
+    _require_prediction_data(model)
     xq = _prep(rows)
     if xq.shape[1] != model._train.shape[1]:
         raise ValueError(f"rows have {rows.shape[1]} features, the model was fitted on {model._train.shape[1]} (after padding)")
     if xq.shape[0] == 0:
-        return np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0)
+        return xq, None, None
     core_q = query_core_distances(xq, model._train, model._k, model.metric)
     w, _, j = mreach_query(xq, core_q, model._train, model._core, model.metric, model.alpha)
-    return assign_from_tree(model.condensed_tree_, model._n, model.selected_clusters_, j.cpu().numpy().astype(np.int64),
-                            w.cpu().numpy().astype(np.float64), model.cluster_selection_epsilon, model.allow_single_cluster)
+    return xq, j.cpu().numpy().astype(np.int64), w.cpu().numpy().astype(np.float64)
+
+
+def _predict(model: "HDBSCAN", rows):
+    _, j, w = _nearest_fitted(model, rows)
+    if j is None:
+        return np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0)
+    return assign_from_tree(model.condensed_tree_, model._n, model.selected_clusters_, j, w, model.cluster_selection_epsilon,
+                            model.allow_single_cluster)
 
 
 def approximate_predict(model: "HDBSCAN", rows) -> Tuple[np.ndarray, np.ndarray]:
@@ -657,6 +818,81 @@ def approximate_predict_scores(model: "HDBSCAN", rows) -> np.ndarray:
     """GLOSH outlier scores of new rows under a model fitted with `prediction_data=True`: float64 [m] in [0, 1]
     (see `assign_from_tree`; the search and the core-distance convention are `approximate_predict`'s)."""
     return _predict(model, rows)[2]
+
+
+# ------------------------------------------------------------------------------------------------ GPU: soft clustering
+
+
+def group_min_distances(xq, xe, group, n_groups: int, metric: str = "euclidean"):
+    """Per row of xq [m, d] and per group c in [0, n_groups) the nearest row of xe [e, d] among those with
+    group[j] == c: (dist float32 [m, n_groups], j int32 [m, n_groups]) on the device (wm_group_min_dist); j is the lowest
+    index into xe that attains the distance, and a group without a row gives inf / -1.  `group`: e integers in
+    [0, n_groups) in any order (a tensor or an array): the columns are sorted by (group, index) for the kernel, which
+    wants the groups in runs, and the indices mapped back.  The distances are `manifold.knn_query`'s bits."""
+    import torch
+
+    code = metric_code(metric)
+    xq, xe = _prep(xq), _prep(xe)
+    (m, d), e, g = xq.shape, xe.shape[0], int(n_groups)
+    if xe.shape[1] != d:
+        raise ValueError(f"the rows have {d} features (padded), the grouped rows {xe.shape[1]}")
+    group = torch.as_tensor(group)
+    if group.shape != (e,) or group.dtype not in (torch.int32, torch.int64):
+        raise ValueError("group: one int32 / int64 id per row of xe expected")
+    if g < 0 or (e and (int(group.min()) < 0 or int(group.max()) >= g)):
+        raise ValueError(f"group ids must lie in [0, n_groups = {g})")
+    dist = torch.full((m, g), float("inf"), dtype=torch.float32, device=xq.device)
+    j = torch.full((m, g), -1, dtype=torch.int32, device=xq.device)
+    if m == 0 or e == 0 or g == 0:
+        return dist, j  # (nothing to compare)
+    order = torch.argsort(group.to(xq.device), stable=True)  # by (group, index)
+    xs = xe[order].contiguous()
+    gs = group.to(xq.device)[order].to(torch.int32).contiguous()
+    lib = _lib.load()
+    need = lib.wm_group_min_dist_workspace_bytes(m, e, d, g)
+    if need == 0:
+        raise ValueError(f"group_min_distances: unsupported sizes m={m} e={e} d={d} n_groups={g}")
+    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    check(lib.wm_group_min_dist(ptr(xq), m, ptr(xs), ptr(gs), e, d, code, g, ptr(dist), ptr(j), ptr(ws), need, stream_ptr()),
+          "wm_group_min_dist")
+    back = order.to(torch.int32)[j.clamp(min=0).long()]
+    return dist, torch.where(j >= 0, back, j)
+
+
+def _exemplar_distances(model: "HDBSCAN", xq) -> np.ndarray:
+    """float64 [m, C]: the distance of every prepared row to the nearest exemplar of every cluster of the model."""
+    import torch
+
+    ex = model.exemplar_indices_
+    rows = np.concatenate(ex) if ex else np.zeros(0, dtype=np.int64)
+    group = np.repeat(np.arange(len(ex)), [r.size for r in ex]) if ex else np.zeros(0, dtype=np.int64)
+    xe = model._train[torch.from_numpy(rows).to(model._train.device)]
+    return group_min_distances(xq, xe, torch.from_numpy(group), len(ex), model.metric)[0].cpu().numpy().astype(np.float64)
+
+
+def all_points_membership_vectors(model: "HDBSCAN") -> np.ndarray:
+    """Soft clustering of the fitted rows under a model fitted with `prediction_data=True`: float64 [n, C], one column
+    per cluster in label order (`membership_from_tree`, which states the formulas and what the one column of a
+    single root cluster holds).  A row sits in its own condensed parent at its own lambda; the distances to the
+    clusters' nearest exemplars (`exemplar_indices_`) are one pass of wm_group_min_dist over the stored matrix.  The
+    name is the `hdbscan` package's.  A model that follows a `refit` answers under the relabelling."""
+    _require_prediction_data(model)
+    _, _, _, _, _, pt_parent, pt_lam = _tree_tables(model.condensed_tree_, model._n)
+    return membership_from_tree(model.condensed_tree_, model._n, model.selected_clusters_, pt_parent, pt_lam,
+                                _exemplar_distances(model, model._train))
+
+
+def membership_vector(model: "HDBSCAN", rows) -> np.ndarray:
+    """Soft clustering of new rows [m, d] under a model fitted with `prediction_data=True`: float64 [m, C].  A new row
+    sits in the cluster C and at the lambda 1 / weight of `approximate_predict`'s walk (the same search, the same
+    code); the rest is `all_points_membership_vectors`'.  The refusals are `approximate_predict`'s."""
+    xq, j, w = _nearest_fitted(model, rows)
+    if j is None:
+        return np.zeros((0, model.selected_clusters_.size))
+    n = model._n
+    _, cl_parent, birth, _, _, pt_parent, pt_lam = _tree_tables(model.condensed_tree_, n)
+    at, lam = _walk(n, cl_parent, birth, pt_parent, pt_lam, j, w)
+    return membership_from_tree(model.condensed_tree_, n, model.selected_clusters_, at, lam, _exemplar_distances(model, xq))
 
 
 # ------------------------------------------------------------------------------------------------ scores

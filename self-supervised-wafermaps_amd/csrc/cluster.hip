@@ -11,7 +11,10 @@
 //                         every square mode sets to (x, n);
 //   wm_mreach_query       for the rows of a second matrix the row of x nearest in mutual reachability
 //                         max(core_q[i], core[c], dist * inv_alpha), equal weights resolved by the plain distance and then
-//                         by the index (what HDBSCAN's prediction for new rows starts from).
+//                         by the index (what HDBSCAN's prediction for new rows starts from);
+//   wm_group_min_dist     for the rows of a second matrix, per group of columns (runs of equal group ids: the exemplars
+//                         of one cluster) the nearest column and its distance (what HDBSCAN's soft clustering starts
+//                         from).
 //
 // ONE distance function serves all of them (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
@@ -37,8 +40,27 @@
 //   min edge  every thread keeps the best (w, j) of its TM rows in registers; one LDS reduction at the end;
 //   query     the same without the component filter and with the plain distance carried between w and j;
 //   sums      distances -> LDS tile; the row's owner adds them in column order, in double, and flushes the running sum
-//             to out[i][label] whenever the label changes (rows sorted by label: once per cluster).
-// Core, knn, min edge and query split the columns into slices (grid.y) whose partial results a second small kernel combines in a
+//             to out[i][label] whenever the label changes (rows sorted by label: once per cluster);
+//   group min the sums shape with a running (best distance, its column) in place of the running sum: distances -> LDS
+//             tile; the row's owner scans the 64 columns in ascending order (a later column replaces the best only when
+//             strictly nearer: the lowest index wins a tie) and, when the group id changes, stores the finished group's
+//             pair and +inf / -1 for the ids it skipped.  Group ids do not decrease, so every out[i][c] is stored
+//             exactly once: no memset.  What was chosen and why: the work is m rows (12 k .. 811 k) against a few
+//             hundred to a few thousand columns, so the rows carry the parallelism.  TM = 4 (64-row tiles, 35 KB of
+//             LDS, four workgroups per CU): the owners are then exactly one full wave, the LDS array stays far from
+//             its limit (8 ds_read_b128 = 32 LDS cycles per wave against 128 VALU instructions = 512 cycles per 4
+//             features), and 12 449 rows give 195 row tiles.  That alone would leave CUs idle, so the columns are cut
+//             into slices as in the other modes (about a thousand workgroups in all, but at most 16 slices: the
+//             workspace holds one [m][g] plane of pairs per slice, 16 x the result at the most, of which a slice
+//             touches only its own groups; 1000 rows against 59 column tiles then still give 240 workgroups).  A slice stores only the groups
+//             it meets (the first slice also the empty ones before, the last those behind), into its own [m][g] plane
+//             of the workspace; cl_group_min_merge takes, per (row, group), the slices whose id range holds the group
+//             in slice order -- ascending columns, so "strictly nearer" again keeps the lowest index.  With one slice
+//             (m >= 64 k rows) the kernel stores straight into the outputs and nothing is merged.  Against the
+//             keep-best-in-registers shape: a thread's four columns (tx + 16 c) interleave the groups, so it would need
+//             a best per (row, group in the tile) and a reduction per group; the owner scan costs one wave 64 LDS reads
+//             and compares per tile, about a quarter of the pair work at d = 52 and a fortieth at d = 512.
+// Core, knn, min edge, query and group min split the columns into slices (grid.y) whose partial results a second small kernel combines in a
 // fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
 // atomics anywhere: two calls give the same bits.
 // Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
@@ -53,7 +75,8 @@ constexpr int CL_KC = 32;            // features per staged chunk
 constexpr int CL_LDK = CL_KC + 4;    // LDS row pitch of a staged chunk (floats)
 constexpr int CL_LDD = CL_COLS + 1;  // LDS row pitch of a distance tile (floats)
 constexpr int CL_MAXK = 64;
-constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3, CL_MREACHQ = 4;
+constexpr int CL_GROUPMIN_SLICES = 16;  // group min: at most this many column slices (the workspace: as many result planes)
+constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3, CL_MREACHQ = 4, CL_GROUPMIN = 5;
 // the modes whose per-row best stays in registers (no distance tile in LDS)
 constexpr bool cl_keeps_best(int mode) { return mode == CL_MINEDGE || mode == CL_MREACHQ; }
 
@@ -86,10 +109,13 @@ struct ClArgs {
   // query (with core, inv_alpha, part_w, part_j)
   const float* core_q;  // [nr]
   float* part_d;        // [slices][nr]
-  // sums
+  // sums; group min: the columns' group ids, non-decreasing, and the number of groups
   const int* labels;
   int n_clusters;
   double* out;  // [n][n_clusters]
+  // group min: [slices][nr][n_clusters] (the outputs themselves when there is one slice)
+  float* group_d;
+  int* group_j;
 };
 
 template <int MODE, int TM>
@@ -98,7 +124,7 @@ constexpr size_t cl_lds_bytes(int kl) {
   if (!cl_keeps_best(MODE)) f += (size_t)16 * TM * CL_LDD;
   if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
   if (MODE == CL_KNN) f += (size_t)2 * 16 * TM * kl;
-  if (MODE == CL_SUMS) f += CL_COLS;
+  if (MODE == CL_SUMS || MODE == CL_GROUPMIN) f += CL_COLS;
   return f * sizeof(float);
 }
 
@@ -127,6 +153,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   int bj[TM];
   int cur = -1;
   double run = 0.0;
+  [[maybe_unused]] float gbest = INFINITY;  // group min: the owner's best of the group `cur` so far and its column
+  [[maybe_unused]] int gj = -1;
   if constexpr (MODE == CL_MINEDGE) {
 #pragma unroll
     for (int r = 0; r < TM; ++r) {
@@ -264,7 +292,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
           Dt[(ty + 16 * r) * CL_LDD + tx + 16 * c] = j0 + tx + 16 * c < n ? cl_finish<METRIC>(acc[r][c]) : INFINITY;
-      if constexpr (MODE == CL_SUMS) {
+      if constexpr (MODE == CL_SUMS || MODE == CL_GROUPMIN) {
         if (t < CL_COLS) reinterpret_cast<int*>(extra)[t] = j0 + t < n ? p.labels[j0 + t] : -1;
       }
       __syncthreads();
@@ -291,6 +319,34 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
               kth = L[k - 1];
             }
           }
+        } else if constexpr (MODE == CL_GROUPMIN) {
+          const int* lab = reinterpret_cast<const int*>(extra);
+          const size_t at = ((size_t)blockIdx.y * nr + i0 + t) * p.n_clusters;
+          float* od = p.group_d + at;
+          int* oj = p.group_j + at;
+          for (int c = 0; c < CL_COLS; ++c) {
+            const int l = lab[c];
+            if (l < 0 || l >= p.n_clusters) continue;
+            if (l != cur) {
+              if (cur >= 0) {
+                od[cur] = gbest;
+                oj[cur] = gj;
+              }
+              // the ids skipped are empty groups; the first slice also owns those before its first column
+              for (int q = cur >= 0 ? cur + 1 : (blockIdx.y == 0 ? 0 : l); q < l; ++q) {
+                od[q] = INFINITY;
+                oj[q] = -1;
+              }
+              cur = l;
+              gbest = INFINITY;
+              gj = -1;
+            }
+            const float v = row[c];
+            if (gj < 0 || v < gbest) {
+              gbest = v;
+              gj = j0 + c;
+            }
+          }
         } else {
           const int* lab = reinterpret_cast<const int*>(extra);
           double* orow = p.out + (size_t)(i0 + t) * p.n_clusters;
@@ -312,6 +368,21 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   // ---- the slice's result
   if constexpr (MODE == CL_SUMS) {
     if (t < ROWS && i0 + t < nr && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
+  }
+  if constexpr (MODE == CL_GROUPMIN) {
+    if (t < ROWS && i0 + t < nr) {
+      const size_t at = ((size_t)blockIdx.y * nr + i0 + t) * p.n_clusters;
+      if (cur >= 0) {
+        p.group_d[at + cur] = gbest;
+        p.group_j[at + cur] = gj;
+      }
+      if (blockIdx.y == gridDim.y - 1) {  // the last slice owns the empty groups behind its last column
+        for (int q = cur + 1; q < p.n_clusters; ++q) {
+          p.group_d[at + q] = INFINITY;
+          p.group_j[at + q] = -1;
+        }
+      }
+    }
   }
   if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
     if (t < ROWS && i0 + t < nr) {
@@ -485,17 +556,49 @@ __global__ __launch_bounds__(CL_THREADS) void cl_mreach_query_merge(const float*
   out_j[i] = j;
 }
 
+// Per (row, group) the slices' (distance, column) in slice order.  A slice has stored the ids from its first column's
+// group to its last column's (the first slice from 0, the last up to g - 1) and nothing else, so only those planes are
+// read; a group no slice holds is empty.  Slices ascend in the columns: "strictly nearer" keeps the lowest column.
+__global__ __launch_bounds__(CL_THREADS) void cl_group_min_merge(const float* __restrict__ pd, const int* __restrict__ pj,
+                                                                 const int* __restrict__ group, int slices,
+                                                                 int tiles_per_slice, int m, int e, int g,
+                                                                 float* __restrict__ out_d, int* __restrict__ out_j) {
+  const size_t total = (size_t)m * g;
+  for (size_t q = (size_t)blockIdx.x * CL_THREADS + threadIdx.x; q < total; q += (size_t)gridDim.x * CL_THREADS) {
+    const int c = (int)(q % g);
+    float best = INFINITY;
+    int j = -1;
+    for (int s = 0; s < slices; ++s) {
+      const int first = s * tiles_per_slice * CL_COLS;
+      const int last = min(first + tiles_per_slice * CL_COLS, e) - 1;
+      const int lo = s == 0 ? 0 : group[first];
+      const int hi = s == slices - 1 ? g - 1 : group[last];
+      if (c < lo || c > hi) continue;
+      const float ds = pd[(size_t)s * total + q];
+      const int js = pj[(size_t)s * total + q];
+      if (js >= 0 && (j < 0 || ds < best)) {
+        best = ds;
+        j = js;
+      }
+    }
+    out_d[q] = j < 0 ? INFINITY : best;
+    out_j[q] = j;
+  }
+}
+
 struct ClGrid {
   int row_tiles, col_tiles, slices, tiles_per_slice;
 };
 // Column slices so that about a thousand workgroups exist (four per CU); every slice holds at least one tile.  m rows
-// (the row operand) against n columns; the square modes pass n for both.
-inline ClGrid cl_grid(int m, int n, int rows, bool sliced) {
+// (the row operand) against n columns; the square modes pass n for both.  max_slices: the group-min mode's cap (its
+// workspace is a whole [m][g] plane per slice).
+inline ClGrid cl_grid(int m, int n, int rows, bool sliced, int max_slices = 1 << 30) {
   ClGrid g;
   g.row_tiles = wm_cdiv(m, rows);
   g.col_tiles = wm_cdiv(n, CL_COLS);
   int want = sliced ? wm_cdiv(1024, g.row_tiles) : 1;
   if (want > g.col_tiles) want = g.col_tiles;
+  if (want > max_slices) want = max_slices;
   g.tiles_per_slice = wm_cdiv(g.col_tiles, want);
   g.slices = wm_cdiv(g.col_tiles, g.tiles_per_slice);
   return g;
@@ -718,4 +821,44 @@ extern "C" int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n
   a.n_clusters = n_clusters;
   a.out = out;
   return cl_launch<CL_SUMS, 4>(a, g, metric, st);
+}
+
+extern "C" size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g) {
+  if (m <= 0 || m > CL_MAX_N || e <= 0 || e > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
+  const ClGrid gr = cl_grid(m, e, 64, true, CL_GROUPMIN_SLICES);
+  return (gr.slices > 1 ? (size_t)gr.slices * m * g * 8 : 0) + 256;
+}
+
+extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
+                                 float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(xq && xe && group && out_dist && out_j && workspace, WM_EINVAL);
+  WM_REQUIRE(m > 0 && e > 0 && d > 0 && g > 0, WM_EINVAL);
+  WM_REQUIRE(m <= CL_MAX_N && e <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(xe) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+             WM_EALIGN);
+  const ClGrid gr = cl_grid(m, e, 64, true, CL_GROUPMIN_SLICES);
+  const size_t entries = gr.slices > 1 ? (size_t)gr.slices * m * g : 0;
+  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = xe;
+  a.n = e;
+  a.xr = xq;
+  a.nr = m;
+  a.d = d;
+  a.tiles_per_slice = gr.tiles_per_slice;
+  a.col_tiles = gr.col_tiles;
+  a.labels = group;
+  a.n_clusters = g;
+  a.group_d = gr.slices > 1 ? static_cast<float*>(workspace) : out_dist;
+  a.group_j = gr.slices > 1 ? reinterpret_cast<int*>(a.group_d + entries) : out_j;
+  const int rc = cl_launch<CL_GROUPMIN, 4>(a, gr, metric, st);
+  if (rc != WM_OK || gr.slices == 1) return rc;
+  const size_t blocks = ((size_t)m * g + CL_THREADS - 1) / CL_THREADS;
+  cl_group_min_merge<<<(unsigned)(blocks < 65536 ? blocks : 65536), CL_THREADS, 0, st>>>(a.group_d, a.group_j, group, gr.slices,
+                                                                                       gr.tiles_per_slice, m, e, g, out_dist,
+                                                                                       out_j);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
 }
