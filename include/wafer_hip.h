@@ -843,6 +843,37 @@ size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g);
 int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
                       float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream);
 
+/* DBCV (density-based cluster validity, Moulavi et al. 2014; DESIGN.md states the definition): its three all-pairs parts
+ * under the same distance function.  All take rows SORTED BY GROUP: group int32, non-decreasing, values in [0, g); with
+ * another sequence the outputs are unspecified (no access leaves the buffers).  The square ones walk, per row tile, only
+ * the column tiles of that tile's own groups: the cost is the sum of n_c^2 over the groups, not n^2.  The workspace-size
+ * functions return 0 for sizes that are not supported.  No atomics: two calls give the same bits.
+ *
+ * wm_allpoints_core: out[i] = ((1 / (n_c - 1)) * sum over the rows j of i's group with dist(i, j) > 0 of
+ * dist(i, j)^-p)^(-1 / p), n_c the size of the group; 0 for a row without a positive distance.  The sum is an online
+ * log-sum-exp of -p * log(dist) in double, taken in column order, so any p > 0 that a double holds is fine where
+ * dist^-p itself would overflow.  out double [n]. */
+size_t wm_allpoints_core_workspace_bytes(int n, int d, int g);
+int wm_allpoints_core(const float* x, const int32_t* group, int n, int d, int metric, int g, double p, double* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* wm_mreach_min_edge (at inv_alpha = 1) with the further condition group[j] == group[i]: one Boruvka round of every
+ * group's own mutual-reachability tree per call.  A row whose component holds its whole group gets -1 / +inf.  For the
+ * rows of one group the weights and (relative to the group's first row) the indices are wm_mreach_min_edge's bits on that
+ * group's rows alone. */
+size_t wm_mreach_min_edge_grouped_workspace_bytes(int n, int d, int g);
+int wm_mreach_min_edge_grouped(const float* x, const float* core, const int32_t* comp, const int32_t* group, int n, int d,
+                               int metric, int g, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* wm_group_min_dist with the mutual reachability in place of the distance: out_w[i][c] = the smallest
+ * max(core_q[i], core[j], dist(xq_i, xe_j)) over the rows j of xe with group[j] == c (wm_mreach_query's out_w bits on
+ * those columns alone; wm_group_min_dist's bits when all core distances are 0) and out_j[i][c] the lowest j that attains
+ * it; +inf / -1 for a group without a column.  core_q float32 [m], core float32 [e]; everything else, the workspace
+ * included, as for wm_group_min_dist (here only the columns are grouped, and all of them are walked). */
+size_t wm_group_min_mreach_workspace_bytes(int m, int e, int d, int g);
+int wm_group_min_mreach(const float* xq, const float* core_q, int m, const float* xe, const float* core, const int32_t* group,
+                        int e, int d, int metric, int g, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas
  * are stated in full in csrc/umap.hip.

@@ -6,7 +6,7 @@ notebooks/3.1-Embeddings-clustering.ipynb and 3.2-Embeddings-SSL-categories.ipyn
     python scripts/embedding_clustering_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
                                                [--trials 30] [--design random|grid] [--seed 0] [--rows N]
                                                [--metrics euclidean manhattan] [--no-scale] [--out DIR]
-                                               [--holdout N] [--soft]
+                                               [--holdout N] [--soft] [--validity]
 
 What the notebooks do, and where it is here:
   StandardScaler().fit_transform(embeddings)              -> retrieval.StandardScaler (skipped with --no-scale)
@@ -43,6 +43,12 @@ strongly every row, noise rows included, belongs to every cluster): membership.n
 holdout_membership.npy [N, n_clusters]; and in summary.json `soft_noise_above_half` (the share of the noise rows whose
 largest membership exceeds 0.5; null without noise rows) and `soft_mean_row_sum` (the mean probability of belonging
 to any cluster).
+
+--validity scores every trial without ground truth, by density and not by convexity (the `hdbscan` package's two scores):
+the columns `relative_validity` (HDBSCAN.relative_validity_: from the trial's spanning tree, free) and `dbcv`
+(cluster.validity_index: DBCV on the GPU; NaN for a trial with fewer than two clusters) follow the columns above in
+trials.csv and pareto.csv, `dbcv` joins the Pareto objectives (up), and summary.json names `chosen_by_dbcv`, the trial with
+the best DBCV (null when no trial has one).  Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -64,6 +70,8 @@ COLUMNS = ["trial", "metric", "min_samples", "min_cluster_size", "cluster_select
            "homogeneity", "silhouette", "calinski_harabasz", "davies_bouldin"]
 # (column, +1 when larger is better)
 OBJECTIVES = [("silhouette", 1), ("calinski_harabasz", 1), ("homogeneity", 1), ("davies_bouldin", -1), ("n_noise", -1)]
+VALIDITY_COLUMNS = ["relative_validity", "dbcv"]  # --validity: after COLUMNS
+VALIDITY_OBJECTIVES = [("dbcv", 1)]  # --validity: after OBJECTIVES
 
 
 def load_embeddings(path):
@@ -112,9 +120,10 @@ def design_trials(trials: int, design: str, seed: int, metrics, max_samples: int
     return out
 
 
-def pareto_rows(rows):
-    """Indices of the rows no other row dominates on OBJECTIVES (rows without finite scores never qualify)."""
-    vals = np.array([[s * float(r[c]) for c, s in OBJECTIVES] for r in rows], dtype=np.float64)
+def pareto_rows(rows, objectives=None):
+    """Indices of the rows no other row dominates on `objectives` (OBJECTIVES when None; rows without finite scores
+    never qualify)."""
+    vals = np.array([[s * float(r[c]) for c, s in objectives or OBJECTIVES] for r in rows], dtype=np.float64)
     ok = np.isfinite(vals).all(axis=1)
     keep = []
     for i in np.flatnonzero(ok):
@@ -155,6 +164,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--holdout", type=int, default=0, help="keep the last N rows out of the sweep and predict them")
     ap.add_argument("--soft", action="store_true", help="write the chosen trial's membership vectors and exemplars")
+    ap.add_argument("--validity", action="store_true", help="add the relative_validity and dbcv columns and the dbcv objective")
     a = ap.parse_args(argv)
 
     import torch
@@ -194,21 +204,28 @@ def main(argv=None) -> dict:
         labels = model.labels_.copy()
         all_labels.append(labels)
         rows.append({"trial": t, **p, **score_trial(x, truth, labels, p["metric"])})
+        if a.validity:
+            rows[-1]["relative_validity"] = model.relative_validity_
+            rows[-1]["dbcv"] = cluster.validity_index(x, labels, p["metric"]) if rows[-1]["n_clusters"] >= 2 else float("nan")
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
 
+    columns = COLUMNS + VALIDITY_COLUMNS if a.validity else COLUMNS
     with open(out / "trials.csv", "w", newline="") as fh:
-        wr = csv.DictWriter(fh, fieldnames=COLUMNS)
+        wr = csv.DictWriter(fh, fieldnames=columns)
         wr.writeheader()
         wr.writerows(rows)
-    front = pareto_rows(rows)
+    front = pareto_rows(rows, OBJECTIVES + VALIDITY_OBJECTIVES if a.validity else None)
     with open(out / "pareto.csv", "w", newline="") as fh:
-        wr = csv.DictWriter(fh, fieldnames=COLUMNS)
+        wr = csv.DictWriter(fh, fieldnames=columns)
         wr.writeheader()
         wr.writerows(rows[i] for i in front)
     chosen = max(front, key=lambda i: rows[i]["silhouette"]) if front else None
     summary = {"n": int(x.shape[0]), "d": int(x.shape[1]), "trials": len(rows), "n_trees": len(trees),
                "sweep_seconds": wall, "pareto": front, "chosen": chosen}
+    if a.validity:
+        scored = [i for i, r in enumerate(rows) if np.isfinite(r["dbcv"])]
+        summary["chosen_by_dbcv"] = max(scored, key=lambda i: rows[i]["dbcv"]) if scored else None
     if a.holdout:
         summary.update(holdout=int(a.holdout), holdout_noise=None, holdout_homogeneity=None)  # (filled for a chosen trial)
     if chosen is not None:

@@ -299,6 +299,15 @@ SIGNATURES = {
     "wm_group_min_dist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_group_min_dist": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
+    "wm_allpoints_core_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_allpoints_core": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "wm_mreach_min_edge_grouped_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_mreach_min_edge_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_group_min_mreach_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_group_min_mreach": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,

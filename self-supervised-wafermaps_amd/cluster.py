@@ -27,6 +27,14 @@ row through the condensed tree to a label, a membership strength and a GLOSH out
 Soft clustering (`exemplar_indices_`, `all_points_membership_vectors`, `membership_vector`): one rectangular pass
 (wm_group_min_dist) gives every row its distance to the nearest exemplar of every cluster; the merge heights in the
 condensed tree and the membership vectors themselves are host code (`exemplars_from_tree`, `membership_from_tree`).
+
+Cluster validity without ground truth (`validity_index`, `relative_validity`, `HDBSCAN.relative_validity_`): DBCV of
+Moulavi et al. 2014 under the names of the `hdbscan` package's validity module.  With the rows sorted by label its three
+all-pairs parts are block-diagonal passes of the same kernels (wm_allpoints_core, wm_mreach_min_edge_grouped: one
+Boruvka round of every cluster's own tree per launch, wm_group_min_mreach); which rows and edges of a cluster's tree are
+internal and the score itself are host code (`validity_from_parts`).  `relative_validity` is the package's cheap
+approximation from the fitted spanning tree and uses no GPU.  DESIGN.md states the definition and what differs from the
+package.
 """
 from __future__ import annotations
 
@@ -139,8 +147,11 @@ def mutual_reachability_mst(x, min_samples: int, metric: str = "euclidean", alph
     return out if return_rounds else out[:3]
 
 
-def _boruvka(x, core, metric: str, alpha: float):
-    """mutual_reachability_mst's rounds on a prepared matrix and its core distances: (u, v, w, rounds)."""
+def _boruvka(x, core, metric: str, alpha: float, group=None, n_groups: int = 1):
+    """mutual_reachability_mst's rounds on a prepared matrix and its core distances: (u, v, w, rounds).  With `group`
+    (int32 device tensor [n], non-decreasing, every id in [0, n_groups) present; alpha 1) the rounds run on every
+    group's own graph at once (wm_mreach_min_edge_grouped) and end at one component per group: a spanning forest of
+    n - n_groups edges, found in at most ceil(log2 of the largest group) rounds."""
     import torch
 
     n = x.shape[0]
@@ -148,8 +159,12 @@ def _boruvka(x, core, metric: str, alpha: float):
     eu, ev, ew = [], [], []
     n_comp, rounds = n, 0
     comp = parent.copy()
-    while n_comp > 1:
-        w_d, j_d = min_outgoing_edges(x, core, torch.from_numpy(comp.astype(np.int32)).to(x.device), metric, alpha)
+    while n_comp > (1 if group is None else n_groups):
+        comp_d = torch.from_numpy(comp.astype(np.int32)).to(x.device)
+        if group is None:
+            w_d, j_d = min_outgoing_edges(x, core, comp_d, metric, alpha)
+        else:
+            w_d, j_d = grouped_min_outgoing_edges(x, core, comp_d, group, n_groups, metric)
         w, j = w_d.cpu().numpy(), j_d.cpu().numpy().astype(np.int64)
         rounds += 1
         i = np.flatnonzero(j >= 0)
@@ -651,7 +666,8 @@ class HDBSCAN:
     `gen_min_span_tree` is set, since `refit` needs it).  `min_samples=None` means `min_cluster_size`.
     `refit(min_cluster_size=..., cluster_selection_epsilon=...)` relabels from the stored tree: the tree depends on
     (metric, min_samples, alpha) only.  `fit` and `refit` also set `selected_clusters_` (the sorted condensed-tree ids
-    of the clusters: position = label) and `outlier_scores_` (`glosh`).  With `prediction_data=True`, `fit` keeps the
+    of the clusters: position = label) and `outlier_scores_` (`glosh`); `relative_validity_` scores the labelling from the
+    tree alone.  With `prediction_data=True`, `fit` keeps the
     prepared device matrix and the device core distances, which `approximate_predict` needs."""
 
     def __init__(self, min_cluster_size: int = 5, min_samples: Optional[int] = None, cluster_selection_epsilon: float = 0.0,
@@ -672,7 +688,7 @@ class HDBSCAN:
         self.gen_min_span_tree, self.prediction_data = bool(gen_min_span_tree), bool(prediction_data)
         self.labels_ = self.probabilities_ = self.condensed_tree_ = self.minimum_spanning_tree_ = None
         self.selected_clusters_ = self.outlier_scores_ = None
-        self._n = self._k = self._train = self._core = self._exemplars = None
+        self._n = self._k = self._train = self._core = self._exemplars = self._relative_validity = None
 
     def fit(self, x) -> "HDBSCAN":
         k = self.min_cluster_size if self.min_samples is None else int(self.min_samples)
@@ -701,8 +717,18 @@ class HDBSCAN:
             t[:, 0].astype(np.int64), t[:, 1].astype(np.int64), t[:, 2], self._n, self.min_cluster_size,
             self.cluster_selection_epsilon, self.cluster_selection_method, self.allow_single_cluster, return_selected=True)
         self.outlier_scores_ = glosh(self.condensed_tree_, self._n)
-        self._exemplars = None
+        self._exemplars = self._relative_validity = None
         return self
+
+    @property
+    def relative_validity_(self):
+        """`relative_validity` of the fitted tree under the current labels (a float; no GPU work); None before `fit`.
+        Computed on first access after a `fit` / `refit`."""
+        if self.labels_ is None:
+            return None
+        if self._relative_validity is None:
+            self._relative_validity = relative_validity(self.minimum_spanning_tree_, self.labels_)
+        return self._relative_validity
 
     @property
     def exemplar_indices_(self):
@@ -893,6 +919,269 @@ def membership_vector(model: "HDBSCAN", rows) -> np.ndarray:
     _, cl_parent, birth, _, _, pt_parent, pt_lam = _tree_tables(model.condensed_tree_, n)
     at, lam = _walk(n, cl_parent, birth, pt_parent, pt_lam, j, w)
     return membership_from_tree(model.condensed_tree_, n, model.selected_clusters_, at, lam, _exemplar_distances(model, xq))
+
+
+# ------------------------------------------------------------------------------------------------ GPU: DBCV
+
+
+def _sorted_groups(group, n: int, g: int, device):
+    """(order or None, group int32 on the device in non-decreasing order): `order` sorts the rows by (group, index) and is
+    None when they already are."""
+    import torch
+
+    group = torch.as_tensor(group)
+    if group.shape != (n,) or group.dtype not in (torch.int32, torch.int64):
+        raise ValueError("group: one int32 / int64 id per row expected")
+    if g < 1 or (n and (int(group.min()) < 0 or int(group.max()) >= g)):
+        raise ValueError(f"group ids must lie in [0, n_groups = {g})")
+    group = group.to(device)
+    if n < 2 or bool((group[1:] >= group[:-1]).all()):
+        return None, group.to(torch.int32).contiguous()
+    order = torch.argsort(group, stable=True)
+    return order, group[order].to(torch.int32).contiguous()
+
+
+def allpoints_core_distances(x, labels, d: Optional[float] = None, metric: str = "euclidean"):
+    """DBCV's all-points core distance of every row of x [n, D] (device tensor) inside its own cluster:
+    ((1 / (n_c - 1)) * sum_j dist_ij^-p)^(-1 / p) over the rows j of the cluster at a positive distance, with p = `d`,
+    or D as passed (before the padding to a multiple of 4) when `d` is None.  float64 [n] on the device
+    (wm_allpoints_core: the sum is a log-sum-exp, so no p overflows); NaN on the noise rows (label -1), 0 for a row
+    whose cluster holds nothing but copies of it.  `labels`: any integer array or tensor [n]."""
+    import torch
+
+    code = metric_code(metric)
+    p = float(x.shape[1] if d is None else d)
+    if not 0 < p < math.inf:
+        raise ValueError(f"d must be positive and finite (got {d})")
+    lab = np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels)
+    if lab.shape != (x.shape[0],) or lab.dtype.kind not in "iu":
+        raise ValueError("one integer label per row expected")
+    x = _prep(x)
+    n, dim = x.shape
+    out = torch.full((n,), float("nan"), dtype=torch.float64, device=x.device)
+    keep = np.flatnonzero(lab >= 0)
+    if keep.size == 0:
+        return out
+    _, enc = np.unique(lab[keep], return_inverse=True)
+    order = np.argsort(enc, kind="stable")  # by (cluster, index)
+    rows = torch.from_numpy(keep[order]).to(x.device)
+    xs = x[rows].contiguous()
+    gs = torch.from_numpy(enc[order].astype(np.int32)).to(x.device)
+    m, g = int(keep.size), int(enc.max()) + 1
+    lib = _lib.load()
+    need = lib.wm_allpoints_core_workspace_bytes(m, dim, g)
+    if need == 0:
+        raise ValueError(f"allpoints_core_distances: unsupported sizes n={m} d={dim} clusters={g}")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    res = torch.empty(m, dtype=torch.float64, device=x.device)
+    check(lib.wm_allpoints_core(ptr(xs), ptr(gs), m, dim, code, g, p, ptr(res), ptr(ws), need, stream_ptr()), "wm_allpoints_core")
+    out[rows] = res
+    return out
+
+
+def grouped_min_outgoing_edges(x, core, comp, group, n_groups: int, metric: str = "euclidean"):
+    """`min_outgoing_edges` (alpha 1) inside every group at once: per row the lightest mutual-reachability edge to a row
+    of its own group in another component, as (weight float32 [n], j int32 [n]); -1 / inf where the row's component
+    holds its whole group (wm_mreach_min_edge_grouped).  `group`: n integers in [0, n_groups) in any order; rows that
+    are not in runs are sorted by (group, index) for the kernel and the indices mapped back."""
+    import torch
+
+    code = metric_code(metric)
+    x = _prep(x)
+    require_gpu(core, comp)
+    n, d = x.shape
+    if core.shape != (n,) or comp.shape != (n,) or core.dtype != torch.float32 or comp.dtype != torch.int32:
+        raise ValueError("core float32 [n] and comp int32 [n] expected")
+    g = int(n_groups)
+    order, gs = _sorted_groups(group, n, g, x.device)
+    if order is not None:
+        x, core, comp = x[order].contiguous(), core[order].contiguous(), comp[order].contiguous()
+    lib = _lib.load()
+    need = lib.wm_mreach_min_edge_grouped_workspace_bytes(n, d, g)
+    if need == 0:
+        raise ValueError(f"grouped_min_outgoing_edges: unsupported sizes n={n} d={d} n_groups={g}")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    w = torch.empty(n, dtype=torch.float32, device=x.device)
+    j = torch.empty(n, dtype=torch.int32, device=x.device)
+    check(lib.wm_mreach_min_edge_grouped(ptr(x), ptr(core), ptr(comp), ptr(gs), n, d, code, g, ptr(w), ptr(j), ptr(ws), need,
+                                         stream_ptr()), "wm_mreach_min_edge_grouped")
+    if order is None:
+        return w, j
+    back = torch.where(j >= 0, order.to(torch.int32)[j.clamp(min=0).long()], j)
+    w_out, j_out = torch.empty_like(w), torch.empty_like(j)
+    w_out[order], j_out[order] = w, back
+    return w_out, j_out
+
+
+def group_min_mreach(xq, core_q, xe, core, group, n_groups: int, metric: str = "euclidean"):
+    """`group_min_distances` with the mutual reachability max(core_q[i], core[j], dist_ij) in place of the distance:
+    (weight float32 [m, n_groups], j int32 [m, n_groups]) on the device (wm_group_min_mreach), j the lowest index into xe
+    that attains the weight, inf / -1 for a group without a row.  core_q float32 [m], core float32 [e]."""
+    import torch
+
+    code = metric_code(metric)
+    xq, xe = _prep(xq), _prep(xe)
+    require_gpu(core_q, core)
+    (m, d), e, g = xq.shape, xe.shape[0], int(n_groups)
+    if xe.shape[1] != d:
+        raise ValueError(f"the rows have {d} features (padded), the grouped rows {xe.shape[1]}")
+    if core_q.shape != (m,) or core.shape != (e,) or core_q.dtype != torch.float32 or core.dtype != torch.float32:
+        raise ValueError("core_q float32 [m] and core float32 [e] expected")
+    if m < 1 or e < 1:
+        raise ValueError("group_min_mreach needs at least one row on either side")
+    order, gs = _sorted_groups(group, e, g, xq.device)
+    if order is not None:
+        xe, core = xe[order].contiguous(), core[order].contiguous()
+    w = torch.empty((m, g), dtype=torch.float32, device=xq.device)
+    j = torch.empty((m, g), dtype=torch.int32, device=xq.device)
+    lib = _lib.load()
+    need = lib.wm_group_min_mreach_workspace_bytes(m, e, d, g)
+    if need == 0:
+        raise ValueError(f"group_min_mreach: unsupported sizes m={m} e={e} d={d} n_groups={g}")
+    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    check(lib.wm_group_min_mreach(ptr(xq), ptr(core_q), m, ptr(xe), ptr(core), ptr(gs), e, d, code, g, ptr(w), ptr(j), ptr(ws),
+                                  need, stream_ptr()), "wm_group_min_mreach")
+    if order is None:
+        return w, j
+    return w, torch.where(j >= 0, order.to(torch.int32)[j.clamp(min=0).long()], j)
+
+
+def validity_from_parts(sizes, n_total: int, sparseness, sep) -> Tuple[float, np.ndarray]:
+    """DBCV from its parts, in float64: `sizes` [C] the clusters' row counts, `n_total` the number of rows the labelling
+    covers (noise included), `sparseness` [C] the largest internal edge of every cluster's tree, `sep` [C, C] the
+    clusters' pairwise separations (the diagonal is ignored).  Returns (score, V [C]) with sep_c = the smallest entry
+    of row c off the diagonal, V_c = (sep_c - sparseness_c) / max(sep_c, sparseness_c) (0 when both are 0) and
+    score = sum_c sizes_c / n_total * V_c."""
+    sizes = np.asarray(sizes, dtype=np.float64)
+    sparse = np.asarray(sparseness, dtype=np.float64)
+    sep = np.array(sep, dtype=np.float64)
+    c = sizes.shape[0]
+    if sizes.ndim != 1 or sparse.shape != (c,) or sep.shape != (c, c) or c < 2:
+        raise ValueError("sizes [C], sparseness [C] and sep [C, C] with C >= 2 expected")
+    if not n_total >= sizes.sum() or (sizes < 0).any():
+        raise ValueError("n_total must cover the clusters, and no size may be negative")
+    sep[np.arange(c), np.arange(c)] = np.inf
+    nearest = sep.min(axis=1)
+    if not (np.isfinite(sparse).all() and np.isfinite(nearest).all() and (sparse >= 0).all() and (nearest >= 0).all()):
+        raise ValueError("sparseness and the separations must be finite and not negative")
+    top = np.maximum(nearest, sparse)
+    v = np.divide(nearest - sparse, top, out=np.zeros(c), where=top > 0.0)
+    return float(np.cumsum(sizes / float(n_total) * v)[-1]), v  # (added in cluster order, one at a time)
+
+
+def _internal_parts(u, v, w, group: np.ndarray, starts: np.ndarray):
+    """From the spanning forest (one tree per group; rows sorted by group, `starts` [g + 1] the groups' first rows):
+    (internal bool [n], sparseness float64 [g]).  Internal rows have degree > 1 in their tree, or are the group's first
+    row where no row has (two rows or fewer); internal edges join two internal rows, or are all the group's edges where
+    none does; the sparseness is the largest internal edge weight (0 for a group without an edge)."""
+    n, g = group.shape[0], starts.shape[0] - 1
+    degree = np.bincount(u, minlength=n) + np.bincount(v, minlength=n)
+    internal = degree > 1
+    none = np.bincount(group[internal], minlength=g) == 0
+    internal[starts[:-1][none]] = True
+    eg = group[u]
+    inner = (degree[u] > 1) & (degree[v] > 1)
+    use = inner | (np.bincount(eg[inner], minlength=g) == 0)[eg]
+    sparse = np.zeros(g)
+    np.maximum.at(sparse, eg[use], w[use])
+    return internal, sparse
+
+
+def _validity_parts(x, lab: np.ndarray, metric: str, d):
+    """validity_index's device work: (sizes [C'], sparseness [C'], sep [C', C'], kept label values [C'], detail) over the
+    C' clusters of at least two rows.  `detail` holds what a check needs to restate the score on the same trees: rows
+    (the kept rows in (label, index) order), group, core (float64), u, v, w (the forest, indices into `rows`), internal
+    and rounds."""
+    import torch
+
+    values, counts = np.unique(lab[lab >= 0], return_counts=True)
+    values = values[counts >= 2]
+    keep = np.flatnonzero(np.isin(lab, values))
+    enc = np.searchsorted(values, lab[keep])
+    order = np.argsort(enc, kind="stable")
+    rows, group = keep[order], enc[order]
+    g = int(values.size)
+    sizes = np.bincount(group, minlength=g)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    xp = _prep(x)
+    xs = xp[torch.from_numpy(rows).to(xp.device)].contiguous()
+    core64 = allpoints_core_distances(xs, group, float(x.shape[1] if d is None else d), metric)
+    core = core64.float().contiguous()  # rounded once: both mutual-reachability passes use these bits
+    u, v, w, rounds = _boruvka(xs, core, metric, 1.0, torch.from_numpy(group.astype(np.int32)).to(xp.device), g)
+    internal, sparse = _internal_parts(u, v, w, group, starts)
+    at = np.flatnonzero(internal)
+    at_d = torch.from_numpy(at).to(xp.device)
+    xi, ci = xs[at_d].contiguous(), core[at_d].contiguous()
+    wmin = group_min_mreach(xi, ci, xi, ci, torch.from_numpy(group[at]), g, metric)[0].cpu().numpy().astype(np.float64)
+    sep = np.minimum.reduceat(wmin, np.searchsorted(group[at], np.arange(g)), axis=0)  # (every group has an internal row)
+    detail = {"rows": rows, "group": group, "core": core64.cpu().numpy(), "u": u, "v": v, "w": w, "internal": internal,
+              "rounds": rounds}
+    return sizes, sparse, sep, values, detail
+
+
+def validity_index(x, labels, metric: str = "euclidean", d: Optional[float] = None, per_cluster_scores: bool = False,
+                   mst_raw_dist: bool = False, return_parts: bool = False):
+    """DBCV, the density-based cluster validity of a labelling (`hdbscan.validity.validity_index`): a float in [-1, 1],
+    larger is better; with `per_cluster_scores` also float64 [labels.max() + 1], every cluster's V_c.  x [n, D] device
+    tensor, `labels` [n] integers with -1 for noise, `d` the power of the all-points core distance (default D).
+    DESIGN.md ("DBCV") states the definition.  Noise rows take no part but count in n, so they lower the score.
+    Deliberate differences from the package: a cluster of a single row scores 0 and takes no part in the other clusters'
+    separations; fewer than two clusters of at least two rows raise ValueError (as `silhouette_samples` does);
+    `mst_raw_dist` is not built; the power sums are taken in the log domain, so p = 50 .. 1024 neither overflows nor
+    underflows (the package's float64 powers do).  With `return_parts` a dict of the intermediate arrays follows."""
+    if mst_raw_dist:
+        raise NotImplementedError("mst_raw_dist is not implemented: the trees are always built on the mutual reachability")
+    metric_code(metric)
+    lab = np.asarray(labels.cpu() if hasattr(labels, "cpu") else labels)
+    if x.ndim != 2 or lab.shape != (x.shape[0],) or lab.dtype.kind not in "iu":
+        raise ValueError("x [n, D] and one integer label per row expected")
+    if d is not None and not 0 < float(d) < math.inf:
+        raise ValueError(f"d must be positive and finite (got {d})")
+    usable = int((np.unique(lab[lab >= 0], return_counts=True)[1] >= 2).sum())
+    if usable < 2:
+        raise ValueError(f"validity_index needs at least two clusters of at least two rows (got {usable})")
+    sizes, sparse, sep, kept, detail = _validity_parts(x, lab, metric, d)
+    score, v = validity_from_parts(sizes, lab.shape[0], sparse, sep)
+    out = (score,)
+    if per_cluster_scores:
+        per = np.zeros(int(lab.max()) + 1)
+        per[kept] = v
+        out += (per,)
+    if return_parts:
+        out += ({"sizes": sizes, "n_total": int(lab.shape[0]), "sparseness": sparse, "sep": sep, "clusters": kept, **detail},)
+    return out[0] if len(out) == 1 else out
+
+
+def relative_validity(mst, labels) -> float:
+    """The `hdbscan` package's `relative_validity_`: a cheap stand-in for DBCV from the fitted spanning tree `mst`
+    [n - 1, 3] (u, v, weight: `HDBSCAN.minimum_spanning_tree_`) and `labels` [n].  Host only, float64.  Over the edges:
+    the largest weight inside cluster c is its sparseness DSC_c, the smallest weight between c and another cluster its
+    separation DSPC_c; an edge with one noise end only lowers `min_outlier`, one with two is skipped.  A cluster that
+    no edge joins to another one gets DSPC_c = 2 * (the largest weight of the tree, or with a single cluster
+    `min_outlier`, itself the largest weight when no edge has a noise end).  V_c = (DSPC_c - DSC_c) / max(DSPC_c, DSC_c)
+    (0 when both are 0) and the score is sum_c n_c V_c / n, n counting the noise rows.  No cluster: 0.0."""
+    mst = np.asarray(mst, dtype=np.float64)
+    lab = np.asarray(labels).astype(np.int64)
+    n = lab.shape[0]
+    if lab.ndim != 1 or mst.shape != (max(n - 1, 0), 3):
+        raise ValueError("mst [n - 1, 3] and labels [n] expected")
+    n_clusters = int(lab.max()) + 1 if n else 0
+    if n_clusters <= 0:
+        return 0.0
+    a, b, w = lab[mst[:, 0].astype(np.int64)], lab[mst[:, 1].astype(np.int64)], mst[:, 2]
+    max_w = float(w.max()) if w.size else 0.0
+    one_noise = (a < 0) != (b < 0)
+    min_outlier = float(w[one_noise].min()) if one_noise.any() else max_w
+    dsc, dspc = np.zeros(n_clusters), np.full(n_clusters, np.inf)
+    both = (a >= 0) & (b >= 0)
+    same, cross = both & (a == b), both & (a != b)
+    np.maximum.at(dsc, a[same], w[same])
+    np.minimum.at(dspc, a[cross], w[cross])
+    np.minimum.at(dspc, b[cross], w[cross])
+    dspc[np.isinf(dspc)] = 2.0 * (max_w if n_clusters > 1 else min_outlier)
+    top = np.maximum(dspc, dsc)
+    v = np.divide(dspc - dsc, top, out=np.zeros(n_clusters), where=top > 0.0)
+    return float(np.cumsum(np.bincount(lab[lab >= 0], minlength=n_clusters) * v)[-1] / n)  # (added in cluster order)
 
 
 # ------------------------------------------------------------------------------------------------ scores

@@ -14,7 +14,12 @@
 //                         by the index (what HDBSCAN's prediction for new rows starts from);
 //   wm_group_min_dist     for the rows of a second matrix, per group of columns (runs of equal group ids: the exemplars
 //                         of one cluster) the nearest column and its distance (what HDBSCAN's soft clustering starts
-//                         from).
+//                         from);
+//   wm_allpoints_core, wm_mreach_min_edge_grouped, wm_group_min_mreach
+//                         the three all-pairs parts of DBCV (density-based cluster validity) on rows sorted by cluster:
+//                         the all-points core distance (a power mean of a row's distances inside its own cluster), one
+//                         Boruvka round of every cluster's own mutual-reachability tree at once, and the group min with
+//                         the mutual reachability in place of the plain distance (the clusters' separations).
 //
 // ONE distance function serves all of them (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
@@ -60,6 +65,19 @@
 //             keep-best-in-registers shape: a thread's four columns (tx + 16 c) interleave the groups, so it would need
 //             a best per (row, group in the tile) and a reduction per group; the owner scan costs one wave 64 LDS reads
 //             and compares per tile, about a quarter of the pair work at d = 52 and a fortieth at d = 512.
+//   all-points core  (DBCV) the sums shape on rows sorted by group: every thread turns its pairs into
+//             t = -p * log(dist) in double (-inf for a pair of two groups, a zero distance or a padded column) and stores
+//             t into a double tile in LDS, so that the 4096 logarithms of a tile are spread over all 256 threads; the
+//             row's owner folds its 64 values in column order into an online log-sum-exp (running maximum M and
+//             S = sum exp(t - M), one exp per value).  dist^-p itself leaves float64 for p = 50 .. 1024; M + log S does
+//             not.  cl_apcore_merge folds the slices' (M, S) in slice order and finishes the power mean.
+//   grouped min edge, group min of the mutual reachability: the min-edge mode with `group[j] == group[i]` as a further
+//             condition, and the group-min mode with max(core_q[i], core[j], dist) stored into the distance tile.
+// Block-diagonal walk (all-points core, grouped min edge): with the rows sorted by group a row tile needs only the
+// columns from the first column of its first row's group to the last column of its last row's group.  cl_group_bounds
+// writes every present group's [first, last + 1) into the workspace (one thread per row, the run boundaries store);
+// cl_pairs reads the two ends for its row tile and cuts THAT tile range into the grid's slices, so the cost is the sum
+// of n_c^2 over the groups (rounded up to tiles) and not n^2.  Pairs of two groups inside a shared tile are masked.
 // Core, knn, min edge, query and group min split the columns into slices (grid.y) whose partial results a second small kernel combines in a
 // fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
 // atomics anywhere: two calls give the same bits.
@@ -77,8 +95,13 @@ constexpr int CL_LDD = CL_COLS + 1;  // LDS row pitch of a distance tile (floats
 constexpr int CL_MAXK = 64;
 constexpr int CL_GROUPMIN_SLICES = 16;  // group min: at most this many column slices (the workspace: as many result planes)
 constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3, CL_MREACHQ = 4, CL_GROUPMIN = 5;
+constexpr int CL_APCORE = 6, CL_MINEDGE_G = 7, CL_GROUPMIN_MR = 8;  // DBCV: the grouped forms
+constexpr bool cl_is_minedge(int mode) { return mode == CL_MINEDGE || mode == CL_MINEDGE_G; }
+constexpr bool cl_is_groupmin(int mode) { return mode == CL_GROUPMIN || mode == CL_GROUPMIN_MR; }
 // the modes whose per-row best stays in registers (no distance tile in LDS)
-constexpr bool cl_keeps_best(int mode) { return mode == CL_MINEDGE || mode == CL_MREACHQ; }
+constexpr bool cl_keeps_best(int mode) { return cl_is_minedge(mode) || mode == CL_MREACHQ; }
+// the modes on rows sorted by group that walk only the column tiles of the row tile's own groups
+constexpr bool cl_block_diagonal(int mode) { return mode == CL_APCORE || mode == CL_MINEDGE_G; }
 
 template <int METRIC>
 __device__ __forceinline__ float cl_accum(float a, float b, float acc) {
@@ -116,6 +139,13 @@ struct ClArgs {
   // group min: [slices][nr][n_clusters] (the outputs themselves when there is one slice)
   float* group_d;
   int* group_j;
+  // block-diagonal modes (labels: the rows' group ids, non-decreasing; n_clusters: their number): per group the
+  // columns [bounds[2 c], bounds[2 c + 1]) (cl_group_bounds)
+  const int* bounds;
+  // all-points core: the power and the slices' running maximum / scaled sum [slices][nr]
+  double pw;
+  double* part_m;
+  double* part_s;
 };
 
 template <int MODE, int TM>
@@ -124,7 +154,8 @@ constexpr size_t cl_lds_bytes(int kl) {
   if (!cl_keeps_best(MODE)) f += (size_t)16 * TM * CL_LDD;
   if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
   if (MODE == CL_KNN) f += (size_t)2 * 16 * TM * kl;
-  if (MODE == CL_SUMS || MODE == CL_GROUPMIN) f += CL_COLS;
+  if (MODE == CL_APCORE) f += (size_t)16 * TM * CL_LDD;  // (the tile holds doubles)
+  if (MODE == CL_SUMS || cl_is_groupmin(MODE)) f += CL_COLS;
   return f * sizeof(float);
 }
 
@@ -142,8 +173,22 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   const int lq = (t & 7) * 4, lr = t >> 3;  // staging: float4 at feature lq of row lr (+ 32 per pass)
   const int n = p.n, nr = p.nr, d = p.d;
   const int i0 = blockIdx.x * ROWS;
-  const int tile0 = blockIdx.y * p.tiles_per_slice;
-  const int tile1 = min(tile0 + p.tiles_per_slice, p.col_tiles);
+  int tile0 = blockIdx.y * p.tiles_per_slice;
+  int tile1 = min(tile0 + p.tiles_per_slice, p.col_tiles);
+  if constexpr (cl_block_diagonal(MODE)) {
+    // the columns of the groups of this row tile's first and last row (uniform over the workgroup); an id outside
+    // [0, n_clusters) or bounds that do not fit (rows not sorted: out of contract) give no tile or clamped ones
+    const int ga = p.labels[i0], gb = p.labels[min(i0 + ROWS, nr) - 1];
+    int c0 = 0, c1 = 0;
+    if ((unsigned)ga < (unsigned)p.n_clusters && (unsigned)gb < (unsigned)p.n_clusters) {
+      c0 = max(p.bounds[2 * ga], 0);
+      c1 = min(p.bounds[2 * gb + 1], n);
+    }
+    const int t0 = c0 / CL_COLS, t1 = c1 > c0 ? (c1 + CL_COLS - 1) / CL_COLS : t0;
+    const int per = (t1 - t0 + (int)gridDim.y - 1) / (int)gridDim.y;
+    tile0 = t0 + (int)blockIdx.y * per;
+    tile1 = min(tile0 + per, t1);
+  }
   const int nchunks = (d + CL_KC - 1) / CL_KC;
 
   // ---- per-mode state
@@ -155,7 +200,16 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   double run = 0.0;
   [[maybe_unused]] float gbest = INFINITY;  // group min: the owner's best of the group `cur` so far and its column
   [[maybe_unused]] int gj = -1;
-  if constexpr (MODE == CL_MINEDGE) {
+  [[maybe_unused]] int gi[TM];  // block-diagonal modes: the rows' groups
+  [[maybe_unused]] double lm = -INFINITY, ls = 0.0;  // all-points core: the owner's running maximum and scaled sum
+  if constexpr (cl_block_diagonal(MODE)) {
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      const int i = i0 + ty + 16 * r;
+      gi[r] = i < nr ? p.labels[i] : -1;
+    }
+  }
+  if constexpr (cl_is_minedge(MODE)) {
 #pragma unroll
     for (int r = 0; r < TM; ++r) {
       const int i = i0 + ty + 16 * r;
@@ -165,12 +219,13 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       bj[r] = -1;
     }
   }
-  if constexpr (MODE == CL_MREACHQ) {
+  if constexpr (MODE == CL_MREACHQ || MODE == CL_GROUPMIN_MR) {
 #pragma unroll
     for (int r = 0; r < TM; ++r) {
       const int i = i0 + ty + 16 * r;
       ci[r] = i < nr ? p.core_q[i] : 0.f;
-      bw[r] = bd[r] = INFINITY;
+      bw[r] = INFINITY;
+      if constexpr (MODE == CL_MREACHQ) bd[r] = INFINITY;
       bj[r] = -1;
     }
   }
@@ -241,14 +296,16 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
     }
 
     // ---- the tile's epilogue
-    if constexpr (MODE == CL_MINEDGE) {
+    if constexpr (cl_is_minedge(MODE)) {
       float cj[4];
       int cpj[4];
+      [[maybe_unused]] int gc[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int j = j0 + tx + 16 * c;
         cj[c] = j < n ? p.core[j] : 0.f;
         cpj[c] = j < n ? p.comp[j] : 0;
+        if constexpr (MODE == CL_MINEDGE_G) gc[c] = j < n ? p.labels[j] : -2;
       }
 #pragma unroll
       for (int r = 0; r < TM; ++r) {
@@ -257,7 +314,9 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
         for (int c = 0; c < 4; ++c) {
           const int j = j0 + tx + 16 * c;
           const float w = fmaxf(fmaxf(ci[r], cj[c]), cl_finish<METRIC>(acc[r][c]) * p.inv_alpha);
-          if (iv && j < n && cpj[c] != cpi[r] && (w < bw[r] || (w == bw[r] && j < bj[r]))) {
+          bool ok = iv && j < n && cpj[c] != cpi[r];
+          if constexpr (MODE == CL_MINEDGE_G) ok = ok && gc[c] == gi[r];
+          if (ok && (w < bw[r] || (w == bw[r] && j < bj[r]))) {
             bw[r] = w;
             bj[r] = j;
           }
@@ -286,13 +345,55 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
           }
         }
       }
-    } else {
+    } else if constexpr (MODE == CL_APCORE) {
+      double* Dd = reinterpret_cast<double*>(Dt);  // (8-byte aligned: the staging buffers are a multiple of 16 bytes)
+      int gc[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int j = j0 + tx + 16 * c;
+        gc[c] = j < n ? p.labels[j] : -2;
+      }
 #pragma unroll
       for (int r = 0; r < TM; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-          Dt[(ty + 16 * r) * CL_LDD + tx + 16 * c] = j0 + tx + 16 * c < n ? cl_finish<METRIC>(acc[r][c]) : INFINITY;
-      if constexpr (MODE == CL_SUMS || MODE == CL_GROUPMIN) {
+        for (int c = 0; c < 4; ++c) {
+          const float dist = cl_finish<METRIC>(acc[r][c]);
+          // a zero distance (the row itself, an exact duplicate) and a pair of two groups contribute nothing
+          Dd[(ty + 16 * r) * CL_LDD + tx + 16 * c] = (gc[c] == gi[r] && dist > 0.f) ? -p.pw * log((double)dist) : -INFINITY;
+        }
+      __syncthreads();
+      // (the next write of the tile lies behind the next tile's chunk barriers, which the owners reach after this scan)
+      if (t < ROWS && i0 + t < nr) {
+        const double* row = Dd + t * CL_LDD;
+        for (int c = 0; c < CL_COLS; ++c) {
+          const double v = row[c];
+          if (v == -INFINITY) continue;
+          if (v > lm) {
+            ls = ls * exp(lm - v) + 1.0;  // (lm = -inf at the first value: exp gives 0)
+            lm = v;
+          } else {
+            ls += exp(v - lm);
+          }
+        }
+      }
+    } else {
+      [[maybe_unused]] float cj[4];
+      if constexpr (MODE == CL_GROUPMIN_MR) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int j = j0 + tx + 16 * c;
+          cj[c] = j < n ? p.core[j] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < TM; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          float v = cl_finish<METRIC>(acc[r][c]);
+          if constexpr (MODE == CL_GROUPMIN_MR) v = fmaxf(fmaxf(ci[r], cj[c]), v);  // wm_mreach_query's weight at inv_alpha 1
+          Dt[(ty + 16 * r) * CL_LDD + tx + 16 * c] = j0 + tx + 16 * c < n ? v : INFINITY;
+        }
+      if constexpr (MODE == CL_SUMS || cl_is_groupmin(MODE)) {
         if (t < CL_COLS) reinterpret_cast<int*>(extra)[t] = j0 + t < n ? p.labels[j0 + t] : -1;
       }
       __syncthreads();
@@ -319,7 +420,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
               kth = L[k - 1];
             }
           }
-        } else if constexpr (MODE == CL_GROUPMIN) {
+        } else if constexpr (cl_is_groupmin(MODE)) {
           const int* lab = reinterpret_cast<const int*>(extra);
           const size_t at = ((size_t)blockIdx.y * nr + i0 + t) * p.n_clusters;
           float* od = p.group_d + at;
@@ -369,7 +470,13 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   if constexpr (MODE == CL_SUMS) {
     if (t < ROWS && i0 + t < nr && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
   }
-  if constexpr (MODE == CL_GROUPMIN) {
+  if constexpr (MODE == CL_APCORE) {
+    if (t < ROWS && i0 + t < nr) {
+      p.part_m[(size_t)blockIdx.y * nr + i0 + t] = lm;
+      p.part_s[(size_t)blockIdx.y * nr + i0 + t] = ls;
+    }
+  }
+  if constexpr (cl_is_groupmin(MODE)) {
     if (t < ROWS && i0 + t < nr) {
       const size_t at = ((size_t)blockIdx.y * nr + i0 + t) * p.n_clusters;
       if (cur >= 0) {
@@ -396,7 +503,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       }
     }
   }
-  if constexpr (MODE == CL_MINEDGE) {
+  if constexpr (cl_is_minedge(MODE)) {
     __syncthreads();  // the staging buffers become the reduction scratch: [ROWS][17] weights, then indices
     float* rw = cl_smem;
     int* rj = reinterpret_cast<int*>(cl_smem + ROWS * 17);
@@ -586,6 +693,42 @@ __global__ __launch_bounds__(CL_THREADS) void cl_group_min_merge(const float* __
   }
 }
 
+// Per group present among the sorted ids its columns [first, last + 1): the two rows at a run's ends store them.  An id
+// outside [0, g) stores nothing.
+__global__ __launch_bounds__(CL_THREADS) void cl_group_bounds(const int* __restrict__ group, int n, int g,
+                                                              int* __restrict__ bounds) {
+  const int j = blockIdx.x * CL_THREADS + threadIdx.x;
+  if (j >= n) return;
+  const int v = group[j];
+  if ((unsigned)v >= (unsigned)g) return;
+  if (j == 0 || group[j - 1] != v) bounds[2 * v] = j;
+  if (j == n - 1 || group[j + 1] != v) bounds[2 * v + 1] = j + 1;
+}
+
+// The slices' (running maximum, scaled sum) of a row in slice order, then the power mean of the definition:
+// ((1 / (n_c - 1)) sum dist^-p)^(-1 / p) = exp(-(M + log S - log(n_c - 1)) / p); 0 for a row without a positive distance.
+__global__ __launch_bounds__(CL_THREADS) void cl_apcore_merge(const double* __restrict__ pm, const double* __restrict__ ps,
+                                                              int slices, int n, const int* __restrict__ group,
+                                                              const int* __restrict__ bounds, int g, double pw,
+                                                              double* __restrict__ out) {
+  const int i = blockIdx.x * CL_THREADS + threadIdx.x;
+  if (i >= n) return;
+  double m = -INFINITY, s = 0.0;
+  for (int q = 0; q < slices; ++q) {
+    const double mq = pm[(size_t)q * n + i], sq = ps[(size_t)q * n + i];
+    if (mq == -INFINITY) continue;
+    if (mq > m) {
+      s = s * exp(m - mq) + sq;
+      m = mq;
+    } else {
+      s += sq * exp(mq - m);
+    }
+  }
+  const int v = group[i];
+  const int nc = (unsigned)v < (unsigned)g ? bounds[2 * v + 1] - bounds[2 * v] : 0;
+  out[i] = (m == -INFINITY || nc < 2) ? 0.0 : exp(-(m + log(s) - log((double)(nc - 1))) / pw);
+}
+
 struct ClGrid {
   int row_tiles, col_tiles, slices, tiles_per_slice;
 };
@@ -761,6 +904,85 @@ extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32
   return WM_OK;
 }
 
+extern "C" size_t wm_mreach_min_edge_grouped_workspace_bytes(int n, int d, int g) {
+  if (n <= 0 || n > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
+  return (size_t)cl_grid(n, n, 128, true).slices * n * 8 + (size_t)g * 8 + 256;
+}
+
+extern "C" int wm_mreach_min_edge_grouped(const float* x, const float* core, const int32_t* comp, const int32_t* group, int n,
+                                          int d, int metric, int g, float* out_w, int32_t* out_j, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(x && core && comp && group && out_w && out_j && workspace, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && g > 0, WM_EINVAL);
+  WM_REQUIRE(n <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
+  const ClGrid gr = cl_grid(n, n, 128, true);
+  const size_t entries = (size_t)gr.slices * n;
+  WM_REQUIRE(workspace_bytes >= entries * 8 + (size_t)g * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = a.xr = x;
+  a.n = a.nr = n;
+  a.d = d;
+  a.tiles_per_slice = gr.tiles_per_slice;
+  a.col_tiles = gr.col_tiles;
+  a.core = core;
+  a.comp = comp;
+  a.inv_alpha = 1.f;  // (dist * 1 is dist: the weights are wm_mreach_min_edge's bits at alpha 1)
+  a.labels = group;
+  a.n_clusters = g;
+  a.part_w = static_cast<float*>(workspace);
+  a.part_j = reinterpret_cast<int*>(a.part_w + entries);
+  int* bounds = a.part_j + entries;
+  a.bounds = bounds;
+  cl_group_bounds<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(group, n, g, bounds);
+  WM_LAUNCH_CHECK();
+  const int rc = cl_launch<CL_MINEDGE_G, 8>(a, gr, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, gr.slices, n, out_w, out_j);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_allpoints_core_workspace_bytes(int n, int d, int g) {
+  if (n <= 0 || n > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
+  return (size_t)cl_grid(n, n, 64, true).slices * n * 16 + (size_t)g * 8 + 256;
+}
+
+extern "C" int wm_allpoints_core(const float* x, const int32_t* group, int n, int d, int metric, int g, double p, double* out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  WM_REQUIRE(x && group && out && workspace, WM_EINVAL);
+  WM_REQUIRE(n > 0 && d > 0 && g > 0 && p > 0.0 && p < (double)INFINITY, WM_EINVAL);
+  WM_REQUIRE(n <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+             WM_EALIGN);
+  const ClGrid gr = cl_grid(n, n, 64, true);
+  const size_t entries = (size_t)gr.slices * n;
+  WM_REQUIRE(workspace_bytes >= entries * 16 + (size_t)g * 8, WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = a.xr = x;
+  a.n = a.nr = n;
+  a.d = d;
+  a.tiles_per_slice = gr.tiles_per_slice;
+  a.col_tiles = gr.col_tiles;
+  a.labels = group;
+  a.n_clusters = g;
+  a.pw = p;
+  a.part_m = static_cast<double*>(workspace);
+  a.part_s = a.part_m + entries;
+  int* bounds = reinterpret_cast<int*>(a.part_s + entries);
+  a.bounds = bounds;
+  cl_group_bounds<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(group, n, g, bounds);
+  WM_LAUNCH_CHECK();
+  const int rc = cl_launch<CL_APCORE, 4>(a, gr, metric, st);
+  if (rc != WM_OK) return rc;
+  cl_apcore_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_m, a.part_s, gr.slices, n, group, bounds, g, p, out);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
 extern "C" size_t wm_mreach_query_workspace_bytes(int m, int n, int d) {
   if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0) return 0;
   return (size_t)cl_grid(m, n, 128, true).slices * m * 12 + 256;
@@ -829,9 +1051,15 @@ extern "C" size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g) 
   return (gr.slices > 1 ? (size_t)gr.slices * m * g * 8 : 0) + 256;
 }
 
-extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
-                                 float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// wm_group_min_dist (core_q = core = nullptr) and wm_group_min_mreach: one grid, one workspace layout, one merge.
+template <int MODE>
+int cl_group_min_run(const float* xq, const float* core_q, int m, const float* xe, const float* core, const int32_t* group,
+                     int e, int d, int metric, int g, float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                     void* stream) {
   WM_REQUIRE(xq && xe && group && out_dist && out_j && workspace, WM_EINVAL);
+  WM_REQUIRE(MODE == CL_GROUPMIN || (core_q && core), WM_EINVAL);
   WM_REQUIRE(m > 0 && e > 0 && d > 0 && g > 0, WM_EINVAL);
   WM_REQUIRE(m <= CL_MAX_N && e <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
   WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(xe) & 15) == 0 &&
@@ -849,11 +1077,13 @@ extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const 
   a.d = d;
   a.tiles_per_slice = gr.tiles_per_slice;
   a.col_tiles = gr.col_tiles;
+  a.core_q = core_q;
+  a.core = core;
   a.labels = group;
   a.n_clusters = g;
   a.group_d = gr.slices > 1 ? static_cast<float*>(workspace) : out_dist;
   a.group_j = gr.slices > 1 ? reinterpret_cast<int*>(a.group_d + entries) : out_j;
-  const int rc = cl_launch<CL_GROUPMIN, 4>(a, gr, metric, st);
+  const int rc = cl_launch<MODE, 4>(a, gr, metric, st);
   if (rc != WM_OK || gr.slices == 1) return rc;
   const size_t blocks = ((size_t)m * g + CL_THREADS - 1) / CL_THREADS;
   cl_group_min_merge<<<(unsigned)(blocks < 65536 ? blocks : 65536), CL_THREADS, 0, st>>>(a.group_d, a.group_j, group, gr.slices,
@@ -861,4 +1091,23 @@ extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const 
                                                                                        out_j);
   WM_LAUNCH_CHECK();
   return WM_OK;
+}
+
+}  // namespace
+
+extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
+                                 float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream) {
+  return cl_group_min_run<CL_GROUPMIN>(xq, nullptr, m, xe, nullptr, group, e, d, metric, g, out_dist, out_j, workspace,
+                                       workspace_bytes, stream);
+}
+
+extern "C" size_t wm_group_min_mreach_workspace_bytes(int m, int e, int d, int g) {
+  return wm_group_min_dist_workspace_bytes(m, e, d, g);
+}
+
+extern "C" int wm_group_min_mreach(const float* xq, const float* core_q, int m, const float* xe, const float* core,
+                                   const int32_t* group, int e, int d, int metric, int g, float* out_w, int32_t* out_j,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return cl_group_min_run<CL_GROUPMIN_MR>(xq, core_q, m, xe, core, group, e, d, metric, g, out_w, out_j, workspace,
+                                          workspace_bytes, stream);
 }
