@@ -786,7 +786,8 @@ int wm_eigencam(const void* act, int dtype, int N, int C, int H, int W, int out_
  * dumped embeddings, scored by silhouette).  x float32 [n][d] row-major, 16-byte aligned, d % 4 == 0, d <= 1024.
  * metric 0: Euclidean sqrt(sum (a_k - b_k)^2); 1: Manhattan sum |a_k - b_k| -- accumulated in float32 in index order from
  * the differences themselves, so dist(i, j) and dist(j, i) are the same bits, equal rows are at distance exactly 0 and
- * the relative error is at most (d + 3) * 2^-24 (csrc/cluster.hip).  No atomics: two calls give the same bits.
+ * the relative error is at most (d + 3) * 2^-24 (csrc/cluster.hip).  No floating-point atomics and none on global memory
+ * (wm_rank_query adds integers in LDS, nothing else is atomic): two calls give the same bits.
  *
  * wm_core_distance: out[i] = k-th smallest of dist(i, j) over all rows j, i itself included (so k = 1 gives 0:
  * sklearn.cluster.HDBSCAN's min_samples convention).  1 <= k <= 64, k <= n. */
@@ -873,6 +874,29 @@ size_t wm_group_min_mreach_workspace_bytes(int m, int e, int d, int g);
 int wm_group_min_mreach(const float* xq, const float* core_q, int m, const float* xe, const float* core, const int32_t* group,
                         int e, int d, int metric, int g, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* Ranks in a row's distance ordering (trustworthiness and continuity of an embedding, manifold.py): the two entry points
+ * under the same distance function.  The candidates of a row are ordered by (distance, index).
+ *
+ * wm_pair_dist: out[i][q] = dist(xq_i, x_j), j = idx[i][q], for idx int32 [m][k]: the bits every all-pairs entry point
+ * here gives that pair (wm_knn_graph / wm_knn_query return exactly these for their own lists).  An index outside [0, n)
+ * (-1 pads a list) gives +inf and reads nothing.  xq float32 [m][d], x float32 [n][d], both 16-byte aligned; out float32
+ * [m][k]; 1 <= k <= 64.  A gather kernel, one thread per pair; no workspace. */
+int wm_pair_dist(const float* xq, int m, const float* x, int n, int d, int metric, const int32_t* idx, int k, float* out,
+                 void* stream);
+/* wm_rank_query: count[i][q] = #{ columns l of x, l != skip[i] : (dist(xq_i, x_l), l) < (t[i][q], tj[i][q]) } in the
+ * lexicographic order, for k thresholds per row: t float32 [m][k] with their column indices tj int32 [m][k].  skip int32
+ * [m] names a column that is never counted for the row (the row itself when xq is x; -1: none).  A threshold of +inf or an
+ * index below 0 counts every column but the skipped one.  With t[i][q] = dist(xq_i, x_j) from wm_pair_dist and tj[i][q] =
+ * j, 1 + count is the 1-based rank of j among the candidates of row i, ties resolved by the index.
+ * Precondition: every row's thresholds are sorted ascending by (t, tj) (a kNN list is; +inf / negative indices last).
+ * With another order the counts are unspecified (no access leaves the buffers).  count int32 [m][k].  m, n >= 1,
+ * 1 <= k <= 64; xq, x and the workspace 16-byte aligned.  The workspace is one [m][k] int32 plane per column slice and
+ * nothing but padding when the rows alone fill the machine.  The counts are integers: the only atomics are integer adds
+ * in LDS, and two calls give the same bits. */
+size_t wm_rank_query_workspace_bytes(int m, int n, int d, int k);
+int wm_rank_query(const float* xq, int m, const float* x, int n, int d, int metric, const float* t, const int32_t* tj,
+                  const int32_t* skip, int k, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas

@@ -30,7 +30,10 @@ What the notebooks do, and where it is here:
 Outputs under --out: reduced.npz (`embeddings` float32 [n, components], `labels`: the format --embeddings reads; with
 --densmap also `rad_orig` and `rad_emb`, the log-radii of the data and of the embedding), umap.png for two components,
 summary.json (seconds per stage; sklearn trustworthiness on at most 5 000 seeded rows; with --densmap the Pearson
-correlation of the two radii as `radii_correlation`).  With --label-frac also `transformed` (the fitted rows placed
+correlation of the two radii as `radii_correlation`).  With --quality the summary also holds `trustworthiness_full`,
+`continuity_full` and `neighbor_preservation` over ALL fitted rows (manifold.embedding_quality: HIP rank kernels, the
+same k) with `quality_seconds`, and quality.npz the per-row vectors `trustworthiness_rows`, `continuity_rows` and
+`preservation_rows`.  With --label-frac also `transformed` (the fitted rows placed
 again by transform) and `labels_kept` in the summary; with --holdout `holdout`, `holdout_labels` (`embeddings` and
 `labels` then hold the fitted rows only) and `holdout_recall`: the mean share of a held-out row's 15 nearest fitted rows
 in feature space that are among its 15 nearest fitted points in the embedding.
@@ -91,6 +94,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--label-frac", type=float, default=None,
                     help="semi-supervised fit: keep a stratified fraction of the labels, -1 elsewhere; then transform the rows")
     ap.add_argument("--holdout", type=int, default=0, help="fit on all but the last N rows and transform those")
+    ap.add_argument("--quality", action="store_true",
+                    help="trustworthiness, continuity and neighbour preservation on ALL fitted rows (HIP rank kernels)")
     ap.add_argument("--init", choices=["spectral", "pca", "random"], default="spectral")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rows", type=int, default=0, help="use the first N rows only")
@@ -198,6 +203,15 @@ def main(argv=None) -> dict:
     pick = np.sort(np.random.default_rng(a.seed).permutation(n)[:5000])
     xs = x[torch.from_numpy(pick).to(x.device)].cpu().numpy()
     score = float(trustworthiness(xs, reduced[pick], n_neighbors=min(15, max(1, (pick.size - 1) // 2 - 1))))
+    quality = None
+    if a.quality:
+        # every fitted row, k as the sub-sampled score chooses it (sklearn needs k < n / 2)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        quality = manifold.embedding_quality(x, y, min(15, max(1, (n - 1) // 2 - 1)), metric=model.metric)
+        quality_seconds = time.perf_counter() - t0  # (the scores are on the host: nothing is pending)
+        np.savez(out / "quality.npz", trustworthiness_rows=quality.trustworthiness_rows, continuity_rows=quality.continuity_rows,
+                 preservation_rows=quality.preservation_rows)
     if a.components == 2:
         import matplotlib
 
@@ -213,6 +227,9 @@ def main(argv=None) -> dict:
     summary = {"n": n, "d": int(x.shape[1]), "n_neighbors": k, "n_components": a.components, "min_dist": a.min_dist,
                "n_epochs": n_epochs, "init": a.init, "a": model.a_, "b": model.b_, "graph_entries": int(graph.indices.numel()),
                "seconds": seconds, "trustworthiness": score, "trustworthiness_rows": int(pick.size)}
+    if quality is not None:
+        summary.update(trustworthiness_full=quality.trustworthiness, continuity_full=quality.continuity,
+                       neighbor_preservation=quality.neighbor_preservation, quality_seconds=quality_seconds)
     if a.densmap:
         summary.update(densmap=True, dens_lambda=model.dens_lambda, dens_frac=model.dens_frac, dens_var_shift=model.dens_var_shift,
                        radii_correlation=float(np.corrcoef(extra["rad_orig"].astype(np.float64),

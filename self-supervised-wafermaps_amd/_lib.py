@@ -308,6 +308,10 @@ SIGNATURES = {
     "wm_group_min_mreach_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_group_min_mreach": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_pair_dist": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "wm_rank_query_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_rank_query": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                              c_void_p, c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,

@@ -19,7 +19,14 @@
 //                         the three all-pairs parts of DBCV (density-based cluster validity) on rows sorted by cluster:
 //                         the all-points core distance (a power mean of a row's distances inside its own cluster), one
 //                         Boruvka round of every cluster's own mutual-reachability tree at once, and the group min with
-//                         the mutual reachability in place of the plain distance (the clusters' separations).
+//                         the mutual reachability in place of the plain distance (the clusters' separations);
+//   wm_pair_dist          the distances of listed pairs, out[i][q] = dist(xq[i], x[idx[i][q]]): a gather kernel of its own
+//                         (cl_pair_dist, a thread per pair) that calls the same cl_accum / cl_finish over the features in
+//                         index order, so a pair has the bits the tile pass gives it (the tile pass only adds the exact
+//                         zeros of the padding behind d);
+//   wm_rank_query         for the rows of a second matrix and k thresholds (t, tj) per row the number of columns l before
+//                         each threshold in the row's (distance, index) order -- the rank primitive of trustworthiness and
+//                         continuity (manifold.py); integer results.
 //
 // ONE distance function serves all of them (cl_accum / cl_finish below): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
@@ -73,6 +80,29 @@
 //             not.  cl_apcore_merge folds the slices' (M, S) in slice order and finishes the power mean.
 //   grouped min edge, group min of the mutual reachability: the min-edge mode with `group[j] == group[i]` as a further
 //             condition, and the group-min mode with max(core_q[i], core[j], dist) stored into the distance tile.
+//   rank      what is needed: per (row, q) the count of the columns l with (dist(i, l), l) < (t[i][q], tj[i][q]).  Two
+//             shapes were weighed.  (a) every thread compares each of its TM x 4 pairs with all k thresholds of the pair's
+//             row and the 16 lanes of a row are reduced by DPP: about 4 VALU instructions per (pair, threshold), 250 per
+//             pair at k = 63, against the 8 of the pair itself at d = 4 (2 per feature) and 1024 at d = 512 -- the
+//             epilogue would be 30 x the pair work in the 2-D embedding and still a quarter of it at d = 512.  (b), chosen:
+//             the caller passes every row's thresholds SORTED by (t, tj); a pair is then before the thresholds
+//             pos, pos + 1, ..., k - 1, pos = the first threshold behind the pair, so a thread finds pos by a binary
+//             search of the row's list in LDS (at most 6 steps of one ds_read of t, one of tj and 4 VALU) and adds 1 to
+//             the bin H[row][pos]; the row's counts are the prefix sums of its bins, taken once at the end of the slice.
+//             Before the search every pair is compared with the row's LAST threshold, kept in registers (3 VALU): a pair
+//             behind it counts nowhere and costs nothing more, and for a neighbour list those are all but about
+//             rank(last) of the n columns of a row, so the search and the add run for a small share of the pairs (a wave
+//             skips them when none of its 64 lanes needs them; when one does, the others idle through its chain of
+//             dependent LDS reads).  Measured on 12 449 rows (profiles/embedding_quality.md): the searches and adds are
+//             6 % of the pass at d = 512, k = 15 (0.66 x the kNN graph at the same k) and 48 % at d = 4, k = 15 (0.23 x
+//             the kNN graph), where staging, barriers and the root make up the rest.  All 256 threads take part; there
+//             is no owner scan per tile.  The bins are LDS integers with many writers: ds_add_u32 (integer atomics in
+//             LDS; integer sums do not depend on the order).  LDS at TM = 4: 18 KB of staging and 3 x 64 x (k | 1) x 4
+//             bytes for t, tj and the bins, 30 KB at k = 15 (three workgroups per CU: the 134 VGPRs bound it, not the
+//             LDS) and 66 KB at k = 63 (two per CU of 160 KB, 8 waves; TM = 8 would allow one).  TM = 4 keeps the LDS
+//             array far from its limit (the group-min note above) and gives 195 row tiles on 12 449 rows.
+//             A slice stores its counts into its own [m][k] plane and cl_rank_merge adds the planes; with one slice
+//             the kernel stores straight into the output.
 // Block-diagonal walk (all-points core, grouped min edge): with the rows sorted by group a row tile needs only the
 // columns from the first column of its first row's group to the last column of its last row's group.  cl_group_bounds
 // writes every present group's [first, last + 1) into the workspace (one thread per row, the run boundaries store);
@@ -80,9 +110,12 @@
 // of n_c^2 over the groups (rounded up to tiles) and not n^2.  Pairs of two groups inside a shared tile are masked.
 // Core, knn, min edge, query and group min split the columns into slices (grid.y) whose partial results a second small kernel combines in a
 // fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
-// atomics anywhere: two calls give the same bits.
+// floating-point atomics and no atomics on global memory anywhere; the only atomics are the rank mode's integer adds
+// into its LDS bins, whose sums do not depend on the order: two calls give the same bits.
 // Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
 // ((16 TM + 64) rows per 16 TM x 64 pairs).
+#include <limits.h>
+
 #include "common.h"
 
 namespace {
@@ -96,6 +129,7 @@ constexpr int CL_MAXK = 64;
 constexpr int CL_GROUPMIN_SLICES = 16;  // group min: at most this many column slices (the workspace: as many result planes)
 constexpr int CL_CORE = 0, CL_MINEDGE = 1, CL_SUMS = 2, CL_KNN = 3, CL_MREACHQ = 4, CL_GROUPMIN = 5;
 constexpr int CL_APCORE = 6, CL_MINEDGE_G = 7, CL_GROUPMIN_MR = 8;  // DBCV: the grouped forms
+constexpr int CL_RANK = 9;  // counts before per-row thresholds (no distance tile: thresholds and bins in its place)
 constexpr bool cl_is_minedge(int mode) { return mode == CL_MINEDGE || mode == CL_MINEDGE_G; }
 constexpr bool cl_is_groupmin(int mode) { return mode == CL_GROUPMIN || mode == CL_GROUPMIN_MR; }
 // the modes whose per-row best stays in registers (no distance tile in LDS)
@@ -146,12 +180,16 @@ struct ClArgs {
   double pw;
   double* part_m;
   double* part_s;
+  // rank (no field of its own, so that the other modes' argument block is what it was): core_q holds the rows' k
+  // thresholds sorted by (t, j) [nr][k], comp their column indices [nr][k], labels the column never counted [nr] and
+  // part_idx the counts [slices][nr][k] (the output itself when there is one slice)
 };
 
 template <int MODE, int TM>
 constexpr size_t cl_lds_bytes(int kl) {
   size_t f = (size_t)(16 * TM + CL_COLS) * CL_LDK;
-  if (!cl_keeps_best(MODE)) f += (size_t)16 * TM * CL_LDD;
+  if (!cl_keeps_best(MODE) && MODE != CL_RANK) f += (size_t)16 * TM * CL_LDD;
+  if (MODE == CL_RANK) f += (size_t)3 * 16 * TM * kl;  // thresholds, their indices, the bins
   if (MODE == CL_CORE) f += (size_t)16 * TM * kl;
   if (MODE == CL_KNN) f += (size_t)2 * 16 * TM * kl;
   if (MODE == CL_APCORE) f += (size_t)16 * TM * CL_LDD;  // (the tile holds doubles)
@@ -169,6 +207,10 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   [[maybe_unused]] float* Dt = Bs + CL_COLS * CL_LDK;  // (core, sums) the tile's distances [ROWS][CL_LDD]
   [[maybe_unused]] float* extra = Dt + ROWS * CL_LDD;  // core, knn: the k-lists [ROWS][kl]; sums: the tile's labels [64]
   [[maybe_unused]] int* extra_j = reinterpret_cast<int*>(extra) + ROWS * p.kl;  // knn: the lists' indices [ROWS][kl]
+  // rank: the rows' sorted thresholds, their column indices and the bins [ROWS][kl] each, where the other modes' tile is
+  [[maybe_unused]] float* Th = Dt;
+  [[maybe_unused]] int* Tj = reinterpret_cast<int*>(Dt) + ROWS * p.kl;
+  [[maybe_unused]] int* Hb = Tj + ROWS * p.kl;
   const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
   const int lq = (t & 7) * 4, lr = t >> 3;  // staging: float4 at feature lq of row lr (+ 32 per pass)
   const int n = p.n, nr = p.nr, d = p.d;
@@ -227,6 +269,45 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
       bw[r] = INFINITY;
       if constexpr (MODE == CL_MREACHQ) bd[r] = INFINITY;
       bj[r] = -1;
+    }
+  }
+  [[maybe_unused]] float tmx[TM];  // rank: the row's last (largest) threshold, its index and the column not counted
+  [[maybe_unused]] int tmj[TM], sk[TM];
+  if constexpr (MODE == CL_RANK) {
+    // +inf or an index of -1 stands for "behind every column": (+inf, INT_MAX).  Rows past the end get a last
+    // threshold no pair is before.  (The LDS lists are ordered by the chunk loop's barriers.)
+    const int k = p.k;
+    for (int q = t; q < ROWS * k; q += CL_THREADS) {
+      const int row = q / k, e = q - row * k;
+      float tv = INFINITY;
+      int jv = INT_MAX;
+      if (i0 + row < nr) {
+        tv = p.core_q[(size_t)(i0 + row) * k + e];
+        jv = p.comp[(size_t)(i0 + row) * k + e];
+        if (jv < 0 || tv == INFINITY) {
+          tv = INFINITY;
+          jv = INT_MAX;
+        }
+      }
+      Th[row * p.kl + e] = tv;
+      Tj[row * p.kl + e] = jv;
+      Hb[row * p.kl + e] = 0;
+    }
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      const int i = i0 + ty + 16 * r;
+      tmx[r] = -INFINITY;
+      tmj[r] = -1;
+      sk[r] = -1;
+      if (i < nr) {
+        tmx[r] = p.core_q[(size_t)i * k + k - 1];
+        tmj[r] = p.comp[(size_t)i * k + k - 1];
+        if (tmj[r] < 0 || tmx[r] == INFINITY) {
+          tmx[r] = INFINITY;
+          tmj[r] = INT_MAX;
+        }
+        sk[r] = p.labels[i];
+      }
     }
   }
   if constexpr (MODE == CL_CORE || MODE == CL_KNN) {
@@ -342,6 +423,27 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
             bw[r] = w;
             bd[r] = dist;
             bj[r] = j;
+          }
+        }
+      }
+    } else if constexpr (MODE == CL_RANK) {
+#pragma unroll
+      for (int r = 0; r < TM; ++r) {
+        const float* th = Th + (ty + 16 * r) * p.kl;
+        const int* tj = Tj + (ty + 16 * r) * p.kl;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int l = j0 + tx + 16 * c;
+          const float dv = cl_finish<METRIC>(acc[r][c]);
+          if (l < n && l != sk[r] && (dv < tmx[r] || (dv == tmx[r] && l < tmj[r]))) {
+            // the first threshold behind (dv, l): the last one is, so the answer lies in [0, k - 1]
+            int lo = 0, hi = p.k - 1;
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              const float u = th[mid];
+              if (dv < u || (dv == u && l < tj[mid])) hi = mid; else lo = mid + 1;
+            }
+            atomicAdd(&Hb[(ty + 16 * r) * p.kl + lo], 1);
           }
         }
       }
@@ -469,6 +571,18 @@ __global__ __launch_bounds__(CL_THREADS) void cl_pairs(const ClArgs p) {
   // ---- the slice's result
   if constexpr (MODE == CL_SUMS) {
     if (t < ROWS && i0 + t < nr && cur >= 0) p.out[(size_t)(i0 + t) * p.n_clusters + cur] += run;
+  }
+  if constexpr (MODE == CL_RANK) {
+    __syncthreads();  // every wave's adds are in the bins
+    if (t < ROWS && i0 + t < nr) {
+      const int* h = Hb + t * p.kl;
+      int* o = p.part_idx + ((size_t)blockIdx.y * nr + i0 + t) * p.k;
+      int before = 0;  // a pair in bin q is before the thresholds q, q + 1, ..., k - 1
+      for (int q = 0; q < p.k; ++q) {
+        before += h[q];
+        o[q] = before;
+      }
+    }
   }
   if constexpr (MODE == CL_APCORE) {
     if (t < ROWS && i0 + t < nr) {
@@ -693,6 +807,43 @@ __global__ __launch_bounds__(CL_THREADS) void cl_group_min_merge(const float* __
   }
 }
 
+// The slices' counts of every (row, threshold), added (integers: any order gives the same sum).
+__global__ __launch_bounds__(CL_THREADS) void cl_rank_merge(const int* __restrict__ parts, int slices, size_t total,
+                                                            int* __restrict__ out) {
+  for (size_t q = (size_t)blockIdx.x * CL_THREADS + threadIdx.x; q < total; q += (size_t)gridDim.x * CL_THREADS) {
+    int sum = 0;
+    for (int s = 0; s < slices; ++s) sum += parts[(size_t)s * total + q];
+    out[q] = sum;
+  }
+}
+
+// out[e] = dist(xq[e / k], x[idx[e]]) by the tile pass's own arithmetic: the same cl_accum over the features in index
+// order in one accumulator (the tile pass adds only exact zeros behind d), the same cl_finish.  An index outside [0, n)
+// gives +inf and reads nothing.
+template <int METRIC>
+__global__ __launch_bounds__(CL_THREADS) void cl_pair_dist(const float* __restrict__ xq, const float* __restrict__ x,
+                                                           const int* __restrict__ idx, int n, int d, int k, size_t total,
+                                                           float* __restrict__ out) {
+  for (size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x; e < total; e += (size_t)gridDim.x * CL_THREADS) {
+    const int j = idx[e];
+    float v = INFINITY;
+    if ((unsigned)j < (unsigned)n) {
+      const float4* a = reinterpret_cast<const float4*>(xq + (e / k) * d);
+      const float4* b = reinterpret_cast<const float4*>(x + (size_t)j * d);
+      float acc = 0.f;
+      for (int q = 0; q < d / 4; ++q) {
+        const float4 u = a[q], w = b[q];
+        acc = cl_accum<METRIC>(u.x, w.x, acc);
+        acc = cl_accum<METRIC>(u.y, w.y, acc);
+        acc = cl_accum<METRIC>(u.z, w.z, acc);
+        acc = cl_accum<METRIC>(u.w, w.w, acc);
+      }
+      v = cl_finish<METRIC>(acc);
+    }
+    out[e] = v;
+  }
+}
+
 // Per group present among the sorted ids its columns [first, last + 1): the two rows at a run's ends store them.  An id
 // outside [0, g) stores nothing.
 __global__ __launch_bounds__(CL_THREADS) void cl_group_bounds(const int* __restrict__ group, int n, int g,
@@ -867,6 +1018,66 @@ extern "C" int wm_knn_query(const float* xq, int m, const float* x, int n, int d
   const int rc = cl_launch<CL_KNN, 8>(a, g, metric, st);
   if (rc != WM_OK) return rc;
   cl_knn_merge<<<wm_cdiv(m, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, g.slices, m, k, dist, idx);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" int wm_pair_dist(const float* xq, int m, const float* x, int n, int d, int metric, const int32_t* idx, int k,
+                            float* out, void* stream) {
+  WM_REQUIRE(xq && x && idx && out, WM_EINVAL);
+  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, WM_EALIGN);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t total = (size_t)m * k;
+  const size_t blocks = (total + CL_THREADS - 1) / CL_THREADS;
+  const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
+  if (metric == 0)
+    cl_pair_dist<0><<<grid, CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
+  else
+    cl_pair_dist<1><<<grid, CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_rank_query_workspace_bytes(int m, int n, int d, int k) {
+  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
+  const ClGrid g = cl_grid(m, n, 64, true);
+  return (g.slices > 1 ? (size_t)g.slices * m * k * sizeof(int) : 0) + 256;
+}
+
+extern "C" int wm_rank_query(const float* xq, int m, const float* x, int n, int d, int metric, const float* t, const int32_t* tj,
+                             const int32_t* skip, int k, int32_t* count, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  WM_REQUIRE(xq && x && t && tj && skip && count && workspace, WM_EINVAL);
+  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+             WM_EALIGN);
+  const ClGrid g = cl_grid(m, n, 64, true);
+  const size_t entries = g.slices > 1 ? (size_t)g.slices * m * k : 0;
+  WM_REQUIRE(workspace_bytes >= entries * sizeof(int), WM_EWORKSPACE);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = {};
+  a.x = x;
+  a.n = n;
+  a.xr = xq;
+  a.nr = m;
+  a.d = d;
+  a.tiles_per_slice = g.tiles_per_slice;
+  a.col_tiles = g.col_tiles;
+  a.k = k;
+  a.kl = k | 1;  // odd pitch: the owners' prefix sums fall on distinct banks
+  a.core_q = t;
+  a.comp = tj;
+  a.labels = skip;
+  a.part_idx = g.slices > 1 ? static_cast<int*>(workspace) : count;
+  const int rc = cl_launch<CL_RANK, 4>(a, g, metric, st);
+  if (rc != WM_OK || g.slices == 1) return rc;
+  const size_t total = (size_t)m * k;
+  const size_t blocks = (total + CL_THREADS - 1) / CL_THREADS;
+  cl_rank_merge<<<(unsigned)(blocks < 65536 ? blocks : 65536), CL_THREADS, 0, st>>>(a.part_idx, g.slices, total, count);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

@@ -34,6 +34,13 @@ Semi-supervised fits and the transform of new rows (`reducer.fit(x, y=labels); r
      move -- all epochs in one launch, one wave per point (wm_umap_transform_layout).
 `UMAP` and `DensMAP` themselves keep raising for y= and transform and name these classes.
 
+How far a picture can be believed (`trustworthiness`, `continuity`, `embedding_quality`; sklearn.manifold.trustworthiness
+and its converse) is scored on ALL rows:
+  7. the neighbour lists of both spaces (wm_knn_graph at k + 1, the row removed by index), the distances of the listed
+     pairs in the other space (csrc/cluster.hip: wm_pair_dist) and the rank of every listed row in the other space's
+     (distance, index) order (wm_rank_query, one all-pairs pass with integer counts); the scores are float64 arithmetic
+     on those integer ranks on the host (`quality_from_ranks`).
+
 Not built: target_metric other than "categorical", inverse_transform, update (NotImplementedError naming the feature).
 Only local_connectivity = 1 and set_op_mix_ratio = 1 are supported.
 """
@@ -92,6 +99,63 @@ def negative_index(seed: int, epoch: int, entry: int, t: int, n: int) -> int:
 def is_sampled(q: int, epoch: int) -> bool:
     """Whether an entry of rate q (of 65536) is sampled at `epoch`: (E q) >> 16 times in E epochs."""
     return (((epoch + 1) * q) >> 16) > ((epoch * q) >> 16)
+
+
+class EmbeddingQuality(NamedTuple):
+    """The neighbourhood scores of an embedding at one k ("Trustworthiness and continuity"); the per-row
+    vectors are float64 [n] and the scores are their means."""
+    n_neighbors: int
+    trustworthiness: float
+    continuity: float
+    neighbor_preservation: float
+    trustworthiness_rows: np.ndarray
+    continuity_rows: np.ndarray
+    preservation_rows: np.ndarray
+
+
+def check_quality_k(n: int, k: int) -> int:
+    """sklearn's rule (n_neighbors < n_samples / 2, else the normaliser 2n - 3k - 1 can vanish) and the kNN kernels' (64
+    candidates, the row itself one of them)."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"n_neighbors ({k}) must be at least 1")
+    if 2 * k >= n:
+        raise ValueError(f"n_neighbors ({k}) should be less than n_samples / 2 ({n / 2})")
+    if k > MAX_NEIGHBORS - 1:
+        raise ValueError(f"n_neighbors ({k}) must be at most {MAX_NEIGHBORS - 1}")
+    return k
+
+
+def _penalty_score(ranks, n: int, k: int):
+    """(1 - 2 / (n k (2n - 3k - 1)) * sum_i pen_i, the per-row values 1 - 2 / (k (2n - 3k - 1)) * pen_i float64 [n]) with
+    pen_i = sum_j max(0, rank - k) over the first k entries of row i.  The sums are exact integers (int64), followed by
+    one multiply and one subtract."""
+    pen = np.maximum(ranks[:, :k].astype(np.int64) - k, 0).sum(axis=1)
+    norm = k * (2.0 * n - 3.0 * k - 1.0)
+    return 1.0 - float(pen.sum()) * (2.0 / (n * norm)), 1.0 - pen.astype(np.float64) * (2.0 / norm)
+
+
+def quality_from_ranks(ranks_x, ranks_emb, n_neighbors):
+    """Trustworthiness, continuity and neighbour preservation from integer ranks, in float64 on the host.
+    ranks_x int [n, K]: r_x(i, j), the 1-based rank (self excluded, ties by index) in the INPUT space of the j that is
+    the q-th neighbour of row i in the EMBEDDING; ranks_emb int [n, K]: the rank in the embedding of the q-th neighbour
+    in the input space.  Both lists are ordered, so their first k columns belong to N_k for every k <= K: `n_neighbors`
+    may be one k (an EmbeddingQuality is returned) or a sequence of them (a list, equal to the separate calls).  A
+    neighbour of one space is one of the other exactly when its rank there is at most k, which gives the preservation
+    from either matrix (the trustworthiness side is used)."""
+    ranks_x, ranks_emb = np.asarray(ranks_x), np.asarray(ranks_emb)
+    if ranks_x.ndim != 2 or ranks_x.shape != ranks_emb.shape or ranks_x.dtype.kind not in "iu" or ranks_emb.dtype.kind not in "iu":
+        raise ValueError("two integer rank matrices [n, K] of one shape expected")
+    if np.ndim(n_neighbors) > 0:
+        return [quality_from_ranks(ranks_x, ranks_emb, int(k)) for k in n_neighbors]
+    n, width = ranks_x.shape
+    k = check_quality_k(n, n_neighbors)
+    if k > width:
+        raise ValueError(f"n_neighbors ({k}) exceeds the {width} ranks per row")
+    t, t_rows = _penalty_score(ranks_x, n, k)
+    c, c_rows = _penalty_score(ranks_emb, n, k)
+    p_rows = (ranks_x[:, :k] <= k).sum(axis=1).astype(np.float64) / k
+    return EmbeddingQuality(k, t, c, float(p_rows.mean()), t_rows, c_rows, p_rows)
 
 
 # ------------------------------------------------------------------------------------------------ GPU steps
@@ -165,6 +229,126 @@ def knn_query(xq, x, k: int, metric: str = "euclidean"):
     idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
     check(lib.wm_knn_query(ptr(xq), m, ptr(x), n, d, code, k, ptr(dist), ptr(idx), ptr(ws), need, stream_ptr()), "wm_knn_query")
     return dist, idx
+
+
+def _pair_args(name: str, xq, x, idx):
+    import torch
+
+    xq, x = _prep(xq), _prep(x)
+    require_gpu(idx)
+    if xq.shape[1] != x.shape[1]:
+        raise ValueError(f"xq has {xq.shape[1]} features, x has {x.shape[1]}")
+    if xq.shape[0] < 1 or x.shape[0] < 1:
+        raise ValueError("at least one row expected on either side")
+    if idx.dim() != 2 or idx.shape[0] != xq.shape[0] or idx.dtype != torch.int32:
+        raise ValueError(f"idx int32 [m = {xq.shape[0]}, k] expected")
+    if not 1 <= idx.shape[1] <= MAX_NEIGHBORS:
+        raise ValueError(f"{name}: k ({idx.shape[1]}) must be in [1, {MAX_NEIGHBORS}]")
+    return xq, x
+
+
+def pair_distances(xq, x, idx, metric: str = "euclidean"):
+    """out[i, q] = dist(xq[i], x[idx[i, q]]) float32 [m, k] on the device for idx int32 [m, k] (device tensors): the bits
+    `knn_graph` / `knn_query` give that pair (their own lists come back with their own distances).  An entry of -1 (or any
+    index outside [0, n)) gives +inf.  1 <= k <= 64."""
+    import torch
+
+    code = metric_code(metric)
+    xq, x = _pair_args("pair_distances", xq, x, idx)
+    (m, d), n, k = xq.shape, x.shape[0], idx.shape[1]
+    out = torch.empty((m, k), dtype=torch.float32, device=x.device)
+    check(_lib.load().wm_pair_dist(ptr(xq), m, ptr(x), n, d, code, ptr(idx), k, ptr(out), stream_ptr()), "wm_pair_dist")
+    return out
+
+
+def neighbor_ranks(xq, x, idx, metric: str = "euclidean", exclude_self: bool = False):
+    """The 1-based rank of x[idx[i, q]] among the rows of x as seen from xq[i], int32 [m, k] on the device:
+    1 + #{ l : (dist(i, l), l) < (dist(i, j), j) }, j = idx[i, q] -- the candidates ordered by (distance, index) as
+    `knn_query` orders them, so the q-th entry of that row's kNN list has rank q + 1.  exclude_self (xq is x, m = n):
+    column i is never counted for row i (the rank among the other rows).  An entry of -1 ranks behind every column.
+    The distances of the listed pairs come from `pair_distances`, the counts from wm_rank_query (one all-pairs pass)."""
+    import torch
+
+    code = metric_code(metric)
+    xq, x = _pair_args("neighbor_ranks", xq, x, idx)
+    (m, d), n, k = xq.shape, x.shape[0], idx.shape[1]
+    if exclude_self and m != n:
+        raise ValueError(f"exclude_self needs the rows of x themselves as queries (m = {m}, n = {n})")
+    lib = _lib.load()
+    need = lib.wm_rank_query_workspace_bytes(m, n, d, k)
+    if need == 0:
+        raise ValueError(f"neighbor_ranks: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})")
+    thr = pair_distances(xq, x, idx, metric)
+    # the kernel wants every row's thresholds sorted by (distance, index): a stable sort by the index, then by the distance
+    by_j = torch.sort(idx, dim=1, stable=True).indices
+    order = by_j.gather(1, torch.sort(thr.gather(1, by_j), dim=1, stable=True).indices)
+    t_sorted, j_sorted = thr.gather(1, order).contiguous(), idx.gather(1, order).contiguous()
+    skip = (torch.arange(m, dtype=torch.int32, device=x.device) if exclude_self
+            else torch.full((m,), -1, dtype=torch.int32, device=x.device))
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    count = torch.empty((m, k), dtype=torch.int32, device=x.device)
+    check(lib.wm_rank_query(ptr(xq), m, ptr(x), n, d, code, ptr(t_sorted), ptr(j_sorted), ptr(skip), k, ptr(count), ptr(ws),
+                            need, stream_ptr()), "wm_rank_query")
+    ranks = torch.empty_like(count)
+    ranks.scatter_(1, order, count + 1)
+    return ranks
+
+
+def neighbor_lists(x, k: int, metric: str = "euclidean"):
+    """N_k of every row: the first k rows OTHER than the row itself in its (distance, index) order, int32 [n, k] on the
+    device.  `knn_graph` at k + 1 with the row removed by index, not by distance: exact duplicates of the row stay, and
+    when more than k duplicates with lower indices push the row out of its own list the last entry goes instead."""
+    import torch
+
+    idx = knn_graph(x, k + 1, metric)[1]
+    own = idx == torch.arange(idx.shape[0], dtype=torch.int32, device=idx.device).unsqueeze(1)
+    keep = torch.sort(own.to(torch.int8), dim=1, stable=True).indices[:, :k]  # (the row itself moves to the end)
+    return idx.gather(1, keep).contiguous()
+
+
+def embedding_quality(x, embedding, n_neighbors=5, metric: str = "euclidean", embedding_metric: str = "euclidean"):
+    """Trustworthiness, continuity and neighbour preservation of `embedding` [n, Db] for the rows x [n, Da] (device
+    tensors) on ALL rows: an EmbeddingQuality, or a list of them when n_neighbors is a sequence (one pass at the largest
+    k serves every smaller one).  Two `knn_graph` calls (k + 1, the row removed by index) give the neighbour lists of
+    both spaces, two rank passes (`neighbor_ranks`) the rank of every neighbour of one space in the other; the scores
+    are `quality_from_ranks` of those integers, float64 on the host.  n_neighbors < n / 2 and <= 63."""
+    x, embedding = _prep(x), _prep(embedding)
+    n = x.shape[0]
+    if embedding.shape[0] != n:
+        raise ValueError(f"x has {n} rows, the embedding {embedding.shape[0]}")
+    ks = [int(k) for k in n_neighbors] if np.ndim(n_neighbors) > 0 else [int(n_neighbors)]
+    if not ks:
+        raise ValueError("at least one n_neighbors expected")
+    for k in ks:
+        check_quality_k(n, k)
+    near_x = neighbor_lists(x, max(ks), metric)
+    near_e = neighbor_lists(embedding, max(ks), embedding_metric)
+    ranks_x = neighbor_ranks(x, x, near_e, metric, exclude_self=True).cpu().numpy()
+    ranks_e = neighbor_ranks(embedding, embedding, near_x, embedding_metric, exclude_self=True).cpu().numpy()
+    res = quality_from_ranks(ranks_x, ranks_e, ks)
+    return res if np.ndim(n_neighbors) > 0 else res[0]
+
+
+def trustworthiness(x, embedding, n_neighbors: int = 5, metric: str = "euclidean", embedding_metric: str = "euclidean",
+                    return_rows: bool = False):
+    """sklearn.manifold.trustworthiness on every row, on the device: 1 - 2 / (n k (2n - 3k - 1)) * the sum over the
+    rows i and their k nearest rows j IN THE EMBEDDING of max(0, r_x(i, j) - k), r_x the rank of j in the input space.
+    Ties are resolved by the index (sklearn: arbitrarily).  return_rows: (score, per-row values float64 [n])."""
+    x, embedding = _prep(x), _prep(embedding)
+    n = x.shape[0]
+    if embedding.shape[0] != n:
+        raise ValueError(f"x has {n} rows, the embedding {embedding.shape[0]}")
+    k = check_quality_k(n, n_neighbors)
+    ranks = neighbor_ranks(x, x, neighbor_lists(embedding, k, embedding_metric), metric, exclude_self=True).cpu().numpy()
+    score, rows_ = _penalty_score(ranks, n, k)
+    return (score, rows_) if return_rows else score
+
+
+def continuity(x, embedding, n_neighbors: int = 5, metric: str = "euclidean", embedding_metric: str = "euclidean",
+               return_rows: bool = False):
+    """Trustworthiness with the two spaces exchanged: the neighbours of the input space, ranked in the embedding (how
+    many true neighbours the embedding tore apart).  continuity(a, b) is trustworthiness(b, a) in bits."""
+    return trustworthiness(embedding, x, n_neighbors, embedding_metric, metric, return_rows)
 
 
 def smooth_knn_query(dist):
