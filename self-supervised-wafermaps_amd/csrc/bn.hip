@@ -537,52 +537,93 @@ __global__ __launch_bounds__(BN_THREADS, FORM == 0 ? 4 : 1) void bn_bwd_apply(co
 // a 2 x 2 pixel quad x 8 channels.  The quad's pixels are covered by the four windows (a, b), (a, b+1),
 // (a+1, b), (a+1, b+1) only, so the pooled gradient and the window positions are read 4 times per
 // quad instead of 9 (1 + 2 + 2 + 4 per pixel), with fixed position codes per (pixel, window).
+//
+// Work assignment.  The window row a+1 is needed by the quad rows a and a+1, so with one quad per thread every row of the
+// pooled gradient and of the positions (205 + 103 MB for the step's stem) is fetched twice, and in a grid-stride walk the
+// two readers sat 1.75 blocks apart, on two XCDs with two L2s: one extra copy, 325 MB measured.  Here a thread owns the
+// two vertically adjacent quads (2k, b) and (2k+1, b): the window rows 2k, 2k+1, 2k+2 x two columns = six windows, each
+// loaded once, instead of eight.  Row 2k+2 is still shared with the pair k+1 (3 rows fetched per 2 distinct) and the
+// window column b+1 with the neighbouring lanes; for those a block owns 256 consecutive items (channel chunk fastest,
+// then b, then k, then n) and the hardware block ids are remapped (wm_xcd_swizzle) so that each XCD walks a contiguous
+// range of them and the pairs k and k+1 meet in one L2.  When H / 2 is odd the last pair's second quad does not exist and
+// is skipped.  The arithmetic per element is that of the one-quad form, operation for operation.
 __global__ __launch_bounds__(BN_THREADS) void bn_pool_bwd_apply(const uint16_t* __restrict__ y,
                                                                 const float* __restrict__ coef, int n_coef, int N, int C,
-                                                                int imgs_per_group, int remask,
-                                                                uint16_t* __restrict__ dy, const PoolSrc ps,
-                                                                const WmDiv d_cpr, const WmDiv d_wb, const WmDiv d_ha,
+                                                                int remask, uint16_t* __restrict__ dy, const PoolSrc ps,
+                                                                const WmDiv d_cpr, const WmDiv d_wb, const WmDiv d_ha2,
                                                                 const WmDiv d_ipg) {
-  // 32-bit index arithmetic (host-checked range): the kernel is VALU-bound, see pool.hip
+  // 32-bit arithmetic on 16-byte chunk indices (host-checked range): the kernel is VALU-bound, see pool.hip
   const uint32_t cpr = (uint32_t)C >> 3;
   const uint32_t HA = (uint32_t)ps.H >> 1, WB = (uint32_t)ps.W >> 1;
-  const uint32_t total = (uint32_t)N * HA * WB * cpr;
+  const uint32_t total = (uint32_t)N * d_ha2.d * WB * cpr;  // d_ha2.d = ceil(HA / 2) quad pairs per column
   // The coefficient rows of every group sit in LDS ([G][7][C] floats, a few KB) and are read where they are used: held in
-  // registers across the loop (first build: 56 of them) the kernel needed 196 registers -- two waves per SIMD for a pass
-  // that moves 2.3 GB.
+  // registers across the pixels (first build: 56 of them) the kernel needed 196 registers -- two waves per SIMD for a pass
+  // that moves 2 GB.
+  // A block lives for one item per thread, so nothing amortises its trips to memory over a loop.  All of them start before
+  // the first wait: the table's first 256 float4 (all of it for the stem: 2 x 7 x 64 floats), the six windows and the eight
+  // pixels of y (68 registers of loads in flight; the kernel stays at three waves per SIMD), then the table goes into LDS
+  // behind them.  With the table staged first, and y read pixel by pixel, the pair form was slower than the one-quad form
+  // it replaces (451 us against 427 us) although it fetched 325 MB less; in this order it takes 330 us.
   extern __shared__ __attribute__((aligned(16))) float pool_coef[];
-  for (int i = threadIdx.x; i < n_coef; i += BN_THREADS) pool_coef[i] = coef[i];
-  __syncthreads();
-  for (uint32_t t = blockIdx.x * BN_THREADS + threadIdx.x; t < total; t += gridDim.x * BN_THREADS) {
-    uint32_t rc, rb, ra;
-    uint32_t u = wm_divmod(t, d_cpr, rc);
-    const int c0 = (int)rc * 8;
-    u = wm_divmod(u, d_wb, rb);
-    const int n = (int)wm_divmod(u, d_ha, ra);
-    const int b = (int)rb, a = (int)ra;
-    const int g = (int)wm_div((uint32_t)n, d_ipg);
-    const float* kk = pool_coef + (size_t)g * 7 * C + c0;
-    auto krow = [&](int q, float (&v)[8]) {
-      const float4 lo = *reinterpret_cast<const float4*>(kk + q * C);
-      const float4 hi = *reinterpret_cast<const float4*>(kk + q * C + 4);
-      v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-    };
-    // the four windows (clamped addresses; an out-of-range window contributes nothing)
-    uint2 pk[4];
-    uint4 dv[4];
-    bool wok[4];
+  const int n_coef4 = n_coef >> 2;  // (C % 8 == 0)
+  const float4* coef4 = reinterpret_cast<const float4*>(coef);
+  float4 coef_first = make_float4(0.f, 0.f, 0.f, 0.f);
+  if ((int)threadIdx.x < n_coef4) coef_first = coef4[threadIdx.x];
+  const uint32_t t_raw = wm_xcd_swizzle(blockIdx.x, gridDim.x) * BN_THREADS + threadIdx.x;
+  const bool active = t_raw < total;
+  const uint32_t t = active ? t_raw : total - 1;  // (an idle thread of the last block requests the last item's windows)
+  uint32_t rc, rb, rk;
+  uint32_t u = wm_divmod(t, d_cpr, rc);
+  const int c0 = (int)rc * 8;
+  u = wm_divmod(u, d_wb, rb);
+  const uint32_t n = wm_divmod(u, d_ha2, rk);
+  const int b = (int)rb, a0 = 2 * (int)rk;  // the quads (a0, b) and (a0 + 1, b)
+  const int g = (int)wm_div(n, d_ipg);
+  const float* kk = pool_coef + (size_t)g * 7 * C + c0;
+  auto krow = [&](int q, float (&v)[8]) {
+    const float4 lo = *reinterpret_cast<const float4*>(kk + q * C);
+    const float4 hi = *reinterpret_cast<const float4*>(kk + q * C + 4);
+    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+  };
+  // the six windows (a0 + i, b + jq), i = 0..2 (clamped addresses; an out-of-range window contributes nothing)
+  const uint2* idx2 = reinterpret_cast<const uint2*>(ps.idx);
+  const uint4* pdy4 = reinterpret_cast<const uint4*>(ps.dy);
+  uint2 pk[6];
+  uint4 dv[6];
+  bool wok[6];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int p = a + (j >> 1), q = b + (j & 1);
-      wok[j] = p < ps.P && q < ps.Q;
-      const int pc = p < ps.P ? p : ps.P - 1, qc = q < ps.Q ? q : ps.Q - 1;
-      const size_t o = ((size_t)(n * ps.P + pc) * ps.Q + qc) * C + c0;
-      pk[j] = *reinterpret_cast<const uint2*>(ps.idx + o);
-      dv[j] = *reinterpret_cast<const uint4*>(ps.dy + o);
-    }
-    float dw[4][8];
+  for (int j = 0; j < 6; ++j) {
+    const int p = a0 + (j >> 1), q = b + (j & 1);
+    wok[j] = p < ps.P && q < ps.Q;
+    const int pc = p < ps.P ? p : ps.P - 1, qc = q < ps.Q ? q : ps.Q - 1;
+    const uint32_t o = ((n * (uint32_t)ps.P + (uint32_t)pc) * (uint32_t)ps.Q + (uint32_t)qc) * cpr + rc;
+    pk[j] = idx2[o];
+    dv[j] = pdy4[o];
+  }
+  // the pixels of both quads (a missing second quad reads the first one's again and is not used)
+  const uint4* y4 = reinterpret_cast<const uint4*>(y);
+  uint4 yv[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) unpack8(dv[j], dw[j]);
+  for (int i = 0; i < 8; ++i) {
+    const int a = a0 + (i >> 2), dh = (i >> 1) & 1, dwp = i & 1;
+    const int ac = (uint32_t)a < HA ? a : a0;
+    yv[i] = y4[((n * (uint32_t)ps.H + (uint32_t)(2 * ac + dh)) * (uint32_t)ps.W + (uint32_t)(2 * b + dwp)) * cpr + rc];
+  }
+  {
+    float4* lds4 = reinterpret_cast<float4*>(pool_coef);
+    if ((int)threadIdx.x < n_coef4) lds4[threadIdx.x] = coef_first;
+    for (int i = threadIdx.x + BN_THREADS; i < n_coef4; i += BN_THREADS) lds4[i] = coef4[i];
+    __syncthreads();
+  }
+  if (!active) return;  // (behind the only barrier)
+  float dw[6][8];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) unpack8(dv[j], dw[j]);
+  uint4* dy4 = reinterpret_cast<uint4*>(dy);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int a = a0 + s;
+    if (s == 1 && (uint32_t)a >= HA) break;
     // pixel (dh, dw) of the quad, window j = (jp, jq): position code (2 dh + 1 - 2 jp... ) = kh * 3 + kw with
     // kh = 2a + dh - (2 (a + jp) - 1) = dh + 1 - 2 jp, kw likewise; valid when 0 <= kh, kw <= 2
 #pragma unroll
@@ -596,19 +637,20 @@ __global__ __launch_bounds__(BN_THREADS) void bn_pool_bwd_apply(const uint16_t* 
         const int kh = dh + 1 - 2 * (j >> 1), kw = dwp + 1 - 2 * (j & 1);
         if (kh < 0 || kw < 0) continue;  // compile-time after unrolling
         const int code = kh * 3 + kw;
-        if (wok[j]) {
+        const int jw = j + 2 * s;  // window (a + jp, b + jq) among the six
+        if (wok[jw]) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            const int ie = (int)(((e < 4 ? pk[j].x : pk[j].y) >> (8 * (e & 3))) & 0xff);
-            fd[e] += ie == code ? dw[j][e] : 0.f;
+            const int ie = (int)(((e < 4 ? pk[jw].x : pk[jw].y) >> (8 * (e & 3))) & 0xff);
+            fd[e] += ie == code ? dw[jw][e] : 0.f;
           }
         }
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) fd[e] = bf2f(f2bf(fd[e]));  // as maxpool_bwd would have stored it
-      const size_t off = ((size_t)(n * ps.H + 2 * a + dh) * ps.W + 2 * b + dwp) * C + c0;
+      const uint32_t off = ((n * (uint32_t)ps.H + (uint32_t)(2 * a + dh)) * (uint32_t)ps.W + (uint32_t)(2 * b + dwp)) * cpr + rc;
       float fy[8];
-      unpack8(*reinterpret_cast<const uint4*>(y + off), fy);
+      unpack8(yv[4 * s + pix], fy);
       if (remask) {
         float k5[8], k6[8];
         krow(5, k5);
@@ -628,7 +670,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_pool_bwd_apply(const uint16_t* 
       krow(2, k0);
 #pragma unroll
       for (int e = 0; e < 8; ++e) r[e] = k0[e] * r[e];
-      *reinterpret_cast<uint4*>(dy + off) = pack8(r);
+      dy4[off] = pack8(r);
     }
   }
 }
@@ -1035,9 +1077,13 @@ int bn_bwd_impl(const void* y_, const void* dout_, const void* out_relu_, int re
   if (ps.dy != nullptr && !dz && !out_relu && (ps.H & 1) == 0 && (ps.W & 1) == 0 && BN_THREADS % tpr == 0 &&
       rows * tpr < (1ll << 31) && (size_t)G * 7 * C * sizeof(float) <= 32768) {  // (32-bit item indices; coefficient rows in LDS)
     const int n_img = (int)(rows / ((long long)ps.H * ps.W));
-    bn_pool_bwd_apply<<<stream_grid(rows / 4 * tpr), BN_THREADS, (size_t)G * 7 * C * sizeof(float), st>>>(
-        y, coef, G * 7 * C, n_img, C, n_img / G, remask ? 1 : 0, dy, ps, wm_div_make((uint32_t)(C >> 3)),
-        wm_div_make((uint32_t)(ps.W >> 1)), wm_div_make((uint32_t)(ps.H >> 1)), wm_div_make((uint32_t)(n_img / G)));
+    // one thread per pair of vertically adjacent 2 x 2 quads x 8 channels, one block per 256 consecutive items (the kernel
+    // remaps the block ids so that neighbouring blocks share an L2)
+    const int ha2 = ((ps.H >> 1) + 1) / 2;
+    bn_pool_bwd_apply<<<wm_cdiv((long long)n_img * ha2 * (ps.W >> 1) * tpr, BN_THREADS), BN_THREADS,
+                        (size_t)G * 7 * C * sizeof(float), st>>>(
+        y, coef, G * 7 * C, n_img, C, remask ? 1 : 0, dy, ps, wm_div_make((uint32_t)(C >> 3)),
+        wm_div_make((uint32_t)(ps.W >> 1)), wm_div_make((uint32_t)ha2), wm_div_make((uint32_t)(n_img / G)));
     WM_LAUNCH_CHECK();
     return WM_OK;
   }
