@@ -19,7 +19,8 @@ ulp, three orders below a bf16 rounding) and the fluctuation of a maximum over a
 tensor that needs more is a finding; a call that passes a wider factor says next to it what was measured and why.
 
 The module also holds the emulations (attention, LayerNorm, bias / activation, Linear, the GELU MLP, the convolutions
-of csrc/conv.hip with their fused statistics and BatchNorm-backward epilogue), each with
+of csrc/conv.hip with their fused statistics and BatchNorm-backward epilogue, the BatchNorm entry points of csrc/bn.hip with
+the launch arithmetic their block sums follow, the pooling of csrc/pool.hip), each with
 switches that seed one wrong computation, and the input families.  tests/test_kernel_check_cpu.py proves on the CPU
 that every seeded error is rejected by `check` on these families; the GPU tests feed the kernels the same families.
 """
@@ -91,9 +92,11 @@ def _abs_term(emul, ref64) -> float:
     return float(torch.kthvalue(d, k).values)
 
 
-def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0):
+def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False):
     """[(criterion, measured, bound)] and whether `got` is finite; no assertion (the CPU proofs use this).
-    abs_floor: a lower limit of criterion 4's absolute term (see f32_sum_floor)."""
+    abs_floor: a lower limit of criterion 4's absolute term (see f32_sum_floor).
+    floor_all (the float32 statistics of BatchNorm): criteria 1 and 2 are not asked to go below `factor` roundings of
+    abs_floor either -- see f32_stat_floor."""
     g = _flat64(got)
     finite = bool(torch.isfinite(g).all())
     a = max(_abs_term(emul, ref64), float(abs_floor))
@@ -108,6 +111,10 @@ def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0):
             # a >= one float32 rounding at the scale of the summed magnitudes: a score <= 1 is within that one rounding,
             # which no summation order can promise to beat (the row-order yardstick often adds few bf16 terms exactly)
             return max(factor * yard[k], 1.0)
+        if floor_all and abs_floor > 0 and k != "1 - cosine":
+            r = _flat64(ref64)
+            scale = r.abs().max() if k.startswith("max |err| / max") else r.pow(2).mean().sqrt()
+            return max(factor * yard[k], factor * abs_floor / (float(scale) + 1e-300))
         return factor * yard[k]
 
     if not finite:
@@ -124,14 +131,25 @@ def f32_sum_floor(terms) -> float:
     return float(2.0 ** -24 * terms.detach().double().abs().sum(0).max())
 
 
+def f32_stat_floor(*magnitudes) -> float:
+    """Absolute term for a float32 STATISTIC that is a short chain of float32 operations on sums (a mean, a running
+    statistic after a few updates, a coefficient): one float32 rounding (2^-24) at the largest magnitude that enters it.
+    With verdict(floor_all=True) criteria 1 and 2 accept `factor` such roundings: on two or three rows, or on one update
+    rm' = (1 - momentum) rm + momentum mean, the float32 restatement often lands on the exact value (its score is 0, or a
+    twentieth of an ulp), while a kernel that contracts the same expression into an fma, or adds its row lanes in another
+    order, is one rounding away -- measured on the MI355X: running_mean at 5.3x the factor-4 bound of such a lucky
+    yardstick (37 x 2048, G = 2), all of it one float32 ulp of the largest channel."""
+    return float(2.0 ** -24 * max(float(torch.as_tensor(m).detach().double().abs().max()) for m in magnitudes))
+
+
 def passes(got, ref64, emul, factor: float = FACTOR) -> bool:
     rows, finite = verdict(got, ref64, emul, factor)
     return finite and all(m <= b for _, m, b in rows)
 
 
-def check(got, ref64, emul, what: str, factor: float = FACTOR, abs_floor: float = 0.0) -> float:
+def check(got, ref64, emul, what: str, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False) -> float:
     """Assert the four criteria (each logged through parity()); returns the worst measured / bound ratio."""
-    rows, finite = verdict(got, ref64, emul, factor, abs_floor)
+    rows, finite = verdict(got, ref64, emul, factor, abs_floor, floor_all)
     assert finite, f"{what}: result holds inf / nan"
     worst = 0.0
     failed = []
@@ -726,3 +744,429 @@ def f32_sum_bound(vals, tiles):
     gam = lambda j: j * u / (1.0 - j * u)  # noqa: E731
     return (torch.stack([gam(len(t) - 1) * v[t].abs().sum(0) for t in tiles]),
             torch.stack([gam(len(t)) * (v[t] * v[t]).sum(0) for t in tiles]))
+
+
+# ------------------------------------------------------------------------------------------------ BatchNorm (csrc/bn.hip)
+# A tensor is rows [rows, C]; G equal runs of rows are the statistics groups.  The launch arithmetic of bn.hip, mirrored so
+# that the emulation sums over the kernel's own blocks and the tests can assert which path a shape reaches:
+BN_THREADS = 256
+BN_STREAM_BLOCKS = 256 * 16          # stream_grid: blocks of the apply passes at the most
+BN_SLOTS_DIRECT, BN_SLOTS_REDUCED = 512, 128
+
+
+def bn_rpp(c):
+    """row lanes of a bn_reduce block: BN_THREADS / (C / 8) threads-per-row, at least one"""
+    return max(BN_THREADS // (c >> 3), 1)
+
+
+def bn_reduce_blocks(rpg, c):
+    return max(1, min(256, -(-rpg // (bn_rpp(c) * 16))))
+
+
+def bn_block_rows(rpg, c):
+    """[(first, last + 1)] rows of every bn_reduce block of a group (launch_reduce: ceil(rpg / nblk) rows each, clipped)"""
+    nblk = bn_reduce_blocks(rpg, c)
+    per = -(-rpg // nblk)
+    return [(min(b * per, rpg), min((b + 1) * per, rpg)) for b in range(nblk)]
+
+
+def bn_chunk_pow2(c):
+    cpr = c >> 3
+    return cpr > 0 and cpr & (cpr - 1) == 0 and BN_THREADS % cpr == 0
+
+
+def bn_stream_grid(items):
+    return max(1, min(BN_STREAM_BLOCKS, -(-items // BN_THREADS)))
+
+
+def bn_prereduce_plan(t):
+    """(R, output slots) of stats_prereduce for T > BN_SLOTS_DIRECT slots per group, else (1, T)"""
+    if t <= BN_SLOTS_DIRECT:
+        return 1, t
+    r = 1
+    while -(-t // r) > BN_SLOTS_REDUCED:
+        r *= 2
+    return r, -(-t // r)
+
+
+def bn_wide(rows, c, groups):
+    return 2048 < c <= 16384 and rows // groups <= 65536
+
+
+def fma_colsum_f32(a, b):
+    """sum over rows of a * b by acc = fmaf(a, b, acc) in float32, one row after the other (a bf16-exact, so the product is
+    exact in float64 and the only rounding is the accumulator's)"""
+    a, b = a.detach().double().cpu().numpy(), b.detach().double().cpu().numpy()
+    acc = np.zeros(a.shape[1:], dtype=np.float32)
+    for r in range(a.shape[0]):
+        acc = (acc.astype(np.float64) + a[r] * b[r]).astype(np.float32)
+    return torch.from_numpy(acc)
+
+
+def _f32(t):
+    return t.float().double()
+
+
+def _slot_totals(slots, emulate):
+    """[G, T, 2, C] float32-valued slots -> [G, 2, C] float64 totals; emulate: stats_prereduce's float32 sums of R consecutive
+    slots first, then the finalize kernels' double accumulation"""
+    s = slots.double()
+    r, to = bn_prereduce_plan(s.shape[1])
+    if emulate and r > 1:
+        s = torch.stack([torch.stack([colsum_f32(s[g, o * r:(o + 1) * r].float()) for o in range(to)]) for g in range(s.shape[0])]).double()
+    return s.sum(1)
+
+
+def bn_forward_ref(y, residual, gamma, beta, groups, eps, momentum, relu, running=None, slots=None, group_count=None,
+                   emulate=False, wide=False, seed_error=None):
+    """Training BatchNorm forward on rows y [rows, C] (bf16-exact) in float64 -> dict(out, mean, invstd, scale, shift [G, C],
+    running_mean, running_var [C] after the G updates, relu_mask = out > 0, sums [G, 2, C]).  gamma / beta may be None (1 / 0).
+    slots [G, T, 2, C]: the partial sums (sum y, sum y^2) come from there instead of y (the from_stats and synchronised
+    forms); group_count: the M the sums are divided by (default rows / G: y is the whole group).
+
+    emulate restates the narrow path of bn.hip: per block of bn_block_rows float32 (sum y, fmaf sum y^2) in row order ->
+    double totals -> mean = s / M, var = max(ss / M - mean^2, 0), float32 mean, invstd = 1 / sqrt(var + eps), scale = gamma
+    invstd, shift = beta - mean scale -> out = bf16(relu(y scale + shift (+ residual))) with the float32 coefficients -> the
+    mask from the STORED value -> the running statistics updated in float32 group after group with var M / (M - 1).
+    wide: bn_col_fwd instead -- float32 row-order sum, mean = s / M, two-pass float32 variance sum fmaf(d, d), rsqrtf.
+    seed_error: "biased_running_var", "eps_dropped", "groups_pooled" (one statistic for all groups), "running_from_last_group_only",
+    "residual_after_relu", "var_over_m_minus_1" (the normalisation itself uses the unbiased variance), "mask_ge_zero"."""
+    rows, c = y.shape
+    rpg = rows // groups
+    m_cnt = float(group_count if group_count is not None else rpg)
+    y64 = y.double()
+    ga = gamma.double() if gamma is not None else torch.ones(c, dtype=torch.float64)
+    be = beta.double() if beta is not None else torch.zeros(c, dtype=torch.float64)
+    eps_used = 0.0 if seed_error == "eps_dropped" else float(np.float32(eps))
+    yg = y64.reshape(groups, rpg, c)
+    if seed_error == "groups_pooled" and slots is None:
+        yg = y64.reshape(1, rows, c).expand(groups, rows, c)
+        m_cnt = float(rows) if group_count is None else m_cnt * groups
+    if slots is not None:
+        tot = _slot_totals(slots, emulate)
+        if seed_error == "groups_pooled":
+            tot, m_cnt = tot.sum(0, keepdim=True).expand_as(tot), m_cnt * groups
+        s, ss = tot[:, 0], tot[:, 1]
+    elif emulate and not wide:
+        blocks = bn_block_rows(yg.shape[1], c)
+        s = torch.stack([sum(colsum_f32(g[a:b]).double() for a, b in blocks) for g in yg])
+        ss = torch.stack([sum(colsum_f32(g[a:b] * g[a:b]).double() for a, b in blocks) for g in yg])
+    else:
+        s, ss = yg.sum(1), (yg * yg).sum(1)
+    if emulate and wide:
+        mean = torch.stack([colsum_f32(g) for g in yg]) / torch.tensor(m_cnt, dtype=torch.float32)
+        var = torch.stack([_fma_sq_f32(g.float() - mu) for g, mu in zip(yg, mean)]) / torch.tensor(m_cnt, dtype=torch.float32)
+        unb = var * torch.tensor(m_cnt, dtype=torch.float32) / torch.tensor(m_cnt - 1.0, dtype=torch.float32) if m_cnt > 1 else var
+        if seed_error == "var_over_m_minus_1":
+            var = unb
+        invstd = _f32((var + torch.tensor(eps_used, dtype=torch.float32)).double().rsqrt())
+        mean, var, unb = mean.double(), var.double(), unb.double()
+    else:
+        mean = s / m_cnt
+        if slots is None and not emulate:
+            var = (yg - mean.unsqueeze(1)).pow(2).sum(1) / m_cnt          # (two passes in float64)
+        else:
+            var = (ss / m_cnt - mean * mean).clamp_min(0.0)
+        unb = var * m_cnt / (m_cnt - 1.0) if m_cnt > 1 else var
+        if seed_error == "var_over_m_minus_1":
+            var = unb
+        invstd = (var + eps_used).rsqrt()
+        if emulate:
+            mean, invstd, unb = _f32(mean), _f32(invstd), _f32(unb)
+    if seed_error == "biased_running_var":
+        unb = _f32(var) if emulate else var
+    scale = ga * invstd
+    shift = be - mean * (_f32(scale) if emulate else scale)
+    if emulate:
+        scale, shift = _f32(scale), _f32(shift)
+    grp = torch.arange(rows) // rpg
+    v = y64 * scale[grp] + shift[grp]
+    res = residual.double() if residual is not None else None
+    if res is not None and seed_error != "residual_after_relu":
+        v = v + res
+    if relu:
+        v = v.clamp_min(0.0)
+    if res is not None and seed_error == "residual_after_relu":
+        v = v + res
+    out = bf(v) if emulate else v
+    out = out + 0.0                                                          # (-0 -> +0 plays no role in > 0)
+    mask = out >= 0 if seed_error == "mask_ge_zero" else out > 0
+    result = {"out": out, "mean": mean, "invstd": invstd, "scale": scale, "shift": shift, "relu_mask": mask,
+              "sums": torch.stack([s, ss], 1)}
+    if running is not None:
+        rm, rv = running[0].double().clone(), running[1].double().clone()
+        mom = float(np.float32(momentum))
+        keep = float(np.float32(1.0) - np.float32(momentum)) if emulate else 1.0 - mom       # (the kernel's 1.f - momentum)
+        for g in range(groups):
+            if seed_error == "running_from_last_group_only" and g < groups - 1:
+                continue
+            rm, rv = keep * rm + mom * mean[g], keep * rv + mom * unb[g]
+            if emulate:
+                rm, rv = _f32(rm), _f32(rv)
+        result.update(running_mean=rm, running_var=rv)
+    return result
+
+
+def _fma_sq_f32(d):
+    """sum over rows of d^2 by q = fmaf(d, d, q) in float32 (d float32: the product is exact in float64)"""
+    return fma_colsum_f32(d, d)
+
+
+def bn_pack_mask(mask):
+    """[rows, C] bool -> [rows, C / 8] uint8, bit e of byte (row, chunk) = channel 8 chunk + e (bn_apply's relu_mask)"""
+    rows, c = mask.shape
+    w = (2 ** torch.arange(8)).to(torch.int64)
+    return (mask.reshape(rows, c // 8, 8).to(torch.int64) * w).sum(-1).to(torch.uint8)
+
+
+def bn_eval_ref(y, residual, gamma, beta, running_mean, running_var, eps, relu, emulate=False):
+    """Eval-mode BatchNorm in float64 -> dict(out, scale, shift); emulate: float32 invstd = 1 / sqrt(var + eps), scale and
+    shift as bn_eval_params, one bf16 rounding of the output"""
+    c = y.shape[1]
+    ga = gamma.double() if gamma is not None else torch.ones(c, dtype=torch.float64)
+    be = beta.double() if beta is not None else torch.zeros(c, dtype=torch.float64)
+    e = float(np.float32(eps))
+    if emulate:
+        invstd = _f32((running_var.float() + torch.tensor(e, dtype=torch.float32)).double().rsqrt())
+        scale = _f32(ga * invstd)
+        shift = _f32(be - _f32(running_mean.double() * scale))
+    else:
+        scale = ga * (running_var.double() + e).rsqrt()
+        shift = be - running_mean.double() * scale
+    v = y.double() * scale + shift
+    if residual is not None:
+        v = v + residual.double()
+    if relu:
+        v = v.clamp_min(0.0)
+    return {"out": bf(v) if emulate else v, "scale": scale, "shift": shift}
+
+
+def bn_backward_ref(y, dout, gamma, beta, mean, invstd, groups, out_relu=None, remask=False, group_count=None, want_dz=True,
+                    fx_slots=None, totals=None, accumulate_into=None, emulate=False, wide=False, seed_error=None):
+    """Training BatchNorm backward on rows [rows, C] in float64 -> dict(dy, dz, dgamma, dbeta, sums [G, 2, C], and pre: the
+    values the exact tier needs to be float32-exact).
+        dz = dout * mask;  s1 = sum dz, s2 = sum dz xhat per group, xhat = (y - mean) invstd
+        dy = gamma invstd (dz - s1 / M - xhat s2 / M);  dgamma = sum over groups of s2, dbeta = ... of s1 (+ accumulate_into)
+    mask: out_relu > 0, or (remask) the forward's own y scale + shift > 0, or none.  mean / invstd [G, C] are inputs (float32
+    values).  fx_slots [G, T, 2, C]: the sums come from slots holding (sum g, sum g (y - mean)), dout is g (no mask).  totals
+    [G, 2, C]: the all-reduced sums of the synchronised form, divided by group_count; dgamma / dbeta stay local.
+
+    emulate: narrow path -- float32 block sums (bn_block_rows; s2 by fmaf with the float32 xhat) -> double totals, float32
+    coefficients s1 / M, s2 / M, gamma invstd; the mask recomputed as bf16(fmaf(y, scale, shift)) > 0; dy one bf16 rounding.
+    wide: bn_col_bwd -- float32 row-order sums, float32 c1 = s1 / M, c2 = s2 / M, dgamma summed over groups in float32.
+    seed_error: "dz_unmasked", "xhat_uncentred", "s2_term_dropped", "mean_over_local_rows", "fx_unscaled", "accumulate_ignored",
+    "mask_ge_zero"."""
+    rows, c = y.shape
+    rpg = rows // groups
+    m_cnt = float(rpg if group_count is None or seed_error == "mean_over_local_rows" else group_count)
+    grp = torch.arange(rows) // rpg
+    y64, d = y.double(), dout.double()
+    ga = gamma.double() if gamma is not None else torch.ones(c, dtype=torch.float64)
+    be = beta.double() if beta is not None else torch.zeros(c, dtype=torch.float64)
+    mu, inv = mean.double(), invstd.double()
+    sc = _f32(ga * inv) if emulate else ga * inv
+    sh = _f32(be - _f32(mu * sc)) if emulate else be - mu * sc
+    ge = seed_error == "mask_ge_zero"
+    if seed_error == "dz_unmasked" or (out_relu is None and not remask):
+        dz = d
+    elif out_relu is not None:
+        dz = d * ((out_relu.double() >= 0) if ge else (out_relu.double() > 0))
+    else:
+        pre = y64 * sc[grp] + sh[grp]
+        pre = bf(pre.float().double()) if emulate else pre
+        dz = d * ((pre >= 0) if ge else (pre > 0))
+    cen = y64 if seed_error == "xhat_uncentred" else y64 - mu[grp]
+    xh = cen * inv[grp]
+    if emulate:
+        xh = _f32(_f32(cen) * inv[grp])
+    if fx_slots is not None:
+        tot = _slot_totals(fx_slots, emulate)
+        s1 = tot[:, 0]
+        s2 = tot[:, 1] if seed_error == "fx_unscaled" else inv * tot[:, 1]
+    elif emulate:
+        dzg, xg = dz.reshape(groups, rpg, c), xh.reshape(groups, rpg, c)
+        if wide:
+            s1 = torch.stack([colsum_f32(g) for g in dzg]).double()
+            s2 = torch.stack([fma_colsum_f32(g, x) for g, x in zip(dzg, xg)]).double()
+        else:
+            blocks = bn_block_rows(rpg, c)
+            s1 = torch.stack([sum(colsum_f32(g[a:b]).double() for a, b in blocks) for g in dzg])
+            s2 = torch.stack([sum(fma_colsum_f32(g[a:b], x[a:b]).double() for a, b in blocks) for g, x in zip(dzg, xg)])
+    else:
+        s1, s2 = dz.reshape(groups, rpg, c).sum(1), (dz * xh).reshape(groups, rpg, c).sum(1)
+    sums = torch.stack([s1, s2], 1)
+    if emulate and wide:
+        dgamma, dbeta = colsum_f32(s2), colsum_f32(s1)
+    else:
+        dgamma, dbeta = s2.sum(0), s1.sum(0)
+    if emulate:
+        dgamma, dbeta, sums = _f32(dgamma), _f32(dbeta), _f32(sums)
+    if accumulate_into is not None and seed_error != "accumulate_ignored":
+        dgamma, dbeta = accumulate_into[0].double() + dgamma, accumulate_into[1].double() + dbeta
+        if emulate:
+            dgamma, dbeta = _f32(dgamma), _f32(dbeta)
+    t1, t2 = (totals[:, 0].double(), totals[:, 1].double()) if totals is not None else (s1, s2)
+    c1, c2 = t1 / m_cnt, t2 / m_cnt
+    if emulate:
+        c1, c2 = _f32(c1), _f32(c2)
+    prod = xh * c2[grp]
+    pre_dy = sc[grp] * (dz - c1[grp] - (0.0 if seed_error == "s2_term_dropped" else prod))
+    return {"dy": bf(pre_dy) if emulate else pre_dy, "dz": dz if want_dz else None, "dgamma": dgamma, "dbeta": dbeta,
+            "sums": sums, "pre": {"c1": c1, "c2": c2, "xhat c2": prod, "dy before rounding": pre_dy, "s1": s1, "s2": s2}}
+
+
+def bn_lattice_exact(pre):
+    """Precondition of the exact backward tier: every intermediate of the float64 result is a float32 value (24 bits), so a
+    float32 kernel in any summation order, contracted or not, holds the same numbers"""
+    for key, t in pre.items():
+        assert torch.equal(t, t.float().double()), f"{key}: needs more than 24 bits"
+        assert float(t.abs().max()) < 2.0 ** 24, key
+
+
+BN_FORWARD_FAMILIES = ("lattice", "randn", "offset", "constant", "big_value")
+
+
+def bn_forward_inputs(family, rows, c, groups, seed, offset=50.0):
+    """dict(y, residual [rows, C] bf16-exact, gamma, beta [C], running_mean, running_var [C]) for the BatchNorm forward.
+    lattice: every (group, channel) holds mean +- s on a shuffled half of its rows each (rows / G even), mean an integer
+    that differs per group, s in {0.5, 1, 2}; gamma a power of two, beta and residual integers, the running statistics
+    small dyadic numbers: with eps = 0 mean, invstd = 1 / s, scale, shift and out are exact in float32 in any order.
+    randn: 2 randn + 0.5.  offset: channel mean `offset` with spread 1, the groups' means one apart.  constant: every third
+    channel constant within a group (variance exactly 0: invstd = eps^-1/2, eps decides), the others randn.  big_value: randn
+    with one element (first row of the middle group) times 1e4."""
+    g = torch.Generator().manual_seed(seed)
+    rpg = rows // groups
+    grp = torch.arange(rows) // rpg
+    if family == "lattice":
+        assert rpg % 2 == 0, "the lattice needs an even number of rows per group"
+        mean = torch.randint(-3, 4, (1, c), generator=g).float() + torch.arange(groups).float().view(groups, 1)
+        s = 2.0 ** torch.randint(-1, 2, (groups, c), generator=g).float()
+        sign = torch.stack([torch.stack([(torch.randperm(rpg, generator=g) % 2).float() * 2 - 1 for _ in range(min(c, 16))], 1)
+                            for _ in range(groups)])                         # [G, rpg, 16]: 16 shuffles, cycled over the channels
+        sign = sign.repeat(1, 1, -(-c // 16))[:, :, :c]
+        y = (mean.view(groups, 1, c) + sign * s.view(groups, 1, c)).reshape(rows, c)
+        return {"y": y, "residual": torch.randint(-2, 3, (rows, c), generator=g).float(),
+                "gamma": 2.0 ** torch.randint(-1, 2, (c,), generator=g).float() * (torch.randint(0, 2, (c,), generator=g).float() * 2 - 1),
+                "beta": torch.randint(-2, 3, (c,), generator=g).float(),
+                "running_mean": torch.randint(-2, 3, (c,), generator=g).float() * 0.5,
+                "running_var": torch.randint(1, 4, (c,), generator=g).float() * 0.5, "mean": mean, "s": s}
+    n = torch.randn(rows, c, generator=g)
+    if family == "randn":
+        y = n * 2 + 0.5
+    elif family == "offset":
+        y = offset + grp.float().view(rows, 1) + n
+    elif family == "constant":
+        y = n * 2 + 0.5
+        const = torch.randint(-3, 4, (groups, c), generator=g).float() * 0.75
+        y[:, ::3] = const[grp][:, ::3]
+    elif family == "big_value":
+        # in the FIRST row of the middle group: a sequential float32 sum carries its rounding through every later addition.  (At
+        # the end of a reduce block the row-order yardstick would commit none of it and ask the same of every other order.)
+        y = n * 2 + 0.5
+        y[(rows // 2) // rpg * rpg, c // 2] *= 1e4
+    else:
+        raise ValueError(family)
+    return {"y": bf(y), "residual": bf(torch.randn(rows, c, generator=g)), "gamma": torch.rand(c, generator=g) + 0.5,
+            "beta": torch.randn(c, generator=g) * 0.3, "running_mean": torch.randn(c, generator=g) * 0.1,
+            "running_var": torch.rand(c, generator=g) + 0.5}
+
+
+def bn_backward_inputs(family, rows, c, groups, seed):
+    """bn_inputs plus the gradient dout [rows, C] (lattice: integers in -2 .. 2; else bf16 randn) and non-zero dgamma / dbeta
+    to accumulate onto (lattice: integers)"""
+    b = bn_inputs(family, rows, c, groups, seed)
+    g = torch.Generator().manual_seed(seed + 7919)
+    if family == "lattice":
+        b["dout"] = torch.randint(-2, 3, (rows, c), generator=g).float()
+        b["acc"] = (torch.randint(-4, 5, (c,), generator=g).float(), torch.randint(-4, 5, (c,), generator=g).float())
+    else:
+        b["dout"] = bf(torch.randn(rows, c, generator=g))
+        b["acc"] = (torch.randn(c, generator=g), torch.randn(c, generator=g))
+    return b
+
+
+def bn_row_slots(vals_a, vals_b, groups, t, seed):
+    """Slots [G, T, 2, C] as a convolution epilogue leaves them: the float64 sums of (vals_a, vals_b) [rows, C] over a random
+    partition of every group's rows into T runs, some of them empty (zeros), rounded to float32"""
+    rows, c = vals_a.shape
+    rpg = rows // groups
+    g = torch.Generator().manual_seed(seed)
+    out = torch.zeros(groups, t, 2, c, dtype=torch.float64)
+    for gi in range(groups):
+        cuts = torch.sort(torch.randint(0, rpg + 1, (t - 1,), generator=g)).values.tolist() if t > 1 else []
+        edges = [0] + cuts + [rpg]
+        for k in range(t):
+            a, b = gi * rpg + edges[k], gi * rpg + edges[k + 1]
+            out[gi, k, 0], out[gi, k, 1] = vals_a[a:b].double().sum(0), vals_b[a:b].double().sum(0)
+    return out.float()
+
+
+# ------------------------------------------------------------------------------------------------ pooling (csrc/pool.hip)
+def pooled_side(s):
+    return (s - 1) // 2 + 1
+
+
+def scan_reference(t, y):
+    """t, y [N][H][W][C] float (CPU): per window the maximum of t over its positions inside the image, the code kh * 3 + kw
+    of the FIRST position in scan order that attains it, and y at that position."""
+    n, h, w, c = t.shape
+    p, q = pooled_side(h), pooled_side(w)
+    tp = torch.full((n, h + 2, w + 2, c), float("-inf"))
+    tp[:, 1:h + 1, 1:w + 1] = t
+    yp = torch.zeros((n, h + 2, w + 2, c))
+    yp[:, 1:h + 1, 1:w + 1] = y
+    best = torch.full((n, p, q, c), float("-inf"))
+    code = torch.zeros((n, p, q, c), dtype=torch.uint8)
+    sel = torch.zeros((n, p, q, c))
+    for kh in range(3):
+        for kw in range(3):
+            cand = tp[:, kh:kh + 2 * p - 1:2, kw:kw + 2 * q - 1:2]
+            m = cand > best            # strict: the first maximum stays
+            best = torch.where(m, cand, best)
+            code = torch.where(m, torch.tensor(kh * 3 + kw, dtype=torch.uint8), code)
+            sel = torch.where(m, yp[:, kh:kh + 2 * p - 1:2, kw:kw + 2 * q - 1:2], sel)
+    return best, code, sel
+
+
+def maxpool_ref(x, seed_error=None):
+    """max_pool 3x3 / stride 2 / pad 1 of x [N, H, W, C] -> (y, idx): scan_reference.  seed_error "zero_pad": the padding
+    counts as 0 (a window on the border never goes below 0); "last_max": the LAST of equal maxima is recorded."""
+    if seed_error == "last_max":
+        best, code, _ = scan_reference(x.flip(1, 2), x.flip(1, 2))
+        h, w = x.shape[1:3]
+        assert h % 2 == 1 and w % 2 == 1, "the flipped scan is the same set of windows only for odd H and W"
+        return best.flip(1, 2), (8 - code.flip(1, 2).long()).to(torch.uint8)
+    best, code, _ = scan_reference(x, x)
+    if seed_error == "zero_pad":
+        n, h, w, c = x.shape
+        edge = torch.zeros(best.shape[1], best.shape[2], dtype=torch.bool)
+        edge[0, :], edge[:, 0] = True, True
+        if h % 2 == 0:
+            pass                                                      # (the last window row ends inside the image)
+        else:
+            edge[-1, :] = True
+        if w % 2 == 1:
+            edge[:, -1] = True
+        best = torch.where(edge.view(1, *edge.shape, 1), best.clamp_min(0.0), best)
+    return best, code
+
+
+def maxpool_bwd_ref(dy, idx, h, w):
+    """The gradient of the pooling in float64: every window's dy [N, P, Q, C] goes to the position its code names"""
+    n, p, q, c = dy.shape
+    dx = torch.zeros(n, h + 2, w + 2, c, dtype=torch.float64)
+    for kh in range(3):
+        for kw in range(3):
+            dx[:, kh:kh + 2 * p - 1:2, kw:kw + 2 * q - 1:2] += dy.double() * (idx == kh * 3 + kw)
+    return dx[:, 1:h + 1, 1:w + 1]
+
+
+def gap_ref(x, emulate=False):
+    """mean over HW of x [N, HW, C] in float64; emulate: gap_fwd's float32 row-order sum times float32(1 / HW), one bf16
+    rounding"""
+    n, hw, c = x.shape
+    if not emulate:
+        return x.double().mean(1)
+    inv = np.float32(1.0) / np.float32(hw)
+    s = torch.stack([colsum_f32(img) for img in x])
+    return bf((s * torch.tensor(inv)).double())

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from kernel_check import pooled_side, scan_reference
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "stem_pool"
 
@@ -36,10 +37,6 @@ def lib():
 
         import_module("ssl_wafermap_amd.build").build(verbose=False)
     return _lib.load()
-
-
-def pooled_side(s):
-    return (s - 1) // 2 + 1
 
 
 def fwd_blocks(n, c, h, w):
@@ -103,28 +100,6 @@ def fused_forward(lib, y, scale, shift, g, want_xsel=True):
                                                idx.data_ptr(), _lib.ptr(xsel), _lib.stream_ptr()), "wm_bn_relu_maxpool3x3s2_fwd")
     torch.cuda.synchronize()
     return out, idx, xsel
-
-
-def scan_reference(t, y):
-    """t, y [N][H][W][C] float (CPU): per window the maximum of t over its positions inside the image, the code kh * 3 + kw
-    of the FIRST position in scan order that attains it, and y at that position."""
-    n, h, w, c = t.shape
-    p, q = pooled_side(h), pooled_side(w)
-    tp = torch.full((n, h + 2, w + 2, c), float("-inf"))
-    tp[:, 1:h + 1, 1:w + 1] = t
-    yp = torch.zeros((n, h + 2, w + 2, c))
-    yp[:, 1:h + 1, 1:w + 1] = y
-    best = torch.full((n, p, q, c), float("-inf"))
-    code = torch.zeros((n, p, q, c), dtype=torch.uint8)
-    sel = torch.zeros((n, p, q, c))
-    for kh in range(3):
-        for kw in range(3):
-            cand = tp[:, kh:kh + 2 * p - 1:2, kw:kw + 2 * q - 1:2]
-            m = cand > best            # strict: the first maximum stays
-            best = torch.where(m, cand, best)
-            code = torch.where(m, torch.tensor(kh * 3 + kw, dtype=torch.uint8), code)
-            sel = torch.where(m, yp[:, kh:kh + 2 * p - 1:2, kw:kw + 2 * q - 1:2], sel)
-    return best, code, sel
 
 
 @pytest.fixture(scope="module")

@@ -395,3 +395,287 @@ def test_bn_dgrad_epilogue_honest_passes_and_errors_fail(family, form):
         assert any(m > bb for _, m, bb in rows), f"seeded error accepted -- {error} {family} {form}: {rows}"
         if error == "mask_off_by_channel":
             _reject(bad["dx"], ref["dx"], emul["dx"], f"{error} dx {family}")
+
+
+# ---------------------------------------------------------------------------------------------------- BatchNorm
+# The smallest narrow shapes tests/test_gpu_bn.py runs, one of several blocks, and the smallest wide ones: (rows / G, C, wide)
+BN_SHAPES = [(3, 8, False), (2, 64, False), (530, 40, False), (2, 2056, True), (5, 2056, True)]
+BN_EPS, BN_MOM = 1e-5, 0.1
+# rows / G of every GPU case (narrow, grid caps, wide, the two-rank totals of the synchronised tests)
+BN_ROW_COUNTS = [2, 3, 4, 5, 10, 33, 37, 38, 40, 74, 523, 524, 530, 1366, 1367, 8200, 16500]
+
+
+def _bn_fwd(b, g, wide=False, emulate=False, seed_error=None, relu=1, res=True, eps=BN_EPS):
+    return kc.bn_forward_ref(b["y"], b["residual"] if res else None, b["gamma"], b["beta"], g, eps, BN_MOM, relu,
+                             (b["running_mean"], b["running_var"]), emulate=emulate, wide=wide and emulate, seed_error=seed_error)
+
+
+def _stat_verdict(got, ref, emul, floor):
+    return kc.verdict(got, ref, emul, kc.F32_SUM_FACTOR, floor, floor_all=True)
+
+
+def _bn_floors(b, g):
+    y, m = b["y"].double(), b["y"].shape[0] // g
+    return {"mean": kc.f32_sum_floor(y) / m, "running_mean": kc.f32_sum_floor(y) / m + kc.f32_stat_floor(b["running_mean"]),
+            "running_var": kc.f32_sum_floor(y * y) / max(m - 1, 1) + kc.f32_stat_floor(b["running_var"])}
+
+
+def _stat_rejected(bad, ref, emul, floor, what):
+    rows, finite = _stat_verdict(bad, ref, emul, floor)
+    line = ", ".join(f"{c}: {m:.3g} vs {b:.3g}" for c, m, b in rows)
+    print(f"{what}: {line}")
+    assert not finite or any(m > b for _, m, b in rows), f"seeded error accepted -- {what}: {line}"
+
+
+def test_bn_references_agree_with_torch_in_float64():
+    """bn_forward_ref / bn_backward_ref against torch's own batch_norm and autograd per statistics group, in float64"""
+    import torch.nn.functional as F
+
+    rows, c, g = 24, 16, 3
+    b = kc.bn_forward_inputs("randn", rows, c, g, seed=1)
+    ref = _bn_fwd(b, g)
+    y = b["y"].double().requires_grad_(True)
+    ga, be = b["gamma"].double().requires_grad_(True), b["beta"].double().requires_grad_(True)
+    rm, rv = b["running_mean"].double().clone(), b["running_var"].double().clone()
+    pre = torch.cat([F.batch_norm(part, rm, rv, ga, be, True, float(torch.tensor(BN_MOM).float()), float(torch.tensor(BN_EPS).float()))
+                     for part in y.chunk(g)])
+    out = F.relu(pre + b["residual"].double())
+    torch.testing.assert_close(out, ref["out"], rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(rm, ref["running_mean"], rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(rv, ref["running_var"], rtol=1e-12, atol=1e-12)
+    dout = torch.randn(rows, c, generator=torch.Generator().manual_seed(2)).double()
+    out.backward(dout)
+    back = kc.bn_backward_ref(b["y"], dout, b["gamma"], b["beta"], ref["mean"], ref["invstd"], g, out_relu=ref["out"])
+    torch.testing.assert_close(back["dy"], y.grad, rtol=1e-10, atol=1e-11)
+    torch.testing.assert_close(back["dgamma"], ga.grad, rtol=1e-10, atol=1e-11)
+    torch.testing.assert_close(back["dbeta"], be.grad, rtol=1e-10, atol=1e-11)
+    remask = kc.bn_backward_ref(b["y"], dout, b["gamma"], b["beta"], ref["mean"], ref["invstd"], g, remask=True)
+    nores = _bn_fwd(b, g, res=False)
+    assert torch.equal(remask["dz"], dout * (nores["out"] > 0))
+
+
+@pytest.mark.parametrize("family", kc.BN_FORWARD_FAMILIES[1:])
+@pytest.mark.parametrize("g", [1, 2, 3])
+@pytest.mark.parametrize("rpg,c,wide", BN_SHAPES)
+def test_bn_forward_honest_result_passes(rpg, c, wide, g, family):
+    b = kc.bn_forward_inputs(family, rpg * g, c, g, seed=rpg + c)
+    ref, emul = _bn_fwd(b, g), _bn_fwd(b, g, wide, emulate=True)
+    with kc.jitter(6):
+        got = _bn_fwd(b, g, wide, emulate=True)
+    _accept(got["out"], ref["out"], emul["out"], f"out {family}")
+    floors = _bn_floors(b, g)
+    for name in ("mean", "invstd", "running_mean", "running_var"):
+        rows, finite = _stat_verdict(emul[name] * (1 + 2.0 ** -24), ref[name], emul[name], floors.get(name, kc.f32_stat_floor(ref[name])))
+        assert finite and all(m <= bd for _, m, bd in rows), (name, rows)
+
+
+def test_bn_forward_lattice_is_exact_in_float32():
+    """The emulation (float32 block sums in row order) and float64 agree bit for bit on the lattice: out, mean, invstd,
+    running_mean always, running_var where rows / G - 1 is a power of two"""
+    for rpg, c in [(2, 64), (4, 8), (530, 40), (38, 1032)]:
+        for g in (1, 2, 3):
+            b = kc.bn_forward_inputs("lattice", rpg * g, c, g, seed=rpg)
+            assert g == 1 or not torch.equal(b["mean"][0], b["mean"][1])
+            ref, emul = _bn_fwd(b, g, eps=0.0), _bn_fwd(b, g, emulate=True, eps=0.0)
+            ref = dict(ref, **{k: v for k, v in kc.bn_forward_ref(b["y"], b["residual"], b["gamma"], b["beta"], g, 0.0, 0.125, 1,
+                                                                  (b["running_mean"], b["running_var"])).items() if "running" in k})
+            emul = dict(emul, **{k: v for k, v in kc.bn_forward_ref(b["y"], b["residual"], b["gamma"], b["beta"], g, 0.0, 0.125, 1,
+                                                                    (b["running_mean"], b["running_var"]), emulate=True).items() if "running" in k})
+            for name in ("out", "mean", "invstd", "scale", "shift", "running_mean") + (("running_var",) if rpg == 2 else ()):
+                assert torch.equal(ref[name], emul[name]), (name, rpg, c, g)
+            assert torch.equal(ref["relu_mask"], emul["relu_mask"]) and bool((ref["out"] == 0).any())
+            bad = _bn_fwd(b, g, emulate=True, eps=0.0, seed_error="mask_ge_zero")
+            assert not torch.equal(bad["relu_mask"], ref["relu_mask"])            # mask_ge_zero on the lattice: plain inequality
+
+
+# (error, tensor that shows it, families that can see it, needs G >= 2).  Left out, with the reason:
+#   eps_dropped on randn / offset / big_value -- eps is 2.5e-6 of the variance (or less), below the float32 noise of invstd;
+#     "constant" decides it (variance exactly 0: invstd = eps^-1/2 against inf)
+#   groups_pooled, running_from_last_group_only at G = 1 -- one group: nothing to pool or to leave out
+BN_FWD_ERRORS = [
+    # (offset is left out here: at 530 rows in one reduce block the float32 sum of y^2 is past 2^24 grid steps and the variance
+    # of the narrow path carries 5e-4 .. 2e-3 of noise, the size of 1 / (M - 1); randn at every row count is the test below)
+    ("biased_running_var", "running_var", ("randn", "constant", "big_value"), False),
+    ("eps_dropped", "invstd", ("constant",), False),
+    ("groups_pooled", "mean", ("randn", "offset", "constant", "big_value"), True),
+    ("running_from_last_group_only", "running_mean", ("randn", "offset", "constant", "big_value"), True),
+    ("residual_after_relu", "out", ("randn", "offset", "constant", "big_value"), False),
+    ("var_over_m_minus_1", "invstd", ("randn", "constant", "big_value"), False),   # (offset: see the cancellation test -- its
+    # float32 noise on invstd at |mean| / std = 50 is of the size of 1 / (2 M) from a few hundred rows on)
+]
+
+
+@pytest.mark.parametrize("error,tensor,families,multi", BN_FWD_ERRORS)
+@pytest.mark.parametrize("rpg,c,wide", BN_SHAPES)
+def test_bn_forward_seeded_errors_fail(rpg, c, wide, error, tensor, families, multi):
+    for family in families:
+        for g in ((2, 3) if multi else (1, 2, 3)):
+            b = kc.bn_forward_inputs(family, rpg * g, c, g, seed=rpg + c)
+            ref, emul = _bn_fwd(b, g), _bn_fwd(b, g, wide, emulate=True)
+            bad = _bn_fwd(b, g, wide, emulate=True, seed_error=error)
+            what = f"{error} {family} {rpg}x{c} G={g}"
+            if tensor == "out":
+                _reject(bad[tensor], ref[tensor], emul[tensor], what)
+            else:
+                _stat_rejected(bad[tensor], ref[tensor], emul[tensor], _bn_floors(b, g).get(tensor, kc.f32_stat_floor(ref[tensor])), what)
+
+
+@pytest.mark.parametrize("rpg", BN_ROW_COUNTS)
+def test_bn_biased_running_variance_fails_at_every_row_count(rpg):
+    """1 / (M - 1) relative: 6e-5 at the largest count, three orders above the float32 yardstick"""
+    for wide, c in ((False, 8), (True, 2056)):
+        if wide and rpg > 40:
+            continue
+        b = kc.bn_forward_inputs("randn", rpg, c, 1, seed=rpg)
+        ref, emul = _bn_fwd(b, 1), _bn_fwd(b, 1, wide, emulate=True)
+        bad = _bn_fwd(b, 1, wide, emulate=True, seed_error="biased_running_var")
+        _stat_rejected(bad["running_var"], ref["running_var"], emul["running_var"], _bn_floors(b, 1)["running_var"], f"biased M={rpg}")
+
+
+def test_bn_dropped_eps_fails_on_constant_channels():
+    for rpg, c, wide in BN_SHAPES:
+        b = kc.bn_forward_inputs("constant", rpg * 2, c, 2, seed=c)
+        ref, emul = _bn_fwd(b, 2), _bn_fwd(b, 2, wide, emulate=True)
+        eps32 = torch.tensor(BN_EPS).float().double()
+        assert bool((ref["invstd"][:, ::3] == eps32.rsqrt()).all())                                # variance exactly 0: eps decides
+        assert torch.equal(emul["invstd"][:, ::3], ref["invstd"][:, ::3].float().double())
+        bad = _bn_fwd(b, 2, wide, emulate=True, seed_error="eps_dropped")
+        assert not bool(torch.isfinite(bad["invstd"]).all())
+        _stat_rejected(bad["invstd"], ref["invstd"], emul["invstd"], kc.f32_stat_floor(ref["invstd"]), f"eps_dropped {rpg}x{c}")
+
+
+def _bn_bwd(b, g, emulate=False, wide=False, seed_error=None, form="out", **kw):
+    return kc.bn_backward_ref(b["bn_y"], b["dout"], b["gamma"], b["beta"], b["mean"], b["invstd"], g,
+                              out_relu=b["relu_x"] if form == "out" else None, remask=form == "y", emulate=emulate,
+                              wide=wide and emulate, seed_error=seed_error, **kw)
+
+
+# (error, tensor, families, form).  mask_ge_zero is a lattice matter: randn / offset draw relu_x from randn (no exact zero), and
+# their recomputed pre-activations keep a margin from zero by construction, so > and >= select the same elements there.
+BN_BWD_ERRORS = [
+    ("dz_unmasked", "dz", ("lattice", "randn", "offset"), "out"),
+    ("dz_unmasked", "dy", ("lattice", "randn"), "y"),
+    ("xhat_uncentred", "dy", ("lattice", "randn", "offset"), "out"),
+    ("xhat_uncentred", "dgamma", ("lattice", "randn", "offset"), None),
+    ("s2_term_dropped", "dy", ("lattice", "randn", "offset"), None),
+    ("mask_ge_zero", "dz", ("lattice",), "out"),
+    ("mask_ge_zero", "dz", ("lattice",), "y"),
+]
+
+
+@pytest.mark.parametrize("error,tensor,families,form", BN_BWD_ERRORS)
+@pytest.mark.parametrize("rpg,c,wide", [(4, 8, False), (2, 64, False), (512, 40, False), (2, 2056, True), (4, 2056, True)])
+def test_bn_backward_seeded_errors_fail(rpg, c, wide, error, tensor, families, form):
+    for family in families:
+        for g in (1, 2, 3):
+            b = kc.bn_backward_inputs(family, rpg * g, c, g, seed=rpg + c)
+            ref, bad = _bn_bwd(b, g, form=form), _bn_bwd(b, g, True, wide, error, form)
+            what = f"{error} {family} {rpg}x{c} G={g} {tensor}"
+            if family == "lattice":
+                kc.bn_lattice_exact(ref["pre"])
+                want = kc.bf(ref[tensor]) if tensor == "dy" else ref[tensor]
+                assert not torch.equal(bad[tensor], want), what
+                assert torch.equal(_bn_bwd(b, g, True, wide, None, form)[tensor], want), what   # (and the honest emulation is exact)
+                continue
+            emul = _bn_bwd(b, g, True, wide, None, form)
+            if tensor == "dgamma":
+                dz, xh = ref["dz"], (b["bn_y"].double() - b["mean"].double()[torch.arange(rpg * g) // rpg]) * b["invstd"].double()[torch.arange(rpg * g) // rpg]
+                _stat_rejected(bad[tensor], ref[tensor], emul[tensor], kc.f32_sum_floor(dz * xh), what)
+            else:
+                _reject(bad[tensor], ref[tensor], emul[tensor], what)
+                with kc.jitter(7):
+                    _accept(_bn_bwd(b, g, True, wide, None, form)[tensor], ref[tensor], emul[tensor], what + " honest")
+
+
+@pytest.mark.parametrize("family", ["lattice", "randn", "offset"])
+def test_bn_backward_form_errors_fail(family):
+    """mean_over_local_rows (the synchronised form divides by the local rows), fx_unscaled (slots holding sum g (y - mean) not
+    multiplied by invstd), accumulate_ignored"""
+    rl, c, g = 32, 40, 2
+    b = kc.bn_backward_inputs(family, 2 * rl * g, c, g, seed=9)
+    whole = _bn_bwd(b, g, form=None)
+    half = {k: (v.reshape(g, 2, rl, c)[:, 0].reshape(g * rl, c) if k in ("bn_y", "dout", "relu_x") else v) for k, v in b.items()}
+    lat = family == "lattice"
+
+    def differs(bad, ref, emul, what):
+        if lat:
+            assert not torch.equal(bad, ref) and torch.equal(emul, ref), what
+        else:
+            _reject(bad, ref, emul, what)
+
+    ref = _bn_bwd(half, g, form=None, group_count=2 * rl, totals=whole["sums"])
+    emul = _bn_bwd(half, g, True, form=None, group_count=2 * rl, totals=whole["sums"].float())
+    bad = _bn_bwd(half, g, True, form=None, group_count=2 * rl, totals=whole["sums"].float(), seed_error="mean_over_local_rows")
+    assert torch.equal(ref["dy"], whole["dy"].reshape(g, 2, rl, c)[:, 0].reshape(g * rl, c))     # a rank's rows of the whole batch
+    differs(bad["dy"], kc.bf(ref["dy"]) if lat else ref["dy"], emul["dy"], f"mean_over_local_rows {family}")
+    grp = torch.arange(2 * rl * g) // (2 * rl)
+    gr = b["dout"].double()
+    slots = kc.bn_row_slots(gr, gr * (b["bn_y"].double() - b["mean"].double()[grp]), g, 5, seed=3)
+    ref, emul = _bn_bwd(b, g, form=None, fx_slots=slots), _bn_bwd(b, g, True, form=None, fx_slots=slots)
+    bad = _bn_bwd(b, g, True, form=None, fx_slots=slots, seed_error="fx_unscaled")
+    if not lat:
+        assert float((ref["dgamma"] - whole["dgamma"]).abs().max()) <= 1e-5 * float(whole["dgamma"].abs().max())  # slots = the sums
+    differs(bad["dy"], kc.bf(ref["dy"]) if lat else ref["dy"], emul["dy"], f"fx_unscaled dy {family}")
+    assert not torch.equal(bad["dgamma"], ref["dgamma"])
+    if not lat:
+        _stat_rejected(bad["dgamma"], ref["dgamma"], emul["dgamma"], kc.f32_sum_floor(gr * 4.0), f"fx_unscaled dgamma {family}")
+    ref = _bn_bwd(b, g, form=None, accumulate_into=b["acc"])
+    emul = _bn_bwd(b, g, True, form=None, accumulate_into=b["acc"])
+    bad = _bn_bwd(b, g, True, form=None, accumulate_into=b["acc"], seed_error="accumulate_ignored")
+    for name in ("dgamma", "dbeta"):
+        if lat:
+            assert not torch.equal(bad[name], ref[name]) and torch.equal(emul[name], ref[name])
+        else:
+            _stat_rejected(bad[name], ref[name], emul[name], kc.f32_sum_floor(gr * 4.0), f"accumulate_ignored {name} {family}")
+
+
+def test_bn_narrow_path_cancellation_is_measured():
+    """The documented narrow-path arithmetic (float32 block sums of y and y^2, var = ss / M - mean^2 in double) against float64
+    on save_invstd for the offset family, with bn_col_fwd's two-pass float32 form beside it.  A measurement of the FORMULA
+    (profiles/bn_kernel_check.md holds the numbers).  Asserted: both stay inside what Higham's bound of a float32 sum of n
+    terms allows them -- gamma_n (mean^2 / var + 1) on the one-pass variance (n = the rows of a reduce block), gamma_n on the
+    two-pass one (n = the rows of the group) -- and invstd moves by half of the variance's relative error."""
+    u = 2.0 ** -24
+    for rows, c in ((1568, 64), (530, 40)):
+        n_block = max(b - a for a, b in kc.bn_block_rows(rows, c))
+        for ratio in (50.0, 300.0):
+            b = kc.bn_forward_inputs("offset", rows, c, 1, seed=int(ratio), offset=ratio)
+            ref = _bn_fwd(b, 1)["invstd"]
+            narrow = _bn_fwd(b, 1, emulate=True)["invstd"]
+            two_pass = _bn_fwd(b, 1, wide=True, emulate=True)["invstd"]
+            en, ew = ((narrow - ref).abs() / ref), ((two_pass - ref).abs() / ref)
+            print(f"{rows} x {c}, |mean| / std = {ratio:g}: one-pass max {float(en.max()):.3g} rms {float(en.pow(2).mean().sqrt()):.3g}; "
+                  f"two-pass max {float(ew.max()):.3g} rms {float(ew.pow(2).mean().sqrt()):.3g}; bf16 ulp {kc.BF16_ULP:.3g}")
+            var_min = float(ref.pow(-2).min())
+            assert float(ew.max()) < 0.5 * rows * u * 1.1 + u
+            assert float(en.max()) < 0.5 * n_block * u * (ratio * ratio / var_min + 1.0) * 1.1 + u
+
+
+# ---------------------------------------------------------------------------------------------------- pooling
+def test_pool_references_and_their_seeded_errors():
+    """maxpool_ref / maxpool_bwd_ref / gap_ref against torch; a padding of 0 is rejected on all-negative inputs (and only
+    there: on relu outputs, what tests/test_gpu_ops.py feeds, it is invisible); the last of equal maxima on constant patches."""
+    import torch.nn.functional as F
+
+    g = torch.Generator().manual_seed(0)
+    for n, h, w, c in [(1, 2, 2, 8), (2, 3, 5, 24), (3, 7, 6, 64), (2, 7, 5, 8)]:
+        x = kc.bf(torch.randn(n, h, w, c, generator=g))
+        best, code = kc.maxpool_ref(x)
+        xt = x.permute(0, 3, 1, 2).double().requires_grad_(True)
+        want = F.max_pool2d(xt, 3, 2, 1)
+        assert torch.equal(best.double(), want.permute(0, 2, 3, 1))
+        dy = torch.randn(best.shape, generator=g)
+        want.backward(dy.permute(0, 3, 1, 2).double())
+        assert torch.equal(kc.maxpool_bwd_ref(dy, code, h, w), xt.grad.permute(0, 2, 3, 1))
+        neg = -x.abs() - 0.5
+        assert not torch.equal(kc.maxpool_ref(neg, "zero_pad")[0], kc.maxpool_ref(neg)[0])
+        pos = x.clamp_min(0.0)
+        assert torch.equal(kc.maxpool_ref(pos, "zero_pad")[0], kc.maxpool_ref(pos)[0])            # relu outputs cannot see it
+        if h % 2 == 1 and w % 2 == 1:
+            flat = torch.ones(n, h, w, c)
+            assert not torch.equal(kc.maxpool_ref(flat, "last_max")[1], kc.maxpool_ref(flat)[1])
+            assert torch.equal(kc.maxpool_ref(flat, "last_max")[0], kc.maxpool_ref(flat)[0])
+    x = kc.bf(torch.randn(5, 49, 24, generator=g) * 2 + 0.5)
+    torch.testing.assert_close(kc.gap_ref(x), x.double().mean(1), rtol=1e-14, atol=1e-14)
+    _accept(kc.gap_ref(x, emulate=True), kc.gap_ref(x), kc.gap_ref(x, emulate=True), "gap emulation")
+    _reject(kc.bf(x.double()[:, :-1].mean(1)), kc.gap_ref(x), kc.gap_ref(x, emulate=True), "gap without the last pixel")
