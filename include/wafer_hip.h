@@ -899,6 +899,46 @@ int wm_rank_query(const float* xq, int m, const float* x, int n, int d, int metr
                   const int32_t* skip, int k, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * KMeans on embeddings (sklearn.cluster.KMeans(n_clusters=k) of notebooks/1.0-Preprocess-WM811K.ipynb; cluster.KMeans):
+ * the update step and the k-means++ seeding (csrc/kmeans.hip).  The assignment step is wm_group_min_dist on the centres
+ * of R restarts laid out as R groups of k columns, [R * k][d]: one pass over the rows serves every restart.  x float32
+ * [n][d] under the clustering section's rules (16-byte aligned, d % 4 == 0, d <= 1024); n <= 2^24, 1 <= k <= 65536,
+ * 1 <= R <= 1024.  The workspace-size functions return 0 for sizes that are not supported.  No floating-point atomics,
+ * none on global memory (the member counts are integer adds in LDS), no memset; the order of every floating-point sum
+ * depends on (n, d, k) alone: two calls give the same bits, and a restart gives the same bits whether
+ * it runs alone or among others.
+ *
+ * wm_kmeans_update: assign int32 [n][R] and dist float32 [n][R] are what wm_group_min_dist wrote for those centres (the
+ * column r * k + c for cluster c of restart r, and the distance to it); a value outside [r * k, (r + 1) * k) puts the row
+ * in no cluster of restart r.  prev int32 [n][R] is an earlier assign or NULL.  Per restart r and cluster c:
+ * counts[r][c] = the number of members and centres_new[r][c][:] = the float64 sum of the members' rows, divided in double
+ * by the count and rounded to float32 once; a cluster without a member keeps centres_old[r][c][:] and reports 0.  The sum
+ * runs over fixed slabs of rows, in row order inside a slab, and the slabs are folded in slab order.  Per restart:
+ * inertia[r] = the double sum of (double)dist[i][r]^2 (the same slabs: 64 lanes take a slab's rows round-robin, each in
+ * order, the lane sums are added in lane order and the slabs' sums in a fixed tree), n_changed[r] = the number of rows with assign[i][r] != prev[i][r] (n when prev is NULL), shift2[r] = the double
+ * sum over c and the features of ((double)centres_new - (double)centres_old)^2 (blocks of 256 elements, each and then
+ * the blocks' sums in a fixed tree).  centres_old, centres_new
+ * float32 [R][k][d] (two buffers), counts int32 [R][k], inertia, shift2 double [R], n_changed int32 [R]. */
+size_t wm_kmeans_update_workspace_bytes(int n, int d, int k, int R);
+int wm_kmeans_update(const float* x, int n, int d, const int32_t* assign, const float* dist, const int32_t* prev, int R, int k,
+                     const float* centres_old, float* centres_new, int32_t* counts, double* inertia, int32_t* n_changed,
+                     double* shift2, void* workspace, size_t workspace_bytes, void* stream);
+/* wm_kmeans_seed: greedy k-means++ (Arthur & Vassilvitskii 2007 with sklearn's local trials) driven by a table of
+ * uniforms u double [k][T] in [0, 1) on the device, so that the device makes no random choice; 1 <= T <= 16, k <= n.
+ * Centre 0 is row min(floor(u[0][0] * n), n - 1).  For every later centre c: closest2[i] = the smallest squared distance of
+ * row i to the centres chosen so far (the float32 distance of the clustering section, squared in double), pot = its sum,
+ * candidate t = the first row i with closest2[i] > 0 whose running sum exceeds u[c][t] * pot (so a row at distance 0 is
+ * never drawn; no such row: the last row with closest2 > 0; pot == 0: row min(floor(u[c][t] * n), n - 1)); its potential
+ * is the sum over i of min(closest2[i], dist(i, candidate)^2); the candidate of the lowest potential wins, equal potentials
+ * resolve to the lowest t, and closest2 becomes its minima.  Sums and running sums: blocks of 256 rows in row order, the
+ * blocks folded in block order.  Everything is chained on the stream: no host round trip.  Outputs: centres float32
+ * [k][d] (copies of the chosen rows), idx int32 [k], and where not NULL cand int32 [k][T] and pots double [k][T], the
+ * candidates and potentials of every step (step 0: one candidate; the unused entries are -1 / +inf). */
+size_t wm_kmeans_seed_workspace_bytes(int n, int d, int k, int T);
+int wm_kmeans_seed(const float* x, int n, int d, int k, int T, const double* u, float* centres, int32_t* idx, int32_t* cand,
+                   double* pots, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * UMAP (umap.UMAP(...).fit_transform of the reference's embedding notebooks) on the graph of wm_knn_graph; the formulas
  * are stated in full in csrc/umap.hip.
  *

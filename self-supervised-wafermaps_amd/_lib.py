@@ -312,6 +312,13 @@ SIGNATURES = {
     "wm_rank_query_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_rank_query": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                               c_void_p, c_size_t, c_void_p]),
+    # ---- KMeans
+    "wm_kmeans_update_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_kmeans_update": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_kmeans_seed_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_kmeans_seed": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,

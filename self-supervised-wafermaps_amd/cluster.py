@@ -35,11 +35,19 @@ Boruvka round of every cluster's own tree per launch, wm_group_min_mreach); whic
 internal and the score itself are host code (`validity_from_parts`).  `relative_validity` is the package's cheap
 approximation from the fitted spanning tree and uses no GPU.  DESIGN.md states the definition and what differs from the
 package.
+
+KMeans (`KMeans`, `kmeans_step`, `kmeans_plusplus`; the reference's sklearn.cluster.KMeans(n_clusters=k) of notebook
+1.0-Preprocess-WM811K): a partition of ALL rows into a chosen number of clusters, the baseline that silhouette,
+Calinski-Harabasz and Davies-Bouldin were designed for.  The assignment is wm_group_min_dist again, with the centres of
+R restarts laid out as R groups of k columns, so one pass over the rows assigns them for every restart; the update
+(wm_kmeans_update: float64 sums in a fixed order, no atomics) and the k-means++ seeding (wm_kmeans_seed, driven by a
+host-drawn table of uniforms) are csrc/kmeans.hip.  The stopping rule (`kmeans_stop`) and the empty-cluster rule
+(`kmeans_relocation_plan`) are host functions on numpy values.  DESIGN.md states the definitions.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -1307,3 +1315,401 @@ def homogeneity_score(labels_true, labels_pred) -> float:
     nz = table > 0
     h_ck = float(-(table[nz] / n * np.log(table[nz] / np.broadcast_to(pk, table.shape)[nz])).sum())
     return 1.0 - h_ck / h_c
+
+
+# ------------------------------------------------------------------------------------------------ KMeans
+
+
+class KMeansStep(NamedTuple):
+    """What `kmeans_step` returns.  With centres [k, d] the restart axis is dropped: labels / distances [n], centres
+    [k, d], counts [k], and inertia / n_changed / shift2 are 0-d tensors."""
+    labels: object      # int32 [n, R] on the device: the nearest centre of every restart, in [0, k)
+    distances: object   # float32 [n, R] on the device: the distance to it
+    centres: object     # float32 [R, k, d] on the device: the updated centres
+    counts: object      # int32 [R, k] on the device
+    inertia: object     # float64 [R] on the device
+    n_changed: object   # int32 [R] on the device
+    shift2: object      # float64 [R] on the device
+
+
+def _kmeans_n_init(n_init, init) -> int:
+    """sklearn's rule: n_init="auto" is 1 for k-means++ or an array of centres and 10 for "random"."""
+    if isinstance(n_init, str):
+        if n_init != "auto":
+            raise ValueError(f"n_init must be 'auto' or a positive integer ({n_init!r} given)")
+        return 10 if isinstance(init, str) and init == "random" else 1
+    if int(n_init) < 1:
+        raise ValueError(f"n_init must be 'auto' or a positive integer ({n_init!r} given)")
+    return int(n_init)
+
+
+def kmeans_stop(n_changed: int, shift2: float, tol_scaled: float) -> Optional[str]:
+    """The stopping rule of one restart after one iteration (sklearn's `_kmeans_single_lloyd`): "labels" when no row
+    changed its centre (strict convergence), otherwise "tol" when the squared centre shift is at most the scaled
+    tolerance, otherwise None.  Pure host code."""
+    if int(n_changed) == 0:
+        return "labels"
+    if float(shift2) <= float(tol_scaled):
+        return "tol"
+    return None
+
+
+def kmeans_relocation_plan(counts, labels, distances):
+    """This module's empty-cluster rule as pure numpy (no parity with sklearn's relocation is claimed): the empty
+    clusters (counts == 0) in ascending id take, one each, the rows farthest from their assigned centres, in the order
+    (distance descending, index ascending).  A taken row leaves its old cluster's sum and count, so a row whose cluster
+    would be left without a member is passed over.  Returns (clusters int64 [e], rows int64 [e]): cluster clusters[q]
+    takes row rows[q]; fewer pairs than empty clusters when the rows run out."""
+    counts = np.asarray(counts, dtype=np.int64).copy()
+    labels = np.asarray(labels, dtype=np.int64)
+    distances = np.asarray(distances, dtype=np.float64)
+    if labels.ndim != 1 or distances.shape != labels.shape or counts.ndim != 1:
+        raise ValueError("counts [k], labels [n] and distances [n] expected")
+    empty = np.flatnonzero(counts == 0)
+    order = np.lexsort((np.arange(labels.size), -distances))
+    clusters, rows, at = [], [], 0
+    for c in empty:
+        while at < order.size and counts[labels[order[at]]] <= 1:
+            at += 1
+        if at == order.size:
+            break
+        i = int(order[at])
+        at += 1
+        counts[labels[i]] -= 1
+        clusters.append(int(c))
+        rows.append(i)
+    return np.asarray(clusters, dtype=np.int64), np.asarray(rows, dtype=np.int64)
+
+
+def kmeans_relocate(x, labels, centres_old, centres_new, counts, clusters, rows):
+    """Apply a `kmeans_relocation_plan` to one restart's update on the host: (centres float32 [k, d], counts int64 [k],
+    shift2 float).  Cluster clusters[q] becomes row rows[q] with count 1; every cluster that gave a row is recomputed
+    from its remaining members as the exactly rounded float64 sum (math.fsum) divided by the count and rounded to
+    float32 once; shift2 is math.fsum of the squared moves against centres_old.  x: the prepared device matrix; the
+    other arguments numpy."""
+    import torch
+
+    labels = np.asarray(labels, dtype=np.int64)
+    centres = np.array(centres_new, dtype=np.float32)
+    counts = np.asarray(counts, dtype=np.int64).copy()
+    taken = np.zeros(labels.size, dtype=bool)
+    taken[rows] = True
+    take = x[torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(x.device)].cpu().numpy()
+    for q, c in enumerate(clusters):
+        centres[c] = take[q]
+        counts[c] = 1
+    for donor in np.unique(labels[rows]):
+        keep = np.flatnonzero((labels == donor) & ~taken)
+        member = x[torch.from_numpy(keep).to(x.device)].cpu().numpy().astype(np.float64)
+        centres[donor] = np.array([math.fsum(col) for col in member.T]) / float(keep.size)
+        counts[donor] = keep.size
+    move = centres.astype(np.float64) - np.asarray(centres_old, dtype=np.float64)
+    return centres, counts, math.fsum((move * move).ravel().tolist())
+
+
+def _kmeans_update(x, cols, dist, prev_cols, centres):
+    """wm_kmeans_update on prepared operands: cols / dist [n, R] as wm_group_min_dist wrote them for centres [R, k, d];
+    (centres_new, counts, inertia, n_changed, shift2) on the device."""
+    import torch
+
+    (n, d), (r, k, _) = x.shape, centres.shape
+    lib = _lib.load()
+    need = lib.wm_kmeans_update_workspace_bytes(n, d, k, r)
+    if need == 0:
+        raise ValueError(f"kmeans update: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    new = torch.empty_like(centres)
+    counts = torch.empty((r, k), dtype=torch.int32, device=x.device)
+    inertia = torch.empty(r, dtype=torch.float64, device=x.device)
+    changed = torch.empty(r, dtype=torch.int32, device=x.device)
+    shift2 = torch.empty(r, dtype=torch.float64, device=x.device)
+    check(lib.wm_kmeans_update(ptr(x), n, d, ptr(cols), ptr(dist), ptr(prev_cols), r, k, ptr(centres), ptr(new), ptr(counts),
+                               ptr(inertia), ptr(changed), ptr(shift2), ptr(ws), need, stream_ptr()), "wm_kmeans_update")
+    return new, counts, inertia, changed, shift2
+
+
+def _kmeans_assign(x, centres):
+    """One assignment pass for all restarts: (cols int32 [n, R] = r * k + label, dist float32 [n, R]).  wm_group_min_dist
+    itself, what `group_min_distances` calls: the centres [R, k, d] are in runs of equal group ids already and every group
+    has columns, so that function's sort, its gather, its fills and its index mapping would each be the identity."""
+    import torch
+
+    (n, d), (r, k, _) = x.shape, centres.shape
+    group = torch.arange(r, dtype=torch.int32, device=x.device).repeat_interleave(k).contiguous()
+    lib = _lib.load()
+    need = lib.wm_group_min_dist_workspace_bytes(n, r * k, d, r)
+    if need == 0:
+        raise ValueError(f"kmeans assignment: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    dist = torch.empty((n, r), dtype=torch.float32, device=x.device)
+    cols = torch.empty((n, r), dtype=torch.int32, device=x.device)
+    check(lib.wm_group_min_dist(ptr(x), n, ptr(centres), ptr(group), r * k, d, 0, r, ptr(dist), ptr(cols), ptr(ws), need,
+                                stream_ptr()), "wm_group_min_dist")
+    return cols, dist
+
+
+def _kmeans_centres(x, centres):
+    """Prepared float32 centres [R, k, d_padded] on x's device and whether the restart axis was given."""
+    import torch
+
+    require_gpu(centres)
+    if centres.dim() not in (2, 3):
+        raise ValueError("centres [k, d] or [R, k, d] expected")
+    many = centres.dim() == 3
+    c = centres.float() if many else centres.float().unsqueeze(0)
+    if c.shape[2] % 4:
+        c = torch.nn.functional.pad(c, (0, 4 - c.shape[2] % 4))
+    if c.shape[2] != x.shape[1]:
+        raise ValueError(f"the centres have {centres.shape[-1]} features, the rows {x.shape[1]} (after padding)")
+    if c.shape[0] < 1 or c.shape[1] < 1:
+        raise ValueError("at least one restart and one centre expected")
+    return c.contiguous(), many
+
+
+def kmeans_step(x, centres, prev=None) -> KMeansStep:
+    """One Lloyd iteration on device tensors: the assignment pass (`group_min_distances`, every restart a group of
+    columns: one pass over x [n, d] serves all R restarts) and the update (wm_kmeans_update).  centres [k, d] or
+    [R, k, d]; prev: the labels of an earlier step (int32, the shape of the labels returned here) or None, in which
+    case n_changed = n.  A cluster without a member keeps its centre and has count 0 (`KMeans.fit` then applies
+    `kmeans_relocation_plan`; this function does not).  Returns a `KMeansStep`."""
+    import torch
+
+    x = _prep(x)
+    c, many = _kmeans_centres(x, centres)
+    r, k, _ = c.shape
+    offs = (torch.arange(r, dtype=torch.int32, device=x.device) * k).unsqueeze(0)
+    prev_cols = None
+    if prev is not None:
+        require_gpu(prev)
+        p = prev if many else prev.unsqueeze(1)
+        if p.shape != (x.shape[0], r) or p.dtype != torch.int32:
+            raise ValueError("prev: the int32 labels of an earlier step expected")
+        prev_cols = (p + offs).contiguous()
+    cols, dist = _kmeans_assign(x, c)
+    new, counts, inertia, changed, shift2 = _kmeans_update(x, cols, dist, prev_cols, c)
+    labels = cols - offs
+    new = new[:, :, :centres.shape[-1]].contiguous()
+    if many:
+        return KMeansStep(labels, dist, new, counts, inertia, changed, shift2)
+    return KMeansStep(labels[:, 0].contiguous(), dist[:, 0].contiguous(), new[0], counts[0], inertia[0], changed[0], shift2[0])
+
+
+def kmeans_plusplus(x, n_clusters: int, *, random_state=None, uniforms=None, n_local_trials: Optional[int] = None,
+                    return_details: bool = False):
+    """Greedy k-means++ seeding on the device (wm_kmeans_seed): (centres float32 [k, d] on the device, indices int64
+    [k], numpy), the chosen rows of x [n, d] and their row numbers.
+
+    The rule is sklearn.cluster.kmeans_plusplus's: the first centre uniformly, every later one the best of
+    `n_local_trials` (default 2 + int(ln k)) rows drawn with probability proportional to the squared distance to the
+    nearest centre chosen so far, the best being the one that lowers the potential most.  This is sklearn's
+    DISTRIBUTION and not sklearn's random stream: the draws come from a table of uniforms u float64 [k, T] in [0, 1),
+    `numpy.random.default_rng(random_state).random((k, T))` unless `uniforms` gives it, and the same seed picks other
+    rows than sklearn does.  Centre 0 is row min(floor(u[0, 0] * n), n - 1); trial t of centre c is the first row whose
+    running sum of the squared distances exceeds u[c, t] * potential (strictly, so a row at distance 0 is never drawn);
+    include/wafer_hip.h states the rest.  With `return_details` a dict follows: candidates int64 [k, T] (-1 unused) and
+    potentials float64 [k, T] (inf unused) of every step, and the uniforms."""
+    import torch
+
+    x = _prep(x)
+    n, d = x.shape
+    k = int(n_clusters)
+    if not 1 <= k <= n:
+        raise ValueError(f"n_clusters ({k}) must be in [1, n_samples = {n}]")
+    t = 2 + int(math.log(k)) if n_local_trials is None else int(n_local_trials)
+    if uniforms is None:
+        u = np.random.default_rng(random_state).random((k, t))
+    else:
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (k, t) or not ((u >= 0) & (u < 1)).all():
+            raise ValueError(f"uniforms: float64 [{k}, {t}] in [0, 1) expected")
+    lib = _lib.load()
+    need = lib.wm_kmeans_seed_workspace_bytes(n, d, k, t)
+    if need == 0:
+        raise ValueError(f"kmeans_plusplus: unsupported sizes n={n} d={d} n_clusters={k} n_local_trials={t} (1 .. 16 trials)")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    u_d = torch.from_numpy(u).to(x.device)
+    centres = torch.empty((k, d), dtype=torch.float32, device=x.device)
+    idx = torch.empty(k, dtype=torch.int32, device=x.device)
+    cand = torch.empty((k, t), dtype=torch.int32, device=x.device) if return_details else None
+    pots = torch.empty((k, t), dtype=torch.float64, device=x.device) if return_details else None
+    check(lib.wm_kmeans_seed(ptr(x), n, d, k, t, ptr(u_d), ptr(centres), ptr(idx), ptr(cand), ptr(pots), ptr(ws), need,
+                             stream_ptr()), "wm_kmeans_seed")
+    out = (centres, idx.cpu().numpy().astype(np.int64))
+    if return_details:
+        return out + ({"candidates": cand.cpu().numpy().astype(np.int64), "potentials": pots.cpu().numpy(), "uniforms": u},)
+    return out
+
+
+class KMeans:
+    """sklearn.cluster.KMeans (Lloyd) on device tensors.  `fit(x)` sets `cluster_centers_` (float32 [k, d] on the
+    device), `labels_` (numpy int64 [n]), `inertia_`, `n_iter_`, `n_features_in_`, and per restart `inertias_` and
+    `n_iters_` (numpy [R]).
+
+    `init`: "k-means++" (`kmeans_plusplus`, one table of uniforms per restart from one generator), "random" (k distinct
+    rows from a host permutation per restart), an array or tensor [k, d], or (an extension) [R, k, d] for R explicit
+    restarts.  `n_init="auto"` is 1 for k-means++ or an array and 10 for "random", as sklearn; with an array the number
+    of restarts is the array's.  All restarts advance together, one assignment pass per iteration over all of them
+    (`kmeans_step`); a restart that has stopped leaves the pass.  No sum depends on the number of restarts, so each
+    restart's result is bit-equal to that restart run alone.  The kept restart is the one of the lowest inertia, the
+    lowest index among equals.
+
+    Stopping rule (sklearn's, `kmeans_stop`): `tol` is scaled by the mean per-feature variance of x.  After the update of
+    iteration i a restart stops when no row changed its centre against iteration i - 1 (the centres of the update are
+    then the ones the labels were assigned to), or when the squared centre shift is at most the scaled tolerance, or at
+    max_iter.  After a stop on the tolerance or on max_iter one more assignment pass runs, so that `labels_` and
+    `inertia_` belong to `cluster_centers_`.  `n_iter_` is the number of updates, as sklearn counts.
+
+    Empty clusters follow this module's own rule (`kmeans_relocation_plan`, a host detour on the iteration that has a
+    zero count; no parity with sklearn's relocation is claimed); a restart never stops on the iteration that relocated.
+    `sample_weight` and algorithm="elkan" are not implemented."""
+
+    def __init__(self, n_clusters: int = 8, *, init="k-means++", n_init="auto", max_iter: int = 300, tol: float = 1e-4,
+                 random_state=None, algorithm: str = "lloyd"):
+        if algorithm == "elkan":
+            raise NotImplementedError("algorithm='elkan' is not implemented (available: lloyd)")
+        if algorithm != "lloyd":
+            raise ValueError(f"unknown algorithm {algorithm!r} (available: lloyd)")
+        if int(n_clusters) < 1:
+            raise ValueError("n_clusters must be at least 1")
+        if isinstance(init, str) and init not in ("k-means++", "random"):
+            raise ValueError(f"init must be 'k-means++', 'random' or an array of centres ({init!r} given)")
+        if int(max_iter) < 1 or float(tol) < 0:
+            raise ValueError("max_iter >= 1 and tol >= 0 required")
+        self.n_clusters, self.init, self.n_init = int(n_clusters), init, n_init
+        self._n_init = _kmeans_n_init(n_init, init)
+        self.max_iter, self.tol, self.random_state, self.algorithm = int(max_iter), float(tol), random_state, algorithm
+        self.cluster_centers_ = self.labels_ = self.inertia_ = self.n_iter_ = self.n_features_in_ = None
+        self.inertias_ = self.n_iters_ = None
+
+    @staticmethod
+    def _refuse_weights(sample_weight):
+        if sample_weight is not None:
+            raise NotImplementedError("sample_weight is not implemented")
+
+    def _initial(self, xp):
+        """float32 [R, k, d_padded] on the device."""
+        import torch
+
+        n, k = xp.shape[0], self.n_clusters
+        if not isinstance(self.init, str):
+            init = self.init if hasattr(self.init, "is_cuda") else torch.as_tensor(np.asarray(self.init, dtype=np.float32)).to(xp.device)
+            c, _ = _kmeans_centres(xp, init.contiguous())
+            if c.shape[1] != k:
+                raise ValueError(f"init holds {c.shape[1]} centres, n_clusters is {k}")
+            return c
+        rng = np.random.default_rng(self.random_state)
+        out = []
+        for _ in range(self._n_init):
+            if self.init == "random":
+                rows = np.sort(rng.permutation(n)[:k])
+                out.append(xp[torch.from_numpy(rows).to(xp.device)])
+            else:
+                t = 2 + int(math.log(k))
+                out.append(kmeans_plusplus(xp, k, uniforms=rng.random((k, t)))[0])
+        return torch.stack(out).contiguous()
+
+    def fit(self, x, y=None, sample_weight=None) -> "KMeans":
+        import torch
+
+        self._refuse_weights(sample_weight)
+        xp = _prep(x)
+        n, k = xp.shape[0], self.n_clusters
+        if k > n:
+            raise ValueError(f"n_clusters ({k}) must be at most the number of samples ({n})")
+        cur = self._initial(xp)  # the centres of the restarts that still run, [len(active), k, d]; never written in place
+        r = cur.shape[0]
+        centres = torch.empty_like(cur)  # every restart's final centres
+        tol_scaled = float(xp[:, :x.shape[1]].double().var(dim=0, unbiased=False).mean()) * self.tol  # (no padding columns)
+        active = list(range(r))
+        prev = None  # cols [n, len(active)] of the iteration before
+        labels = np.zeros((r, n), dtype=np.int64)
+        inertias, n_iters = np.zeros(r), np.zeros(r, dtype=np.int64)
+        again = []  # restarts that need the closing assignment pass
+        for it in range(1, self.max_iter + 1):
+            cols, dist = _kmeans_assign(xp, cur)
+            new, counts, inertia, changed, shift2 = _kmeans_update(xp, cols, dist, prev, cur)
+            # one synchronisation per iteration: what the stopping rule reads, and whether a cluster is empty
+            inertia_h, shift_h, changed_h, empty_h = torch.stack(
+                [inertia, shift2, changed.double(), (counts == 0).any(dim=1).double()]).cpu().numpy()
+            relocated = set()
+            for a in np.flatnonzero(empty_h):
+                lab, counts_a = (cols[:, a] - a * k).cpu().numpy(), counts[a].cpu().numpy()
+                clusters, rows = kmeans_relocation_plan(counts_a, lab, dist[:, a].cpu().numpy())
+                if rows.size:
+                    c_new, _, shift_h[a] = kmeans_relocate(xp, lab, cur[a].cpu().numpy(), new[a].cpu().numpy(), counts_a, clusters,
+                                                           rows)
+                    new[a] = torch.from_numpy(c_new).to(xp.device)
+                    relocated.add(int(a))
+            keep = []
+            for a, rr in enumerate(active):
+                why = None if a in relocated else kmeans_stop(changed_h[a], shift_h[a], tol_scaled)
+                if why is None and it < self.max_iter:
+                    keep.append(a)
+                    continue
+                n_iters[rr] = it
+                centres[rr] = new[a]
+                if why == "labels":
+                    labels[rr] = (cols[:, a] - a * k).cpu().numpy()
+                    inertias[rr] = inertia_h[a]
+                else:
+                    again.append(rr)
+            if not keep:
+                break
+            if len(keep) == len(active):
+                cur, prev = new, cols
+                continue
+            k_idx = torch.tensor(keep, device=xp.device)
+            offs = (torch.arange(len(keep), dtype=torch.int32, device=xp.device) - k_idx.to(torch.int32)) * k
+            cur = new[k_idx].contiguous()
+            prev = (cols[:, k_idx] + offs.unsqueeze(0)).contiguous()  # (the columns renumbered for the restarts that go on)
+            active = [active[a] for a in keep]
+        if again:
+            sel = torch.tensor(again, device=xp.device)
+            last = centres[sel].contiguous()
+            cols, dist = _kmeans_assign(xp, last)
+            _, _, inertia, _, _ = _kmeans_update(xp, cols, dist, None, last)
+            offs = (torch.arange(len(again), dtype=torch.int32, device=xp.device) * k).unsqueeze(0)
+            labels[again] = (cols - offs).cpu().numpy().T
+            inertias[again] = inertia.cpu().numpy()
+        best = int(np.argmin(inertias))
+        d_in = int(x.shape[1])
+        self._centres_padded = centres[best].contiguous()
+        self.cluster_centers_ = centres[best, :, :d_in].contiguous()
+        self.labels_, self.inertia_, self.n_iter_ = labels[best], float(inertias[best]), int(n_iters[best])
+        self.inertias_, self.n_iters_, self.n_features_in_ = inertias, n_iters, d_in
+        return self
+
+    def _check_fitted(self, x):
+        if self.cluster_centers_ is None:
+            raise RuntimeError("KMeans used before fit")
+        if x.dim() != 2 or x.shape[1] != self.n_features_in_:
+            raise ValueError(f"rows have {x.shape[-1]} features, the model was fitted on {self.n_features_in_}")
+
+    def fit_predict(self, x, y=None, sample_weight=None) -> np.ndarray:
+        return self.fit(x, sample_weight=sample_weight).labels_
+
+    def predict(self, x) -> np.ndarray:
+        """The nearest centre of every row: numpy int64 [m]; `manifold.knn_query(x, cluster_centers_, 1)`'s choice."""
+        self._check_fitted(x)
+        cols, _ = _kmeans_assign(_prep(x), self._centres_padded.unsqueeze(0))
+        return cols[:, 0].cpu().numpy().astype(np.int64)
+
+    def transform(self, x):
+        """The distance of every row to every centre: float32 [m, k] on the device (every centre a group of its own)."""
+        import torch
+
+        self._check_fitted(x)
+        k = self.n_clusters
+        return group_min_distances(_prep(x), self._centres_padded, torch.arange(k, dtype=torch.int32), k)[0]
+
+    def fit_transform(self, x, y=None, sample_weight=None):
+        return self.fit(x, sample_weight=sample_weight).transform(x)
+
+    def score(self, x, y=None, sample_weight=None) -> float:
+        """Minus the inertia of x under the fitted centres (the double sum of the squared float32 distances)."""
+        self._refuse_weights(sample_weight)
+        self._check_fitted(x)
+        xp = _prep(x)
+        c = self._centres_padded.unsqueeze(0)
+        cols, dist = _kmeans_assign(xp, c)
+        return -float(_kmeans_update(xp, cols, dist, None, c)[2][0])

@@ -28,7 +28,7 @@
 //                         each threshold in the row's (distance, index) order -- the rank primitive of trustworthiness and
 //                         continuity (manifold.py); integer results.
 //
-// ONE distance function serves all of them (cl_accum / cl_finish below): the float32 differences a_k - b_k are
+// ONE distance function serves all of them (cl_accum / cl_finish, cl_dist.h): the float32 differences a_k - b_k are
 // accumulated in float32 in index order k = 0, 1, ..., d-1 in a single accumulator (Euclidean: fma(t, t, acc), then a
 // correctly rounded square root; Manhattan: acc + |t|).  Not ||a||^2 + ||b||^2 - 2ab: wafer embeddings contain
 // near-duplicates, whose distance that form cancels away.  Two properties the host code and the tests rely on:
@@ -116,6 +116,7 @@
 // ((16 TM + 64) rows per 16 TM x 64 pairs).
 #include <limits.h>
 
+#include "cl_dist.h"
 #include "common.h"
 
 namespace {
@@ -137,17 +138,7 @@ constexpr bool cl_keeps_best(int mode) { return cl_is_minedge(mode) || mode == C
 // the modes on rows sorted by group that walk only the column tiles of the row tile's own groups
 constexpr bool cl_block_diagonal(int mode) { return mode == CL_APCORE || mode == CL_MINEDGE_G; }
 
-template <int METRIC>
-__device__ __forceinline__ float cl_accum(float a, float b, float acc) {
-  const float t = a - b;
-  if constexpr (METRIC == 0) return fmaf(t, t, acc);
-  return acc + fabsf(t);
-}
-template <int METRIC>
-__device__ __forceinline__ float cl_finish(float acc) {
-  if constexpr (METRIC == 0) return sqrtf(acc);  // (the correctly rounded root; __fsqrt_rn is the ~1 ulp native one here)
-  return acc;
-}
+// cl_accum / cl_finish: cl_dist.h
 
 struct ClArgs {
   const float* x;   // the column operand [n][d]
