@@ -1009,6 +1009,38 @@ int wm_densmap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32
                       double dens_lambda, double dens_frac, double dens_var_shift, uint32_t seed, int epoch_begin, int epoch_end,
                       int n_epochs, int neg_rate, void* workspace, size_t workspace_bytes, int* result_buffer, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PCA of an embedding matrix (sklearn.decomposition.PCA): the passes over the rows, on float64 MFMA tiles
+ * (v_mfma_f64_16x16x4_f64); tile sizes, the slice rule and the summation orders are stated in csrc/pca.hip.  The
+ * eigendecomposition of the d x d covariance is host code (decomposition.py).
+ *
+ * Common to the four: x float32 [n][d] row-major; 1 <= n <= 2^24; d % 4 == 0, d <= 4096 (pad with zero columns);
+ * 1 <= m <= d; mean: float64 [d] or NULL (nothing subtracted / added); every pointer aligned to its element, the
+ * workspace and the x of wm_pca_gram to 16 bytes; the workspace is owned by the caller and holds at least the companion's byte count (0:
+ * unsupported sizes; the companions launch nothing; project and reconstruct report a fixed token size and store nothing
+ * there).  No atomics, no allocation, no synchronisation: two calls give the same bits.
+ *
+ * wm_pca_mean: mean_out[f] = (sum_i x[i][f]) / n in double: slabs of rows summed sequentially in row order, the slabs'
+ * sums added in slab order.  Slab size: 256 rows while that gives at most 1024 slabs, above that ceil(n / 1024)
+ * rounded up to a multiple of 256. */
+size_t wm_pca_mean_workspace_bytes(int n, int d);
+int wm_pca_mean(const float* x, int n, int d, double* mean_out, void* workspace, size_t workspace_bytes, void* stream);
+/* out[d][d] float64 = sum_i (x_i - mean)(x_i - mean)^T, centred before it is multiplied; exactly symmetric (tiles on
+ * and below the diagonal are computed, the merge mirrors them).  Rows are cut into slices, each slice's partial plane
+ * owned by one workgroup per tile, the planes added in slice order. */
+size_t wm_pca_gram_workspace_bytes(int n, int d);
+int wm_pca_gram(const float* x, int n, int d, const double* mean, double* out, void* workspace, size_t workspace_bytes,
+                void* stream);
+/* out[n][m] float32 = (x - mean) W^T, W float64 [m][d]; accumulated in double in feature order, rounded once. */
+size_t wm_pca_project_workspace_bytes(int n, int d, int m);
+int wm_pca_project(const float* x, int n, int d, const double* mean, const double* w, int m, float* out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* out[n][d] float32 = y W + mean, y float32 [n][m], W float64 [m][d]; accumulated in double in component order, the
+ * mean added last, rounded once. */
+size_t wm_pca_reconstruct_workspace_bytes(int n, int m, int d);
+int wm_pca_reconstruct(const float* y, int n, int m, const double* w, int d, const double* mean, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

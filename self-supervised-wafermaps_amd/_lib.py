@@ -319,6 +319,15 @@ SIGNATURES = {
     "wm_kmeans_seed_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_kmeans_seed": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    # ---- PCA
+    "wm_pca_mean_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_pca_mean": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_pca_gram_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_pca_gram": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_pca_project_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_pca_project": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_pca_reconstruct_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_pca_reconstruct": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
