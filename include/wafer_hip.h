@@ -166,7 +166,10 @@ int wm_l2_normalize(const void* x, int in_dtype, int rows, int d, float eps, voi
                     int out_dtype, float* inv_norm, void* stream);
 /* Backward of the above: dx = (dy - y * <dy,y>) * inv_norm ; all float32. */
 /* dx (out_dtype WM_F32 or WM_BF16) = (dy (dy_dtype WM_F32 or WM_BF16) - y <dy, y>) * inv_norm (* *scale_dev when non-NULL: the device-resident
- * gradient of the scalar loss the normalised rows feed, so that no separate scaling pass is needed). */
+ * gradient of the scalar loss the normalised rows feed, so that no separate scaling pass is needed).  A row the forward
+ * clamped (||x|| < eps, seen as ||y||^2 < 0.999) gets dx = dy * inv_norm: the clamp passes no gradient to the norm.
+ * eps is not an argument here, so a clamped row with ||x|| in [0.9995 eps, eps) is taken for an unclamped one and keeps
+ * the projection (relative difference of dx at the most 1: the band where F.normalize itself is discontinuous). */
 int wm_l2_normalize_bwd(const void* dy, int dy_dtype, const float* y, const float* inv_norm, int rows, int d,
                         void* dx, int out_dtype, const float* scale_dev, void* stream);
 
@@ -511,7 +514,7 @@ int wm_vicreg_variance(const float* var_biased, int N, int D, float eps, float* 
 
 /* lightly's SwaV Sinkhorn-Knopp (scripts/WM811k_benchmark.py:832-834 via lightly.loss.SwaVLoss): out WM_F32 / WM_BF16
  * [B][K] prototype scores; Q [B][K] f32 = the transport plan (rows sum to 1) after `iters` rounds at
- * temperature eps; workspace: B + K floats. */
+ * temperature eps (iters = 0: exp(out / eps) * B / sum, lightly's initial normalisation alone); workspace: B + K floats. */
 int wm_sinkhorn(const void* out, int dtype, int B, int K, float eps, int iters, float* Q, float* workspace,
                 void* stream);
 

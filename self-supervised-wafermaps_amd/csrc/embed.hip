@@ -51,9 +51,18 @@ __global__ __launch_bounds__(256) void l2norm_bwd(const TI* __restrict__ dy,
     if constexpr (sizeof(TI) == 2) return bf2f(dyr[c]);
     else return dyr[c];
   };
-  float dot = 0.f;
-  for (int c = lane; c < d; c += 64) dot += ld(c) * yr[c];
+  float dot = 0.f, yy = 0.f;
+  for (int c = lane; c < d; c += 64) {
+    const float yv = yr[c];
+    dot += ld(c) * yv;
+    yy += yv * yv;
+  }
   dot = wave_sum(dot);
+  yy = wave_sum(yy);
+  // a row the forward clamped (||x|| < eps) is y = x / eps with ||y|| < 1; F.normalize's clamp passes no gradient to the
+  // norm there: dx = dy / eps without the projection (an unclamped row has ||y||^2 = 1 within float32 rounding).  eps is not
+  // known here: a clamped row with ||x|| in [0.9995 eps, eps) passes for unclamped and keeps the projection.
+  if (yy < 0.999f) dot = 0.f;
   // scale: the (device) gradient of the scalar loss this normalisation feeds -- dy is then the unscaled gradient
   const float s = inv_norm[row] * (scale != nullptr ? *scale : 1.f);
   for (int c = lane; c < d; c += 64) {
@@ -904,6 +913,19 @@ __global__ __launch_bounds__(256) void sk_write_kernel(const T* __restrict__ out
   }
 }
 
+// iters = 0: lightly's initial Q /= sum(Q) is all that happens (with iters > 0 the first prototype pass absorbs it).
+// r[b] holds 1 / (B sum_k E[b][k]) from sk_sample_kernel with c = 1; every r[b] becomes 1 / sum_{b,k} E.  One block.
+__global__ __launch_bounds__(256) void sk_total_kernel(float* __restrict__ r, int B) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) s += 1.f / r[b];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const float inv_total = (float)B / (red[0] + red[1] + red[2] + red[3]);
+  for (int b = threadIdx.x; b < B; b += 256) r[b] = inv_total;   // (a thread rewrites only the entries it read)
+}
+
 __global__ void sk_fill_kernel(float* p, int n, float v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = v;
@@ -915,9 +937,15 @@ int sinkhorn_impl(const void* out, int B, int K, float eps, int iters, float* Q,
   float* r = ws;
   float* c = ws + B;
   const float inv = 1.f / eps;
-  // r = 1, c = 1 (the initial Q /= sum(Q) is absorbed by the first prototype pass; iters = 0 leaves exp * B)
+  // r = 1, c = 1 (the initial Q /= sum(Q) is absorbed by the first prototype pass; iters = 0 applies it on its own)
   sk_fill_kernel<<<wm_cdiv(B + K, 256), 256, 0, st>>>(ws, B + K, 1.f);
   WM_LAUNCH_CHECK();
+  if (iters == 0) {
+    sk_sample_kernel<T><<<B, 256, 0, st>>>(x, c, B, K, inv, r);
+    WM_LAUNCH_CHECK();
+    sk_total_kernel<<<1, 256, 0, st>>>(r, B);
+    WM_LAUNCH_CHECK();
+  }
   for (int it = 0; it < iters; ++it) {
     sk_proto_kernel<T><<<wm_cdiv(K, 256), 256, 0, st>>>(x, r, B, K, inv, c);
     WM_LAUNCH_CHECK();

@@ -23,6 +23,7 @@ of csrc/conv.hip with their fused statistics and BatchNorm-backward epilogue, th
 the launch arithmetic their block sums follow, the pooling of csrc/pool.hip), each with
 switches that seed one wrong computation, and the input families.  tests/test_kernel_check_cpu.py proves on the CPU
 that every seeded error is rejected by `check` on these families; the GPU tests feed the kernels the same families.
+The loss kernels of csrc/embed.hip have theirs in the sibling tests/loss_cases.py.
 """
 import contextlib
 import math
@@ -92,11 +93,16 @@ def _abs_term(emul, ref64) -> float:
     return float(torch.kthvalue(d, k).values)
 
 
-def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False):
+def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False,
+            floor_cosine: bool = False):
     """[(criterion, measured, bound)] and whether `got` is finite; no assertion (the CPU proofs use this).
     abs_floor: a lower limit of criterion 4's absolute term (see f32_sum_floor).
     floor_all (the float32 statistics of BatchNorm): criteria 1 and 2 are not asked to go below `factor` roundings of
-    abs_floor either -- see f32_stat_floor."""
+    abs_floor either -- see f32_stat_floor.
+    floor_cosine (the loss gradients, whose terms can cancel to zero as a whole: a collapsed batch, D = 1, a negative equal to
+    the positive): neither is the direction.  `factor` roundings of abs_floor on each of n elements are an error of norm
+    rho |ref| at the most, rho = factor abs_floor sqrt(n) / |ref|, and the angle it can turn the tensor by has sin <= rho:
+    1 - cosine <= rho^2 for rho < 1, and nothing can be asked of the direction (2) where the floor exceeds the tensor."""
     g = _flat64(got)
     finite = bool(torch.isfinite(g).all())
     a = max(_abs_term(emul, ref64), float(abs_floor))
@@ -106,7 +112,12 @@ def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, fl
         if k == "1 - cosine":
             # 1 - cosine = (relative error)^2 / 2: a stated factor f > 2 on the amplitude (F32_SUM_FACTOR) is f^2 here;
             # 2^-48 is the resolution of the float64 dot product and norms the criterion itself is computed with
-            return (factor if factor <= FACTOR else factor * factor) * yard[k] + 2.0 ** -48
+            b = (factor if factor <= FACTOR else factor * factor) * yard[k] + 2.0 ** -48
+            if floor_cosine and abs_floor > 0:
+                r = _flat64(ref64)
+                rho = factor * abs_floor * math.sqrt(r.numel()) / (float(r.norm()) + 1e-300)
+                b = max(b, rho * rho if rho < 1.0 else 2.0)
+            return b
         if k.startswith("max |err| / (a") and abs_floor > 0:
             # a >= one float32 rounding at the scale of the summed magnitudes: a score <= 1 is within that one rounding,
             # which no summation order can promise to beat (the row-order yardstick often adds few bf16 terms exactly)
@@ -147,9 +158,10 @@ def passes(got, ref64, emul, factor: float = FACTOR) -> bool:
     return finite and all(m <= b for _, m, b in rows)
 
 
-def check(got, ref64, emul, what: str, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False) -> float:
+def check(got, ref64, emul, what: str, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False,
+          floor_cosine: bool = False) -> float:
     """Assert the four criteria (each logged through parity()); returns the worst measured / bound ratio."""
-    rows, finite = verdict(got, ref64, emul, factor, abs_floor, floor_all)
+    rows, finite = verdict(got, ref64, emul, factor, abs_floor, floor_all, floor_cosine)
     assert finite, f"{what}: result holds inf / nan"
     worst = 0.0
     failed = []

@@ -679,3 +679,454 @@ def test_pool_references_and_their_seeded_errors():
     torch.testing.assert_close(kc.gap_ref(x), x.double().mean(1), rtol=1e-14, atol=1e-14)
     _accept(kc.gap_ref(x, emulate=True), kc.gap_ref(x), kc.gap_ref(x, emulate=True), "gap emulation")
     _reject(kc.bf(x.double()[:, :-1].mean(1)), kc.gap_ref(x), kc.gap_ref(x, emulate=True), "gap without the last pixel")
+
+
+# ---------------------------------------------------------------------------------------------------- loss kernels
+# csrc/embed.hip: tests/loss_cases.py holds the references (dt = float64), the float32 restatements (dt = float32) and the
+# seeded errors; tests/test_gpu_losses.py feeds the kernels the same families at the same shapes.
+import functools  # noqa: E402
+import math  # noqa: E402
+
+import loss_cases as lc  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+from oracle import ntxent as on  # noqa: E402
+
+F64, F32 = torch.float64, torch.float32
+ONE_ULP = 1.0 + 2.0 ** -24          # (a float64 scalar moved by one float32 rounding)
+
+
+def _ulp(t, seed=0):
+    """every element of a float32 tensor moved to its float32 NEIGHBOUR, up or down at random (torch.nextafter): one more
+    rounding somewhere in the chain.  An exact 0 stays (a masked entry, 0 x anything: no order of operations moves it)."""
+    if not (torch.is_tensor(t) and t.dtype == F32):
+        return t
+    g = torch.Generator().manual_seed(seed)
+    up = torch.rand(t.shape, generator=g) < 0.5
+    out = torch.nextafter(t, torch.where(up, torch.full_like(t, float("inf")), torch.full_like(t, -float("inf"))))
+    out = torch.where(t == 0, t, out)
+    assert not bool((t != 0).any()) or not torch.equal(out, t)
+    return out
+
+
+def _honest(fn, *args, **kw):
+    """An honest float32 result that is NOT the yardstick: the float32 restatement with every sum in the reverse order
+    (loss_cases.other_order: another reduction tree), then every element moved to a float32 neighbour (_ulp)"""
+    with lc.other_order():
+        out = fn(*args, dt=F32, **kw)
+    if torch.is_tensor(out):
+        return _ulp(out)
+    return {k: _ulp(v, seed=i) for i, (k, v) in enumerate(out.items())}
+
+
+def _accept32(got, ref, emul, floor, what):
+    rows, finite = lc.verdict_f32(got, ref, emul, floor)
+    line = ", ".join(f"{c}: {m:.3g} vs {b:.3g}" for c, m, b in rows)
+    assert finite and all(m <= b for _, m, b in rows), f"honest result rejected -- {what}: {line}"
+
+
+def _reject32(got, ref, emul, floor, what):
+    rows, finite = lc.verdict_f32(got, ref, emul, floor)
+    line = ", ".join(f"{c}: {m:.3g} vs {b:.3g}" for c, m, b in rows)
+    print(f"{what}: {line}")
+    assert not finite or any(m > b for _, m, b in rows), f"seeded error accepted -- {what}: {line}"
+
+
+# Where a seeded error computes the SAME thing on a family, the test that leaves the pair out says so at that place and,
+# where it is cheap, asserts the equality (test_seeded_errors_that_are_equivalent).  The NT-Xent pairs not run: pos_at_rank0 at
+# rank_offset = 0 (that column is the right one); drop_last_tile where 2 b_global % 64 == 0 (no ragged tile); drop_last_split
+# where nsplit == 1 (one slab); no_max where every exp(logit) stays below the float32 maximum e^88 (T >= 0.07, or randn rows
+# at T = 0.01, whose cosines at d = 96 stay below 0.5).
+
+
+def test_seeded_errors_that_are_equivalent():
+    """the pairs the rejection tests leave out give bit-identical float32 results: nothing is hidden by leaving them out"""
+    same = lambda x, y: all(torch.equal(x[k], y[k]) for k in x if torch.is_tensor(x[k]))  # noqa: E731
+    args, _, emul = _nx_case("randn", 33, 1, 0, 96, 0.5)
+    assert same(lc.ntxent(*args, dt=F32, seed_error="pos_at_rank0"), emul)                 # rank_offset = 0
+    args, _, emul = _nx_case("randn", 256, 1, 0, 32, 0.07)
+    assert same(lc.ntxent(*args, dt=F32, seed_error="drop_last_tile"), emul)               # 512 % 64 == 0
+    args, _, emul = _nx_case("randn", 1, 1, 0, 32, 0.5)
+    assert same(lc.ntxent(*args, dt=F32, seed_error="drop_last_split"), emul)              # nsplit == 1
+    x, t = lc.logit_inputs("randn", 7, 5, seed=1), torch.rand(7, 5)
+    assert same(lc.bce_logits(x, t, None, dt=F32, seed_error="pos_weight_by_row"), lc.bce_logits(x, t, None, dt=F32))
+    y = torch.arange(7) % 5
+    for error in ("mean_over_B", "ignored_counted"):                                       # no weights, nothing ignored
+        assert same({"d": lc.cross_entropy(x, y, None, dt=F32, seed_error=error)["dlogits"]}, {"d": lc.cross_entropy(x, y, None, dt=F32)["dlogits"]})
+    z0, z1 = lc.dcl_inputs(3, 32, seed=1)
+    for error in ("weights_differentiated", "weight_one_direction"):                       # DCL: the weights are the constant 1
+        bad, good = lc.dcl(z0, z1, 0.1, None, dt=F32, seed_error=error), lc.dcl(z0, z1, 0.1, None, dt=F32)
+        assert torch.equal(bad["dz0"], good["dz0"]) and torch.equal(bad["terms"], good["terms"])
+    raw = torch.randn(17, 17)
+    assert same(lc.barlow(raw, 0.1, 5e-3, 0.0, dt=F32, seed_error="lambda_on_diagonal"), lc.barlow(raw, 0.1, 5e-3, 0.0, dt=F32))
+    xs = lc.sinkhorn_inputs(1, 7, seed=1)                                                 # B = 1: Q is the row's softmax either way
+    for error in ("samples_first", "one_round_short"):
+        assert torch.equal(lc.sinkhorn(xs, 0.05, 0, dt=F32, seed_error=error), lc.sinkhorn(xs, 0.05, 0, dt=F32))   # iters = 0: no round
+    x0 = torch.zeros(2, 8)
+    assert torch.equal(lc.l2norm(x0, 1e-3, dt=F32, seed_error="eps_added")["y"], lc.l2norm(x0, 1e-3, dt=F32)["y"])   # a zero row: 0 either way
+
+
+@functools.lru_cache(maxsize=None)
+def _nx_case(family, b_local, world, rank, d, temp):
+    z0, z1 = lc.ntxent_inputs(family, b_local * world, d, seed=b_local + d)
+    bg = b_local * world
+    zall = lc.normalized32(torch.cat([z0, z1]))
+    zn = torch.cat([zall[rank * b_local:(rank + 1) * b_local], zall[bg + rank * b_local:bg + (rank + 1) * b_local]]).contiguous()
+    args = (zn, zall, b_local, bg, rank * b_local, temp, 1.0 / (2 * b_local))
+    return args, lc.ntxent(*args, dt=F64), lc.ntxent(*args, dt=F32)
+
+
+def _nx_compare(fn, bad, ref, emul, temp, what):
+    for key, floor in (("lse", lc.ntxent_lse_floor(temp, ref)), ("loss_rows", lc.ntxent_lse_floor(temp, ref)), ("dzn", ref["dzn_floor"])):
+        fn(bad[key], ref[key], emul[key], floor, f"{what} {key}")
+
+
+@pytest.mark.parametrize("family", lc.NTXENT_FAMILIES)
+@pytest.mark.parametrize("b_local,world,rank,d,temp", [(1, 1, 0, 32, 0.5), (33, 1, 0, 96, 0.5), (33, 1, 0, 96, 0.01),
+                                                        (256, 1, 0, 32, 0.07), (37, 3, 2, 32, 0.07)])
+def test_ntxent_reference_is_autograd_and_honest_emulation_passes(family, b_local, world, rank, d, temp):
+    args, ref, emul = _nx_case(family, b_local, world, rank, d, temp)
+    zn, zall, _, bg, off, _, gs = args
+    # the reference against torch: all global rows' cross-entropy on the masked logits, differentiated by autograd in double
+    za = zall.double().requires_grad_(True)
+    t = float(torch.tensor(temp, dtype=F32))
+    s = (za @ za.t() / t).masked_fill(torch.eye(2 * bg, dtype=torch.bool), -float("inf"))
+    pos = torch.cat([torch.arange(bg, 2 * bg), torch.arange(0, bg)])
+    rows_all = F.cross_entropy(s, pos, reduction="none")
+    (rows_all.sum() * float(torch.tensor(gs, dtype=F32))).backward()
+    mine = torch.cat([torch.arange(off, off + b_local), torch.arange(bg + off, bg + off + b_local)])
+    torch.testing.assert_close(ref["loss_rows"], rows_all.detach()[mine], rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(ref["dzn"], za.grad[mine], rtol=1e-10, atol=1e-12 * ref["dzn_floor"] / lc.U)   # (collapsed: the terms cancel to 0)
+    if world == 1 and b_local > 1:
+        # ... and the oracle fed doubles (it normalises once more: float32 unit rows have norm 1 within 2^-23, times 1 / T)
+        want = float(on.ntxent_lightly(zn[:b_local].double(), zn[b_local:].double(), t))
+        assert abs(float(ref["loss_rows"].mean()) - want) <= 4 * 2.0 ** -23 / t + 1e-12
+    if family == "collapsed":
+        assert abs(float(ref["loss_rows"].mean()) - math.log(2 * bg - 1)) < 1e-5
+    _nx_compare(_accept32, _honest(lc.ntxent, *args), ref, emul, temp,
+                f"ntxent {family} b={b_local} T={temp}")
+
+
+NX_ERRORS = [  # (error, tensors it must show in, (family, b_local, world, rank, d, temp))
+    ("self_included", ("lse", "dzn"), ("randn", 33, 1, 0, 96, 0.5)),
+    ("self_included", ("lse", "dzn"), ("offset", 256, 1, 0, 32, 0.07)),
+    ("no_max", ("lse",), ("collapsed", 33, 1, 0, 96, 0.01)),
+    ("no_max", ("lse",), ("duplicates", 256, 1, 0, 32, 0.01)),
+    ("pos_at_rank0", ("loss_rows", "dzn"), ("randn", 37, 3, 2, 32, 0.07)),
+    ("drop_last_tile", ("lse", "dzn"), ("randn", 33, 1, 0, 96, 0.5)),
+    ("drop_last_tile", ("lse", "dzn"), ("collapsed", 1100, 1, 0, 32, 0.5)),
+    ("drop_last_split", ("dzn",), ("randn", 1100, 1, 0, 32, 0.5)),
+    ("drop_last_split", ("dzn",), ("offset", 33, 1, 0, 96, 0.07)),
+    ("lse_row_only", ("dzn",), ("randn", 33, 1, 0, 96, 0.5)),
+    ("lse_row_only", ("dzn",), ("duplicates", 256, 1, 0, 32, 0.01)),
+    ("temp_once", ("dzn",), ("randn", 33, 1, 0, 96, 0.5)),
+    ("temp_once", ("dzn",), ("antipodal", 33, 1, 0, 96, 0.07)),
+]
+
+
+@pytest.mark.parametrize("error,tensors,case", NX_ERRORS)
+def test_ntxent_seeded_errors_fail(error, tensors, case):
+    family, b_local, world, rank, d, temp = case
+    args, ref, emul = _nx_case(*case)
+    bad = lc.ntxent(*args, dt=F32, seed_error=error)
+    floors = {"lse": lc.ntxent_lse_floor(temp, ref), "loss_rows": lc.ntxent_lse_floor(temp, ref), "dzn": ref["dzn_floor"]}
+    for key in tensors:
+        _reject32(bad[key], ref[key], emul[key], floors[key], f"{error} {family} b={b_local} T={temp} {key}")
+
+
+def test_ntxent_launch_arithmetic_mirrors():
+    """the shapes tests/test_gpu_losses.py claims paths with (the issue's table)"""
+    assert lc.nx_fwd_rpw(1024) == 2 and lc.nx_fwd_rpw(1025) == 8
+    assert lc.nx_bwd_plan(1, 1) == (1, 1, 1)
+    assert lc.nx_bwd_plan(256, 256) == (16, 8, 1)
+    assert lc.nx_bwd_plan(1025, 1025) == (65, 3, 11)
+    assert lc.nx_bwd_plan(1100, 1100) == (69, 3, 12) and lc.cdiv(2200, 64) - 2 * 12 == 11 and 2200 % 64 == 24
+    assert lc.nx_bwd_plan(2049, 2049) == (129, 1, 65)
+    assert lc.nx_bwd_lds_bytes(256) == 107648
+    assert lc.grid_blocks(4100 * 65, lc.BCE_CAP) == lc.BCE_CAP and lc.grid_blocks(730 * 730, lc.BARLOW_CAP) == lc.BARLOW_CAP
+    assert lc.grid_blocks(4200 * 250, lc.CENTER_CAP) == lc.CENTER_CAP and lc.grid_blocks(16400, 1 << 30) > lc.VICREG_CAP
+    assert lc.grid_blocks(300 * 3000, lc.SK_WRITE_CAP) == lc.SK_WRITE_CAP
+
+
+@pytest.mark.parametrize("rows,d", [(5, 8), (3, 65), (300, 100)])
+@pytest.mark.parametrize("eps", [1e-12, 1e-3])
+def test_l2norm_reference_and_seeded_error(rows, d, eps):
+    x, dy = lc.l2norm_inputs(rows, d, eps, seed=rows + d)
+    e32 = float(torch.tensor(eps, dtype=F32))
+    xr = x.double().requires_grad_(True)
+    y = F.normalize(xr, dim=1, eps=e32)
+    (y * dy.double()).sum().backward()
+    ref = lc.l2norm(x, eps, dy, scale=1.0, dt=F64)
+    assert float((ref["norm"] / e32 - 1).abs().min()) > 0.4            # no row near the clamp's switch
+    torch.testing.assert_close(ref["y"], y.detach(), rtol=1e-13, atol=0)
+    torch.testing.assert_close(ref["dx"], xr.grad, rtol=1e-10, atol=1e-13 * float(xr.grad.abs().max()))
+    live = ref["norm"] > e32
+    for bf16 in (False, True):
+        emul = lc.l2norm(x, eps, dy, dt=F32, y_bf16=bf16, dx_bf16=bf16)
+        bad = lc.l2norm(x, eps, dy, dt=F32, y_bf16=bf16, dx_bf16=bf16, seed_error="eps_added")
+        if bf16:
+            with kc.jitter(3):
+                got = lc.l2norm(x, eps, dy, dt=F32, y_bf16=True, dx_bf16=True)
+            _accept(got["y"], ref["y"], emul["y"], "l2norm y bf16")
+            _accept(got["dx"][live], ref["dx"][live], emul["dx"][live], "l2norm dx bf16")
+            if eps == 1e-3:
+                _reject(bad["y"], ref["y"], emul["y"], "eps_added y bf16")
+        else:
+            got = _honest(lc.l2norm, x, eps, dy)
+            _accept32(got["y"], ref["y"], emul["y"], lc.f32_floor(ref["y"]), "l2norm y")
+            _accept32(got["dx"][live], ref["dx"][live], emul["dx"][live], lc.mag_floor(ref["dx_terms"][live]), "l2norm dx")
+            if eps == 1e-3:   # (at 1e-12 the added eps is below a float32 rounding of any live norm: equivalent there)
+                _reject32(bad["y"], ref["y"], emul["y"], lc.f32_floor(ref["y"]), "eps_added y")
+                _reject32(bad["inv_norm"][live], ref["inv_norm"][live], emul["inv_norm"][live], lc.f32_floor(ref["inv_norm"][live]),
+                          "eps_added inv_norm")
+
+
+@pytest.mark.parametrize("b,d,k,temp,tie", [(1, 32, 1, 0.1, False), (48, 128, 200, 0.1, True), (5, 100, 63, 0.01, False)])
+def test_bank_loss_reference_and_seeded_error(b, d, k, temp, tie):
+    q, kp, bank = lc.bank_inputs(b, d, k, seed=b + k, key_in_bank=tie)
+    t = float(torch.tensor(temp, dtype=F32))
+    qr, kr = q.double().requires_grad_(True), kp.double().requires_grad_(True)
+    logits = torch.cat([(qr * kr).sum(1, keepdim=True), qr @ bank.double()], 1) / t
+    F.cross_entropy(logits, torch.zeros(b, dtype=torch.long)).backward()
+    ref, emul = lc.bank_loss(q, kp, bank, temp, dt=F64), lc.bank_loss(q, kp, bank, temp, dt=F32)
+    want = float(on.ntxent_memory_bank(q.double(), kp.double(), bank.double(), t))
+    assert abs(float(ref["terms"].sum()) - want) <= 4 * 2.0 ** -23 / t + 1e-12
+    torch.testing.assert_close(ref["dq"], qr.grad, rtol=1e-10, atol=1e-14)
+    torch.testing.assert_close(ref["dk"], kr.grad, rtol=1e-10, atol=1e-14)
+    chain = lc.row_chain(lc.cdiv(k, 256), b)
+    assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain, ref["mags"])
+    bad = lc.bank_loss(q, kp, bank, temp, dt=F32, seed_error="pos_not_in_lse")
+    assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain, ref["mags"])
+    got = _honest(lc.bank_loss, q, kp, bank, temp)
+    for key in ("dq", "dk"):
+        _accept32(got[key], ref[key], emul[key], ref[key + "_floor"], f"bank {key}")
+        _reject32(bad[key], ref[key], emul[key], ref[key + "_floor"], f"pos_not_in_lse {key}")
+
+
+@pytest.mark.parametrize("b,d,zero", [(b, d, z) for b, d in [(1, 1), (37, 63), (37, 2048)]
+                                      for z in [(), ("x0",), ("x1",), ("both",), ("x0", "x1", "both")] if b > 1 or len(z) < 2])
+def test_neg_cosine_reference_and_seeded_error(b, d, zero):
+    """torch clamps each norm in place under no_grad, so for 0 < |x| < eps its gradient treats the norm as unclamped while the
+    kernel differentiates the clamped function; on a ZERO row (the only clamped rows the reference's models can produce, and
+    the ones tested) both give x1 / (eps |x1|).  Rows with a clamped norm hold gradients of size 1 / eps: they are
+    compared apart from the live rows, so that their scale does not hide the others."""
+    x0, x1 = lc.neg_cosine_inputs(b, d, seed=b + d, zero=zero)
+    eps = 1e-8
+    e32 = float(torch.tensor(eps, dtype=F32))
+    ar, br = x0.double().requires_grad_(True), x1.double().requires_grad_(True)
+    (-F.cosine_similarity(ar, br, dim=1, eps=e32).mean()).backward()
+    ref, emul = lc.neg_cosine(x0, x1, eps, dt=F64), lc.neg_cosine(x0, x1, eps, dt=F32)
+    assert lc.neg_cosine_margin(ref, e32) > 0.9
+    torch.testing.assert_close(ref["d0"], ar.grad, rtol=1e-10, atol=1e-14)
+    torch.testing.assert_close(ref["d1"], br.grad, rtol=1e-10, atol=1e-14)
+    live = (ref["l0"] > e32) & (ref["l1"] > e32)
+    bad = lc.neg_cosine(x0, x1, eps, dt=F32, seed_error="eps_on_product")
+    got = _honest(lc.neg_cosine, x0, x1, eps)
+    for rows in (live, ~live):
+        if not bool(rows.any()):
+            continue
+        for key in ("d0", "d1"):
+            _accept32(got[key][rows], ref[key][rows], emul[key][rows], ref["floor"](key, rows), f"-cos {key}")
+    chain = lc.row_chain(lc.cdiv(d, 64), b)
+    assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain)
+    if ("x0" in zero or "x1" in zero) and b > 1:      # one norm clamped, the other not: the product form differs
+        key = "d0" if "x0" in zero else "d1"
+        _reject32(bad[key][~live], ref[key][~live], emul[key][~live], ref["floor"](key, ~live), f"eps_on_product {key}")
+
+
+@pytest.mark.parametrize("b,c", [(1, 1), (70, 9), (5, 65), (33, 1000)])
+@pytest.mark.parametrize("family", ["randn", "offset+1e4", "dominant"])
+def test_cross_entropy_reference_and_seeded_errors(b, c, family):
+    g = torch.Generator().manual_seed(b + c)
+    x = lc.logit_inputs(family, b, c, seed=b * c)
+    labels = torch.randint(0, c, (b,), generator=g)
+    w = torch.rand(c, generator=g) + 0.2
+    w[c // 2] = 0.0
+    if b > 4:
+        labels[1], labels[b - 1] = -100, -100
+    for weight in (None, w):
+        if b == 1 and weight is not None:
+            continue                                        # (C = 1 with its only weight 0: 0 / 0, as torch)
+        xr = x.double().requires_grad_(True)
+        F.cross_entropy(xr, labels, weight=None if weight is None else weight.double()).backward()
+        ref, emul = lc.cross_entropy(x, labels, weight, dt=F64), lc.cross_entropy(x, labels, weight, dt=F32)
+        torch.testing.assert_close(ref["dlogits"], xr.grad, rtol=1e-9, atol=1e-15)
+        _accept32(_honest(lc.cross_entropy, x, labels, weight)["dlogits"], ref["dlogits"], emul["dlogits"], ref["floor"], "CE dlogits")
+        chain = lc.row_chain(0, b)
+        assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain, ref["mags"])
+        if b > 4:
+            bad = lc.cross_entropy(x, labels, weight, dt=F32, seed_error="ignored_counted")
+            _reject32(bad["dlogits"], ref["dlogits"], emul["dlogits"], ref["floor"], "ignored_counted")
+            bad = lc.cross_entropy(x, labels, weight, dt=F32, seed_error="mean_over_B")
+            _reject32(bad["dlogits"], ref["dlogits"], emul["dlogits"], ref["floor"], "mean_over_B")
+            if family != "dominant":   # (a dominant logit on the label leaves a loss of ~0 whatever divides it)
+                assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain, ref["mags"])
+
+
+@pytest.mark.parametrize("b,c", [(70, 8), (7, 5), (4100, 65)])
+@pytest.mark.parametrize("family", ["randn", "saturated"])
+def test_bce_reference_and_seeded_error(b, c, family):
+    g = torch.Generator().manual_seed(b + c)
+    x = lc.logit_inputs(family, b, c, seed=b + c)
+    target = torch.rand(b, c, generator=g)
+    pw = torch.rand(c, generator=g) * 3 + 0.5
+    for pos_weight in (None, pw):
+        xr = x.double().requires_grad_(True)
+        F.binary_cross_entropy_with_logits(xr, target.double(), pos_weight=None if pos_weight is None else pos_weight.double()).backward()
+        ref, emul = lc.bce_logits(x, target, pos_weight, dt=F64), lc.bce_logits(x, target, pos_weight, dt=F32)
+        torch.testing.assert_close(ref["dlogits"], xr.grad, rtol=1e-9, atol=1e-16)
+        floor = ref["floor"]
+        _accept32(_honest(lc.bce_logits, x, target, pos_weight)["dlogits"], ref["dlogits"], emul["dlogits"], floor, "BCE dlogits")
+        chain = lc.grid_chain(b * c, lc.BCE_CAP)
+        assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain, ref["mags"])
+        if pos_weight is not None:
+            bad = lc.bce_logits(x, target, pos_weight, dt=F32, seed_error="pos_weight_by_row")
+            _reject32(bad["dlogits"], ref["dlogits"], emul["dlogits"], floor, f"pos_weight_by_row {b}x{c}")
+            assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain, ref["mags"])
+
+
+@pytest.mark.parametrize("b,d,temp,sigma,dup", [(2, 32, 0.1, 0.5, False), (3, 100, 0.07, 0.05, False), (96, 32, 0.1, 0.5, True),
+                                                 (257, 32, 0.07, 0.5, False)])
+def test_dcl_reference_and_seeded_errors(b, d, temp, sigma, dup):
+    z0, z1 = lc.dcl_inputs(b, d, seed=b + d, duplicates=dup)
+    t, sg = float(torch.tensor(temp, dtype=F32)), float(torch.tensor(sigma, dtype=F32))
+    for s_, s32 in ((None, None), (sigma, sg)):
+        ref, emul = lc.dcl(z0, z1, temp, s_, dt=F64), lc.dcl(z0, z1, temp, s_, dt=F32)
+        got = _honest(lc.dcl, z0, z1, temp, s_)
+        r0, r1 = z0.double().requires_grad_(True), z1.double().requires_grad_(True)
+        want = on.dcl_loss(r0, r1, t, s32)
+        want.backward()
+        # (it normalises once more: float32 unit rows have norm 1 within 2^-23, times 1 / T, and times B in the weights 2 - B softmax)
+        assert abs(float(ref["terms"].sum()) - float(want.detach())) <= 8 * 2.0 ** -23 / t * max(1.0, b * 1.0 if s_ else 1.0) + 1e-12
+        for key, z, r in (("dz0", z0, r0), ("dz1", z1, r1)):
+            # the oracle normalises once more: its gradient is the tangent-space part of ours
+            proj = ref[key] - z.double() * (ref[key] * z.double()).sum(1, keepdim=True)
+            torch.testing.assert_close(proj, r.grad, rtol=1e-5, atol=1e-6 * float(r.grad.abs().max()))
+            _accept32(got[key], ref[key], emul[key], ref[key + "_floor"], f"DCL {key}")
+        chain = lc.row_chain(0, 2 * b)
+        assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain, ref["mags"])
+        errors = ["self_in_negatives"] + (["weights_differentiated", "weight_one_direction"] if s_ else [])
+        for error in errors:
+            bad = lc.dcl(z0, z1, temp, s_, dt=F32, seed_error=error)
+            _reject32(bad["dz0"], ref["dz0"], emul["dz0"], ref["dz0_floor"], f"{error} b={b} dz0")
+            if error != "weights_differentiated":     # (the weights are detached in the VALUE: that error changes the gradient only)
+                assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain, ref["mags"]), error
+
+
+@pytest.mark.parametrize("d", [1, 17, 256])
+@pytest.mark.parametrize("diag_weight", [1.0, 0.0])
+def test_barlow_reference_and_seeded_error(d, diag_weight):
+    g = torch.Generator().manual_seed(d)
+    n = 64
+    raw = (torch.randn(d, d, generator=g) * 8 + torch.eye(d) * n).float()
+    scale, lam = (n - 1) / (n * n), 5e-3
+    rr = raw.double().requires_grad_(True)
+    c = rr * float(torch.tensor(scale, dtype=F32))
+    on_ = (torch.diagonal(c) - 1).pow(2).sum() * diag_weight
+    off = (c.pow(2).sum() - torch.diagonal(c).pow(2).sum()) * float(torch.tensor(lam, dtype=F32))
+    (on_ + off).backward()
+    ref, emul = lc.barlow(raw, scale, lam, diag_weight, dt=F64), lc.barlow(raw, scale, lam, diag_weight, dt=F32)
+    torch.testing.assert_close(ref["draw"], rr.grad, rtol=1e-10, atol=1e-16)
+    assert abs(float(ref["terms"].sum()) - float(on_ + off)) <= 1e-10 * abs(float(on_ + off)) + 1e-14
+    floor = ref["floor"]
+    _accept32(_honest(lc.barlow, raw, scale, lam, diag_weight)["draw"], ref["draw"], emul["draw"], floor, "barlow draw")
+    chain = lc.grid_chain(d * d, lc.BARLOW_CAP)
+    assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain)
+    bad = lc.barlow(raw, scale, lam, diag_weight, dt=F32, seed_error="lambda_on_diagonal")
+    if diag_weight:
+        _reject32(bad["draw"], ref["draw"], emul["draw"], floor, "lambda_on_diagonal draw")
+        assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain)
+
+
+@pytest.mark.parametrize("n,d", [(2, 1), (64, 256), (64, 16400)])
+def test_vicreg_variance_reference_and_seeded_errors(n, d):
+    vb = lc.vicreg_inputs(n, d, seed=d)
+    eps = 1e-4
+    ref, emul = lc.vicreg_variance(vb, n, eps, dt=F64), lc.vicreg_variance(vb, n, eps, dt=F32)
+    assert lc.vicreg_margin(ref) > 0.01
+    # autograd: centred columns with exactly these biased variances
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(n, min(d, 300), generator=g, dtype=F64)
+    x = x - x.mean(0)
+    x = (x / x.pow(2).mean(0).sqrt() * vb[:x.shape[1]].double().sqrt()).requires_grad_(True)
+    sd = torch.sqrt(x.var(dim=0) + float(torch.tensor(eps, dtype=F32)))
+    (torch.relu(1.0 - sd).sum() / d).backward()
+    torch.testing.assert_close(ref["coef"][:x.shape[1]] * x.detach(), x.grad, rtol=1e-9, atol=1e-15)
+    floor = lc.f32_floor(ref["coef"])
+    _accept32(_honest(lc.vicreg_variance, vb, n, eps)["coef"], ref["coef"], emul["coef"], floor, "vicreg coef")
+    chain = lc.grid_chain(d, lc.VICREG_CAP)
+    assert lc.scalar_ok(emul["terms"].double().sum() * ONE_ULP, ref["terms"], emul["terms"], chain)
+    for error in ("biased_variance", "coef_without_hinge"):
+        if n == 2 and d == 1 and error == "coef_without_hinge":
+            continue                                     # the only column has sd 0.5: the hinge is active (EQUIVALENT)
+        bad = lc.vicreg_variance(vb, n, eps, dt=F32, seed_error=error)
+        _reject32(bad["coef"], ref["coef"], emul["coef"], floor, f"{error} coef")
+    bad = lc.vicreg_variance(vb, n, eps, dt=F32, seed_error="biased_variance")
+    assert not lc.scalar_ok(bad["terms"].double().sum(), ref["terms"], emul["terms"], chain)
+    z = kc.bf(torch.randn(n, min(d, 256), generator=torch.Generator().manual_seed(1)) + 3)
+    mean = z.double().mean(0).float()
+    cref, cem = lc.center_columns(z, mean, dt=F64), lc.center_columns(z, mean, dt=F32)
+    with kc.jitter(5):
+        _accept(lc.center_columns(z, mean, dt=F32), cref, cem, "center_columns")
+    _reject(kc.bf(z.double() - mean.double().roll(1)[None, :]) if d > 1 else cem + 1, cref, cem, "centred with the neighbour's mean")
+
+
+@pytest.mark.parametrize("b,k", [(1, 1), (48, 255), (48, 257), (300, 3000)])
+@pytest.mark.parametrize("iters", [0, 1, 3])
+@pytest.mark.parametrize("eps", [0.05, 0.02])
+def test_sinkhorn_reference_and_seeded_errors(b, k, iters, eps):
+    x = lc.sinkhorn_inputs(b, k, seed=b + k)
+    assert float(x.abs().max()) <= 1.0
+    e32 = float(torch.tensor(eps, dtype=F32))
+    ref, emul = lc.sinkhorn(x, eps, iters, dt=F64), lc.sinkhorn(x, eps, iters, dt=F32)
+    assert bool(torch.isfinite(emul).all())
+    torch.testing.assert_close(ref, on.sinkhorn(x.double(), iters, e32), rtol=1e-9, atol=1e-300)
+    if iters > 0:
+        torch.testing.assert_close(ref.sum(1), torch.ones(b, dtype=F64), rtol=1e-12, atol=0)
+    floor = lc.f32_floor(ref)
+    _accept32(_honest(lc.sinkhorn, x, eps, iters), ref, emul, floor, "sinkhorn Q")
+    if iters > 0 and b > 1:     # (B = 1: every round leaves the row's softmax; iters = 0: no round -- equivalent, see above)
+        for error in ("samples_first", "one_round_short"):
+            _reject32(lc.sinkhorn(x, eps, iters, dt=F32, seed_error=error), ref, emul, floor, f"{error} {b}x{k} iters={iters}")
+
+
+@pytest.mark.parametrize("n,d", [(64, 256), (96, 128)])
+def test_barlow_twins_module_reference_and_wiring_error(n, d):
+    a, b = lc.e2e_inputs(n, d, seed=n + d)
+    ar, br = a.double().requires_grad_(True), b.double().requires_grad_(True)
+    want = on.barlow_twins_loss(ar, br)
+    want.backward()
+    ref, emul = lc.barlow_twins_e2e(a, b), lc.barlow_twins_e2e(a, b, emulate=True)
+    # (the reference takes scale, lambda and eps as the float32 values the kernels receive: 2^-24 relative each, squared in places)
+    assert abs(ref["loss"] - float(want.detach())) <= 16 * lc.U * abs(float(want.detach()))
+    torch.testing.assert_close(ref["dz_a"], ar.grad, rtol=0, atol=16 * lc.U * float(ar.grad.abs().max()))
+    torch.testing.assert_close(ref["dz_b"], br.grad, rtol=0, atol=16 * lc.U * float(br.grad.abs().max()))
+    with kc.jitter(7):
+        got = lc.barlow_twins_e2e(a, b, emulate=True)
+    bad = lc.barlow_twins_e2e(a, b, emulate=True, seed_error="scale_1_over_n")
+    assert abs(got["loss"] - ref["loss"]) <= ref["loss_bound"] < abs(bad["loss"] - ref["loss"])
+    assert abs(emul["loss"] - ref["loss"]) <= ref["loss_bound"]
+    for key in ("dz_a", "dz_b"):
+        _accept(got[key], ref[key], emul[key], f"BarlowTwinsLoss {key}")
+        _reject(bad[key], ref[key], emul[key], f"scale_1_over_n {key}")
+
+
+@pytest.mark.parametrize("n,d", [(64, 256), (96, 128)])
+def test_vicreg_module_reference_and_wiring_errors(n, d):
+    a, b = lc.e2e_inputs(n, d, seed=n + d, small_std=True)
+    ar, br = a.double().requires_grad_(True), b.double().requires_grad_(True)
+    want = on.vicreg_loss(ar, br, eps=float(torch.tensor(1e-4, dtype=F32)))
+    want.backward()
+    ref, emul = lc.vicreg_e2e(a, b), lc.vicreg_e2e(a, b, emulate=True)
+    # (the reference takes scale, lambda and eps as the float32 values the kernels receive: 2^-24 relative each, squared in places)
+    assert abs(ref["loss"] - float(want.detach())) <= 16 * lc.U * abs(float(want.detach()))
+    torch.testing.assert_close(ref["dz_a"], ar.grad, rtol=0, atol=16 * lc.U * float(ar.grad.abs().max()))
+    torch.testing.assert_close(ref["dz_b"], br.grad, rtol=0, atol=16 * lc.U * float(br.grad.abs().max()))
+    with kc.jitter(9):
+        got = lc.vicreg_e2e(a, b, emulate=True)
+    assert abs(got["loss"] - ref["loss"]) <= ref["loss_bound"] and abs(emul["loss"] - ref["loss"]) <= ref["loss_bound"]
+    for key in ("dz_a", "dz_b"):
+        _accept(got[key], ref[key], emul[key], f"VICRegLoss {key}")
+    for error in ("cov_scale_n", "mu_not_halved"):
+        bad = lc.vicreg_e2e(a, b, emulate=True, seed_error=error)
+        assert abs(bad["loss"] - ref["loss"]) > ref["loss_bound"], error
+        _reject(bad["dz_a"], ref["dz_a"], emul["dz_a"], f"{error} dz_a")
