@@ -200,8 +200,8 @@ __device__ __forceinline__ float wm_gelu_grad(float v) {
 
 
 // Counter RNG shared with the oracle (oracle/augment.py: rand01): lowbias32 finaliser.  DieNoise (augment.hip) and
-// dropout (evalops.hip) draw from it.
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+// dropout (evalops.hip) draw from it; umap.hip also forms its epoch keys with it on the host.
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352dU;
   x ^= x >> 15;

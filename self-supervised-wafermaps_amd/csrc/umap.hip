@@ -128,6 +128,8 @@
 // v_permlane16/32_swap) -- true xor exchanges, so both partners add the same two numbers and, float addition being
 // commutative, every slot ends with the same bits; log2(EPP) additions.  An epoch without a sampled entry leaves y_i as
 // it is.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -135,6 +137,56 @@ namespace {
 constexpr int UM_THREADS = 256;
 constexpr int UM_MAX_DIM = 64;
 constexpr int UM_MAX_NEG = 64;
+
+// ---- smooth kNN: one thread per row, in double.  FIT: the rows of a fit (rho is subtracted, the row itself weighs 0);
+// otherwise the rows of new points (rho = 0 is not subtracted, there is no self test).
+
+template <bool FIT>
+__device__ __forceinline__ double um_excess(float d, double rho) {
+  if constexpr (FIT) return (double)d - rho;
+  else return (double)d;
+}
+
+// The bisection of the header on the row dr[0 .. k), then the floor; rounded to float32.
+template <bool FIT>
+__device__ __forceinline__ float um_sigma(const float* __restrict__ dr, int k, double rho, double floor_s) {
+  const double target = log2((double)k);
+  double lo = 0.0, hi = INFINITY, mid = 1.0;
+  for (int it = 0; it < 64; ++it) {
+    double psum = 0.0;
+    for (int j = 1; j < k; ++j) {
+      const double d = um_excess<FIT>(dr[j], rho);
+      psum += d > 0.0 ? exp(-d / mid) : 1.0;
+    }
+    if (fabs(psum - target) < 1e-5) break;
+    if (psum > target) {
+      hi = mid;
+      mid = 0.5 * (lo + hi);
+    } else {
+      lo = mid;
+      mid = hi == INFINITY ? 2.0 * mid : 0.5 * (lo + hi);
+    }
+  }
+  if (mid < floor_s) mid = floor_s;
+  return (float)mid;
+}
+
+// The memberships of row i from the rounded sigma; idx_row is read only with FIT.
+template <bool FIT>
+__device__ __forceinline__ void um_weights(const float* __restrict__ dr, const int* __restrict__ idx_row, int i, int k, double rho,
+                                           float sg, float* __restrict__ w_row) {
+  for (int j = 0; j < k; ++j) {
+    const double d = um_excess<FIT>(dr[j], rho);
+    double val;
+    if (FIT && idx_row[j] == i)
+      val = 0.0;
+    else if (d <= 0.0 || sg == 0.f)
+      val = 1.0;
+    else
+      val = exp(-d / (double)sg);
+    w_row[j] = (float)val;
+  }
+}
 
 __global__ __launch_bounds__(UM_THREADS) void umap_smooth_knn_kernel(const float* __restrict__ dist, const int* __restrict__ idx,
                                                                      int n, int k, const double* __restrict__ mean_all,
@@ -150,39 +202,52 @@ __global__ __launch_bounds__(UM_THREADS) void umap_smooth_knn_kernel(const float
     sum += (double)v;
     if (rho_f == 0.f && v > 0.f) rho_f = v;
   }
-  const double rho_d = (double)rho_f, target = log2((double)k);
-  double lo = 0.0, hi = INFINITY, mid = 1.0;
-  for (int it = 0; it < 64; ++it) {
-    double psum = 0.0;
-    for (int j = 1; j < k; ++j) {
-      const double d = (double)dr[j] - rho_d;
-      psum += d > 0.0 ? exp(-d / mid) : 1.0;
-    }
-    if (fabs(psum - target) < 1e-5) break;
-    if (psum > target) {
-      hi = mid;
-      mid = 0.5 * (lo + hi);
-    } else {
-      lo = mid;
-      mid = hi == INFINITY ? 2.0 * mid : 0.5 * (lo + hi);
-    }
-  }
-  const double floor_s = 1e-3 * (rho_f > 0.f ? sum / (double)k : *mean_all);
-  if (mid < floor_s) mid = floor_s;
-  const float sg = (float)mid;
+  const double rho_d = (double)rho_f;
+  const float sg = um_sigma<true>(dr, k, rho_d, 1e-3 * (rho_f > 0.f ? sum / (double)k : *mean_all));
   rho[i] = rho_f;
   sigma[i] = sg;
-  for (int j = 0; j < k; ++j) {
-    const double d = (double)dr[j] - rho_d;
-    double val;
-    if (idx[(size_t)i * k + j] == i)
-      val = 0.0;
-    else if (d <= 0.0 || sg == 0.f)
-      val = 1.0;
-    else
-      val = exp(-d / (double)sg);
-    w[(size_t)i * k + j] = (float)val;
-  }
+  um_weights<true>(dr, idx + (size_t)i * k, i, k, rho_d, sg, w + (size_t)i * k);
+}
+
+__global__ __launch_bounds__(UM_THREADS) void umap_smooth_knn_query_kernel(const float* __restrict__ dist, int m, int k,
+                                                                           const double* __restrict__ mean_all,
+                                                                           float* __restrict__ sigma, float* __restrict__ w) {
+  const int i = blockIdx.x * UM_THREADS + threadIdx.x;
+  if (i >= m) return;
+  const float* dr = dist + (size_t)i * k;
+  const float sg = um_sigma<false>(dr, k, 0.0, 1e-3 * *mean_all);
+  sigma[i] = sg;
+  um_weights<false>(dr, nullptr, i, k, 0.0, sg, w + (size_t)i * k);
+}
+
+// ---- layout and transform layout
+// Both kernels write the attraction and the repulsion of the header out in place.  Shared force-inlined helpers for
+// them (eight shapes tried) gave the same bits, but hipcc then lays the layout kernel's loops out differently and its
+// 50-D epoch at 172 950 vertices took 0.9 - 2.6 % longer (profiles/umap_refactor.md): keep the four copies in step.
+
+// The scalars of a term, which the arguments P of both kernels carry under these names.
+template <class P>
+void um_fill_force(P& p, int dim, int neg_rate, double a, double b, double gamma) {
+  p.dim = dim;
+  p.neg_rate = neg_rate;
+  p.a = (float)a;
+  p.b = (float)b;
+  p.c_att = (float)(-2.0 * a * b);
+  p.c_rep = (float)(2.0 * gamma * b);
+}
+
+__device__ __forceinline__ float um_clip(float v) { return fminf(4.f, fmaxf(-4.f, v)); }
+
+// The padded dimension DP of `dim` (1, 2, 4, ..., 64) picks the instantiation: fn(std::integral_constant<int, DP>).
+template <class F>
+void um_with_dp(int dim, F&& fn) {
+  if (dim == 1) fn(std::integral_constant<int, 1>{});
+  else if (dim == 2) fn(std::integral_constant<int, 2>{});
+  else if (dim <= 4) fn(std::integral_constant<int, 4>{});
+  else if (dim <= 8) fn(std::integral_constant<int, 8>{});
+  else if (dim <= 16) fn(std::integral_constant<int, 16>{});
+  else if (dim <= 32) fn(std::integral_constant<int, 32>{});
+  else fn(std::integral_constant<int, 64>{});
 }
 
 struct UmLayoutArgs {
@@ -200,8 +265,6 @@ struct UmLayoutArgs {
   const float* scale;   // s = dens_lambda mu_tot / (std n), on the device
   float ab, omb;        // float32(a b), float32(1 - b)
 };
-
-__device__ __forceinline__ float um_clip(float v) { return fminf(4.f, fmaxf(-4.f, v)); }
 
 // DENS = false is the plain UMAP epoch; DENS = true adds the density term of a DensMAP phase epoch to every sampled entry.
 template <int DP, bool DENS>
@@ -271,24 +334,6 @@ __global__ __launch_bounds__(UM_THREADS) void umap_layout_kernel(const UmLayoutA
     for (int q = 0; q < EPP; ++q) s += red[wave * 64 + q * DP + c];
     p.y_out[(size_t)i * p.dim + c] = yi + p.alpha * s;
   }
-}
-
-template <int DP, bool DENS>
-void um_launch(const UmLayoutArgs& a, hipStream_t st) {
-  umap_layout_kernel<DP, DENS><<<wm_cdiv(a.n, UM_THREADS / 64), UM_THREADS, 0, st>>>(a);
-}
-
-// One epoch: the padded dimension picks the instantiation.
-template <bool DENS>
-void um_epoch(const UmLayoutArgs& p, hipStream_t st) {
-  const int dim = p.dim;
-  if (dim == 1) um_launch<1, DENS>(p, st);
-  else if (dim == 2) um_launch<2, DENS>(p, st);
-  else if (dim <= 4) um_launch<4, DENS>(p, st);
-  else if (dim <= 8) um_launch<8, DENS>(p, st);
-  else if (dim <= 16) um_launch<16, DENS>(p, st);
-  else if (dim <= 32) um_launch<32, DENS>(p, st);
-  else um_launch<64, DENS>(p, st);
 }
 
 // ---- DensMAP: radii, statistics, per-vertex terms
@@ -478,17 +523,10 @@ __global__ __launch_bounds__(DM_THREADS) void densmap_terms_kernel(const double*
 
 void dm_radii_launch(const float* y, const int* indptr, const int* indices, const uint32_t* q, int n, int dim, double a, double b,
                      int n_epochs, double* re_d, double* d_d, double* ratio_d, float* re_f, float* d_f, hipStream_t st) {
-  const int grid = wm_cdiv(n, UM_THREADS / 64);
-#define DM_RADII(DP) \
-  densmap_radii_kernel<DP><<<grid, UM_THREADS, 0, st>>>(y, indptr, indices, q, n, dim, a, b, (uint32_t)n_epochs, re_d, d_d, ratio_d, re_f, d_f)
-  if (dim == 1) DM_RADII(1);
-  else if (dim == 2) DM_RADII(2);
-  else if (dim <= 4) DM_RADII(4);
-  else if (dim <= 8) DM_RADII(8);
-  else if (dim <= 16) DM_RADII(16);
-  else if (dim <= 32) DM_RADII(32);
-  else DM_RADII(64);
-#undef DM_RADII
+  um_with_dp(dim, [&](auto dp) {
+    densmap_radii_kernel<decltype(dp)::value><<<wm_cdiv(n, UM_THREADS / 64), UM_THREADS, 0, st>>>(
+        y, indptr, indices, q, n, dim, a, b, (uint32_t)n_epochs, re_d, d_d, ratio_d, re_f, d_f);
+  });
 }
 
 inline int dm_blocks(long long count) {
@@ -541,41 +579,6 @@ __global__ __launch_bounds__(UM_THREADS) void umap_label_intersect_kernel(const 
     const double mj = ws[j];
     const double mt = (lo < end && indices[lo] == i && mj > 0.0) ? ((double)data[lo] * f) / mj : 0.0;
     out[e] = (float)((me + mt) - me * mt);
-  }
-}
-
-// ---- memberships of new rows: one thread per row, in double
-
-__global__ __launch_bounds__(UM_THREADS) void umap_smooth_knn_query_kernel(const float* __restrict__ dist, int m, int k,
-                                                                           const double* __restrict__ mean_all,
-                                                                           float* __restrict__ sigma, float* __restrict__ w) {
-  const int i = blockIdx.x * UM_THREADS + threadIdx.x;
-  if (i >= m) return;
-  const float* dr = dist + (size_t)i * k;
-  const double target = log2((double)k);
-  double lo = 0.0, hi = INFINITY, mid = 1.0;
-  for (int it = 0; it < 64; ++it) {
-    double psum = 0.0;
-    for (int j = 1; j < k; ++j) {
-      const double d = (double)dr[j];
-      psum += d > 0.0 ? exp(-d / mid) : 1.0;
-    }
-    if (fabs(psum - target) < 1e-5) break;
-    if (psum > target) {
-      hi = mid;
-      mid = 0.5 * (lo + hi);
-    } else {
-      lo = mid;
-      mid = hi == INFINITY ? 2.0 * mid : 0.5 * (lo + hi);
-    }
-  }
-  const double floor_s = 1e-3 * *mean_all;
-  if (mid < floor_s) mid = floor_s;
-  const float sg = (float)mid;
-  sigma[i] = sg;
-  for (int j = 0; j < k; ++j) {
-    const double d = (double)dr[j];
-    w[(size_t)i * k + j] = (float)((d <= 0.0 || sg == 0.f) ? 1.0 : exp(-d / (double)sg));
   }
 }
 
@@ -665,13 +668,92 @@ __global__ __launch_bounds__(UM_THREADS) void umap_transform_kernel(const UmTran
   if (es == 0 && comp) p.y_out[(size_t)i * p.dim + c] = yi;
 }
 
-inline uint32_t um_mix_host(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
+// ---- host: what the three layout entry points share
+
+// Their requirements on the shared arguments.
+int um_check_layout(int dim, double a, double b, double gamma, double learning_rate, int epoch_begin, int epoch_end, int n_epochs,
+                    int neg_rate) {
+  WM_REQUIRE(dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end && epoch_end <= n_epochs, WM_EINVAL);
+  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
+  WM_REQUIRE(dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG, WM_EUNSUPPORTED);
+  return WM_OK;
+}
+
+// What wm_densmap_layout adds to wm_umap_layout.
+struct UmDensity {
+  const float* data;
+  const float* rad;
+  int nnz;
+  double lambda, frac, var_shift;
+  char* ws;  // the workspace of the header
+};
+
+// Epochs [epoch_begin, epoch_end) of the layout, double-buffered between y_a and y_b; with `dens`, the epochs of its phase
+// first compute the radii, their statistics and the per-vertex terms, and run the kernel with the density term.
+int um_run_epochs(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n, int dim, double a,
+                  double b, double gamma, double learning_rate, uint32_t seed, int epoch_begin, int epoch_end, int n_epochs,
+                  int neg_rate, const UmDensity* dens, int* result_buffer, hipStream_t st) {
+  UmLayoutArgs p = {};
+  p.indptr = indptr;
+  p.indices = indices;
+  p.q = q;
+  p.n = n;
+  um_fill_force(p, dim, neg_rate, a, b, gamma);
+  double *scal = nullptr, *slots = nullptr, *re_d = nullptr, *d_d = nullptr, *ratio_d = nullptr;
+  float4* vert = nullptr;
+  if (dens) {
+    scal = reinterpret_cast<double*>(dens->ws);
+    slots = reinterpret_cast<double*>(dens->ws + 64);
+    vert = reinterpret_cast<float4*>(dens->ws + DM_HEAD);
+    re_d = reinterpret_cast<double*>(dens->ws + DM_HEAD + (size_t)n * sizeof(float4));
+    d_d = re_d + n;
+    ratio_d = d_d + n;
+    p.data = dens->data;
+    p.vert = vert;
+    p.scale = reinterpret_cast<const float*>(scal + 5);
+    p.ab = (float)(a * b);
+    p.omb = (float)(1.0 - b);
+  }
+  const int grid = wm_cdiv(n, UM_THREADS / 64);
+  const int nb_vertex = dm_blocks(n);
+  int nb_entry = 0;  // (mu_tot is summed before the call's first phase epoch)
+  float* cur = y_a;
+  float* nxt = y_b;
+  for (int ep = epoch_begin; ep < epoch_end; ++ep) {
+    p.y = cur;
+    p.y_out = nxt;
+    p.ep = (uint32_t)ep;
+    p.ep_key = lowbias32(seed ^ ((uint32_t)ep * 0x9e3779b9U));
+    p.alpha = (float)(learning_rate * (1.0 - (double)ep / (double)n_epochs));
+    const bool phase = dens && dens->lambda > 0.0 && (double)(ep + 1) / (double)n_epochs > 1.0 - dens->frac;
+    if (phase) {
+      if (nb_entry == 0) {
+        nb_entry = dm_blocks(dens->nnz);
+        densmap_mu_kernel<<<nb_entry, DM_THREADS, 0, st>>>(dens->data, q, (long long)dens->nnz, (uint32_t)n_epochs, slots);
+        WM_LAUNCH_CHECK();
+      }
+      dm_radii_launch(cur, indptr, indices, q, n, dim, a, b, n_epochs, re_d, d_d, ratio_d, nullptr, nullptr, st);
+      WM_LAUNCH_CHECK();
+      densmap_sum1_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, n, slots);
+      WM_LAUNCH_CHECK();
+      densmap_sum2_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, dens->rad, n, slots);
+      WM_LAUNCH_CHECK();
+      densmap_terms_kernel<<<wm_cdiv(n, DM_THREADS), DM_THREADS, 0, st>>>(re_d, d_d, ratio_d, dens->rad, n, nb_vertex, nb_entry,
+                                                                         dens->lambda, dens->var_shift, slots, vert, scal);
+      WM_LAUNCH_CHECK();
+    }
+    um_with_dp(dim, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      if (phase) umap_layout_kernel<DP, true><<<grid, UM_THREADS, 0, st>>>(p);
+      else umap_layout_kernel<DP, false><<<grid, UM_THREADS, 0, st>>>(p);
+    });
+    WM_LAUNCH_CHECK();
+    float* sw = cur;
+    cur = nxt;
+    nxt = sw;
+  }
+  *result_buffer = cur == y_a ? 0 : 1;
+  return WM_OK;
 }
 
 }  // namespace
@@ -690,39 +772,11 @@ extern "C" int wm_umap_smooth_knn(const float* dist, const int32_t* idx, int n, 
 extern "C" int wm_umap_layout(float* y_a, float* y_b, const int32_t* indptr, const int32_t* indices, const uint32_t* q, int n,
                               int dim, double a, double b, double gamma, double learning_rate, uint32_t seed, int epoch_begin,
                               int epoch_end, int n_epochs, int neg_rate, int* result_buffer, void* stream) {
-  WM_REQUIRE(y_a && y_b && y_a != y_b && indptr && indices && q && result_buffer, WM_EINVAL);
-  WM_REQUIRE(n > 0 && dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end && epoch_end <= n_epochs,
-             WM_EINVAL);
-  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
-  WM_REQUIRE(dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG && n <= (1 << 24), WM_EUNSUPPORTED);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  UmLayoutArgs p = {};
-  p.indptr = indptr;
-  p.indices = indices;
-  p.q = q;
-  p.n = n;
-  p.dim = dim;
-  p.neg_rate = neg_rate;
-  p.a = (float)a;
-  p.b = (float)b;
-  p.c_att = (float)(-2.0 * a * b);
-  p.c_rep = (float)(2.0 * gamma * b);
-  float* cur = y_a;
-  float* nxt = y_b;
-  for (int ep = epoch_begin; ep < epoch_end; ++ep) {
-    p.y = cur;
-    p.y_out = nxt;
-    p.ep = (uint32_t)ep;
-    p.ep_key = um_mix_host(seed ^ ((uint32_t)ep * 0x9e3779b9U));
-    p.alpha = (float)(learning_rate * (1.0 - (double)ep / (double)n_epochs));
-    um_epoch<false>(p, st);
-    WM_LAUNCH_CHECK();
-    float* sw = cur;
-    cur = nxt;
-    nxt = sw;
-  }
-  *result_buffer = cur == y_a ? 0 : 1;
-  return WM_OK;
+  WM_REQUIRE(y_a && y_b && y_a != y_b && indptr && indices && q && result_buffer && n > 0, WM_EINVAL);
+  if (const int rc = um_check_layout(dim, a, b, gamma, learning_rate, epoch_begin, epoch_end, n_epochs, neg_rate)) return rc;
+  WM_REQUIRE(n <= (1 << 24), WM_EUNSUPPORTED);
+  return um_run_epochs(y_a, y_b, indptr, indices, q, n, dim, a, b, gamma, learning_rate, seed, epoch_begin, epoch_end, n_epochs,
+                       neg_rate, nullptr, result_buffer, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int wm_densmap_graph_radii(const int32_t* indptr, const float* data, const float* dists, const uint32_t* q, int n,
@@ -757,74 +811,15 @@ extern "C" int wm_densmap_layout(float* y_a, float* y_b, const int32_t* indptr, 
                                  int epoch_begin, int epoch_end, int n_epochs, int neg_rate, void* workspace,
                                  size_t workspace_bytes, int* result_buffer, void* stream) {
   WM_REQUIRE(y_a && y_b && y_a != y_b && indptr && indices && q && data && rad && workspace && result_buffer, WM_EINVAL);
-  WM_REQUIRE(n > 1 && nnz >= 0 && dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end && epoch_end <= n_epochs,
-             WM_EINVAL);
-  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
+  WM_REQUIRE(n > 1 && nnz >= 0, WM_EINVAL);
   WM_REQUIRE(dens_lambda >= 0.0 && dens_frac >= 0.0 && dens_frac <= 1.0 && dens_var_shift >= 0.0, WM_EINVAL);
-  WM_REQUIRE(dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG && n <= (1 << 24), WM_EUNSUPPORTED);
+  if (const int rc = um_check_layout(dim, a, b, gamma, learning_rate, epoch_begin, epoch_end, n_epochs, neg_rate)) return rc;
+  WM_REQUIRE(n <= (1 << 24), WM_EUNSUPPORTED);
   WM_REQUIRE(workspace_bytes >= wm_densmap_layout_workspace_bytes(n), WM_EWORKSPACE);
   WM_REQUIRE(((uintptr_t)workspace & 15u) == 0, WM_EALIGN);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
-  double* scal = reinterpret_cast<double*>(ws);
-  double* slots = reinterpret_cast<double*>(ws + 64);
-  float4* vert = reinterpret_cast<float4*>(ws + DM_HEAD);
-  double* re_d = reinterpret_cast<double*>(ws + DM_HEAD + (size_t)n * sizeof(float4));
-  double* d_d = re_d + n;
-  double* ratio_d = d_d + n;
-  UmLayoutArgs p = {};
-  p.indptr = indptr;
-  p.indices = indices;
-  p.q = q;
-  p.n = n;
-  p.dim = dim;
-  p.neg_rate = neg_rate;
-  p.a = (float)a;
-  p.b = (float)b;
-  p.c_att = (float)(-2.0 * a * b);
-  p.c_rep = (float)(2.0 * gamma * b);
-  p.data = data;
-  p.vert = vert;
-  p.scale = reinterpret_cast<const float*>(scal + 5);
-  p.ab = (float)(a * b);
-  p.omb = (float)(1.0 - b);
-  const int nb_vertex = dm_blocks(n);
-  int nb_entry = 0;  // (mu_tot is summed before the call's first phase epoch)
-  float* cur = y_a;
-  float* nxt = y_b;
-  for (int ep = epoch_begin; ep < epoch_end; ++ep) {
-    p.y = cur;
-    p.y_out = nxt;
-    p.ep = (uint32_t)ep;
-    p.ep_key = um_mix_host(seed ^ ((uint32_t)ep * 0x9e3779b9U));
-    p.alpha = (float)(learning_rate * (1.0 - (double)ep / (double)n_epochs));
-    const bool phase = dens_lambda > 0.0 && (double)(ep + 1) / (double)n_epochs > 1.0 - dens_frac;
-    if (phase) {
-      if (nb_entry == 0) {
-        nb_entry = dm_blocks(nnz);
-        densmap_mu_kernel<<<nb_entry, DM_THREADS, 0, st>>>(data, q, (long long)nnz, (uint32_t)n_epochs, slots);
-        WM_LAUNCH_CHECK();
-      }
-      dm_radii_launch(cur, indptr, indices, q, n, dim, a, b, n_epochs, re_d, d_d, ratio_d, nullptr, nullptr, st);
-      WM_LAUNCH_CHECK();
-      densmap_sum1_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, n, slots);
-      WM_LAUNCH_CHECK();
-      densmap_sum2_kernel<<<nb_vertex, DM_THREADS, 0, st>>>(re_d, rad, n, slots);
-      WM_LAUNCH_CHECK();
-      densmap_terms_kernel<<<wm_cdiv(n, DM_THREADS), DM_THREADS, 0, st>>>(re_d, d_d, ratio_d, rad, n, nb_vertex, nb_entry,
-                                                                         dens_lambda, dens_var_shift, slots, vert, scal);
-      WM_LAUNCH_CHECK();
-      um_epoch<true>(p, st);
-    } else {
-      um_epoch<false>(p, st);
-    }
-    WM_LAUNCH_CHECK();
-    float* sw = cur;
-    cur = nxt;
-    nxt = sw;
-  }
-  *result_buffer = cur == y_a ? 0 : 1;
-  return WM_OK;
+  const UmDensity dens = {data, rad, nnz, dens_lambda, dens_frac, dens_var_shift, static_cast<char*>(workspace)};
+  return um_run_epochs(y_a, y_b, indptr, indices, q, n, dim, a, b, gamma, learning_rate, seed, epoch_begin, epoch_end, n_epochs,
+                       neg_rate, &dens, result_buffer, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int wm_umap_label_intersect(const int32_t* indptr, const int32_t* indices, const float* data, const int32_t* labels,
@@ -858,11 +853,9 @@ extern "C" int wm_umap_transform_layout(const float* y_in, float* y_out, const f
                                         double learning_rate, uint32_t seed, int epoch_begin, int epoch_end, int n_epochs,
                                         int neg_rate, void* stream) {
   WM_REQUIRE(y_in && y_out && y_train && idx && q && y_out != y_train, WM_EINVAL);
-  WM_REQUIRE(m > 0 && n > 0 && k > 0 && dim > 0 && n_epochs > 0 && epoch_begin >= 0 && epoch_begin <= epoch_end &&
-                 epoch_end <= n_epochs,
-             WM_EINVAL);
-  WM_REQUIRE(a > 0.0 && b > 0.0 && gamma >= 0.0 && learning_rate >= 0.0 && neg_rate >= 0, WM_EINVAL);
-  WM_REQUIRE(k <= 64 && dim <= UM_MAX_DIM && neg_rate <= UM_MAX_NEG && m <= (1 << 24) && n <= (1 << 24), WM_EUNSUPPORTED);
+  WM_REQUIRE(m > 0 && n > 0 && k > 0, WM_EINVAL);
+  if (const int rc = um_check_layout(dim, a, b, gamma, learning_rate, epoch_begin, epoch_end, n_epochs, neg_rate)) return rc;
+  WM_REQUIRE(k <= 64 && m <= (1 << 24) && n <= (1 << 24), WM_EUNSUPPORTED);
   UmTransformArgs p = {};
   p.y_in = y_in;
   p.y_out = y_out;
@@ -872,28 +865,16 @@ extern "C" int wm_umap_transform_layout(const float* y_in, float* y_out, const f
   p.m = m;
   p.n = n;
   p.k = k;
-  p.dim = dim;
-  p.neg_rate = neg_rate;
+  um_fill_force(p, dim, neg_rate, a, b, gamma);
   p.seed = seed;
   p.ep_begin = epoch_begin;
   p.ep_end = epoch_end;
   p.lr4 = learning_rate / 4.0;
   p.n_epochs = (double)n_epochs;
-  p.a = (float)a;
-  p.b = (float)b;
-  p.c_att = (float)(-2.0 * a * b);
-  p.c_rep = (float)(2.0 * gamma * b);
-  const int grid = wm_cdiv(m, UM_THREADS / 64);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define UM_TRANSFORM(DP) umap_transform_kernel<DP><<<grid, UM_THREADS, 0, st>>>(p)
-  if (dim == 1) UM_TRANSFORM(1);
-  else if (dim == 2) UM_TRANSFORM(2);
-  else if (dim <= 4) UM_TRANSFORM(4);
-  else if (dim <= 8) UM_TRANSFORM(8);
-  else if (dim <= 16) UM_TRANSFORM(16);
-  else if (dim <= 32) UM_TRANSFORM(32);
-  else UM_TRANSFORM(64);
-#undef UM_TRANSFORM
+  um_with_dp(dim, [&](auto dp) {
+    umap_transform_kernel<decltype(dp)::value><<<wm_cdiv(m, UM_THREADS / 64), UM_THREADS, 0, st>>>(p);
+  });
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

@@ -46,6 +46,7 @@ Only local_connectivity = 1 and set_op_mix_ratio = 1 are supported.
 """
 from __future__ import annotations
 
+import ctypes
 import warnings
 from typing import NamedTuple, Optional, Tuple
 
@@ -463,10 +464,7 @@ def label_intersect(graph: CSR, labels, far_dist: float, unknown_dist: float = 1
         raise ValueError(f"labels int32 [{n}] expected")
     if n < 1 or not (far_dist >= 0 and unknown_dist >= 0):
         raise ValueError("a graph of at least one vertex and far_dist, unknown_dist >= 0 expected")
-    # the kernel trusts the graph: check once here that no entry points outside it
-    ip = graph.indptr.long()
-    if int(ip[0]) != 0 or int(ip[-1]) != graph.indices.numel() or bool((ip[1:] < ip[:-1]).any()):
-        raise ValueError("indptr must rise from 0 to nnz")
+    _check_csr(graph.indptr, graph.indices.numel())
     if graph.indices.numel() and (int(graph.indices.min()) < 0 or int(graph.indices.max()) >= n):
         raise ValueError("indices must lie in [0, n)")
     out = torch.empty_like(graph.data)
@@ -488,6 +486,21 @@ def sample_rates(data):
     return torch.round(65536.0 * w / w.max()).to(torch.int32).contiguous()
 
 
+def _check_csr(indptr, nnz: int):
+    """The kernels trust a graph's row pointers: check once on the host that they rise from 0 to nnz."""
+    ip = indptr.long()
+    if int(ip[0]) != 0 or int(ip[-1]) != nnz or bool((ip[1:] < ip[:-1]).any()):
+        raise ValueError("indptr must rise from 0 to nnz")
+
+
+def _check_schedule(a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate, negative_sample_rate):
+    """The epoch range and the parameters of a layout call, as the three layout entry points of csrc/umap.hip require them."""
+    if not 0 <= epoch_begin <= epoch_end <= n_epochs or n_epochs < 1:
+        raise ValueError("0 <= epoch_begin <= epoch_end <= n_epochs expected")
+    if not (a > 0 and b > 0 and gamma >= 0 and learning_rate >= 0 and 0 <= int(negative_sample_rate) <= 64):
+        raise ValueError("a, b > 0, gamma, learning_rate >= 0 and 0 <= negative_sample_rate <= 64 expected")
+
+
 def _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate,
                        negative_sample_rate):
     """The validation `optimize_layout` and `optimize_layout_densmap` share; returns (n, dim)."""
@@ -502,17 +515,22 @@ def _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch
         raise ValueError("indptr, indices and q must be int32")
     if indptr.shape != (n + 1,) or q.shape != indices.shape or indices.dim() != 1:
         raise ValueError("indptr [n + 1], indices [nnz] and q [nnz] expected")
-    # the kernel trusts the graph: check once here that no entry points outside y
-    ip = indptr.long()
-    if int(ip[0]) != 0 or int(ip[-1]) != indices.numel() or bool((ip[1:] < ip[:-1]).any()):
-        raise ValueError("indptr must rise from 0 to nnz")
+    _check_csr(indptr, indices.numel())
     if indices.numel() and (int(indices.min()) < 0 or int(indices.max()) >= n or int(q.min()) < 0 or int(q.max()) > 65536):
         raise ValueError("indices must lie in [0, n) and q in [0, 65536]")
-    if not 0 <= epoch_begin <= epoch_end <= n_epochs or n_epochs < 1:
-        raise ValueError("0 <= epoch_begin <= epoch_end <= n_epochs expected")
-    if not (a > 0 and b > 0 and gamma >= 0 and learning_rate >= 0 and 0 <= int(negative_sample_rate) <= 64):
-        raise ValueError("a, b > 0, gamma, learning_rate >= 0 and 0 <= negative_sample_rate <= 64 expected")
+    _check_schedule(a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate, negative_sample_rate)
     return n, dim
+
+
+def _double_buffered(name: str, y, call):
+    """The layout entry point `name` run as `call(buf_a, buf_b, result)` on a copy of y and a second buffer; returns the
+    buffer that the int at `result` names as the one holding the new positions."""
+    import torch
+
+    bufs = (y.clone(), torch.empty_like(y))
+    which = ctypes.c_int(0)
+    check(call(ptr(bufs[0]), ptr(bufs[1]), ctypes.addressof(which)), name)
+    return bufs[which.value]
 
 
 def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
@@ -521,21 +539,13 @@ def optimize_layout(y, indptr, indices, q, a: float, b: float, n_epochs: int, ep
     """Epochs [epoch_begin, epoch_end) of `n_epochs` of the layout optimisation (csrc/umap.hip) from the positions
     y float32 [n, dim] over the symmetric CSR graph (indptr, indices int32) with sampling rates q (`sample_rates`).
     Returns the new positions; y is left unchanged.  Splitting the epoch range over several calls changes no bit."""
-    import ctypes
-
-    import torch
-
     require_gpu(y, indptr, indices, q)
     epoch_end = n_epochs if epoch_end is None else epoch_end
     n, dim = _check_layout_args(y, indptr, indices, q, a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate,
                                 negative_sample_rate)
-    bufs = (y.clone(), torch.empty_like(y))
-    which = ctypes.c_int(0)
-    check(_lib.load().wm_umap_layout(ptr(bufs[0]), ptr(bufs[1]), ptr(indptr), ptr(indices), ptr(q), n, dim, float(a), float(b),
-                                     float(gamma), float(learning_rate), int(seed) & _MASK32, int(epoch_begin), int(epoch_end),
-                                     int(n_epochs), int(negative_sample_rate), ctypes.addressof(which), stream_ptr()),
-          "wm_umap_layout")
-    return bufs[which.value]
+    return _double_buffered("wm_umap_layout", y, lambda buf_a, buf_b, result: _lib.load().wm_umap_layout(
+        buf_a, buf_b, ptr(indptr), ptr(indices), ptr(q), n, dim, float(a), float(b), float(gamma), float(learning_rate),
+        int(seed) & _MASK32, int(epoch_begin), int(epoch_end), int(n_epochs), int(negative_sample_rate), result, stream_ptr()))
 
 
 def optimize_transform(y_new, y_train, idx, q, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
@@ -564,10 +574,7 @@ def optimize_transform(y_new, y_train, idx, q, a: float, b: float, n_epochs: int
     # the kernel trusts the entries: check once here that none points outside y_train
     if int(idx.min()) < 0 or int(idx.max()) >= n or int(q.min()) < 0 or int(q.max()) > 65536:
         raise ValueError("idx must lie in [0, n) and q in [0, 65536]")
-    if not 0 <= epoch_begin <= epoch_end <= n_epochs or n_epochs < 1:
-        raise ValueError("0 <= epoch_begin <= epoch_end <= n_epochs expected")
-    if not (a > 0 and b > 0 and gamma >= 0 and learning_rate >= 0 and 0 <= int(negative_sample_rate) <= 64):
-        raise ValueError("a, b > 0, gamma, learning_rate >= 0 and 0 <= negative_sample_rate <= 64 expected")
+    _check_schedule(a, b, n_epochs, epoch_begin, epoch_end, gamma, learning_rate, negative_sample_rate)
     out = torch.empty_like(y_new)
     check(_lib.load().wm_umap_transform_layout(ptr(y_new), ptr(out), ptr(y_train), ptr(idx), ptr(q), m, n, k, dim, float(a),
                                                float(b), float(gamma), float(learning_rate), int(seed) & _MASK32,
@@ -594,9 +601,7 @@ def graph_radii(indptr, data, dists, q, n_epochs: int):
         raise ValueError("indptr, q int32 and data, dists float32 expected")
     if indptr.dim() != 1 or indptr.numel() < 2 or data.dim() != 1 or dists.shape != data.shape or q.shape != data.shape:
         raise ValueError("indptr [n + 1] and data, dists, q [nnz] expected")
-    ip = indptr.long()
-    if int(ip[0]) != 0 or int(ip[-1]) != data.numel() or bool((ip[1:] < ip[:-1]).any()):
-        raise ValueError("indptr must rise from 0 to nnz")
+    _check_csr(indptr, data.numel())
     if int(n_epochs) < 1:
         raise ValueError("n_epochs must be positive")
     n = indptr.numel() - 1
@@ -649,6 +654,12 @@ class DensityTerms(NamedTuple):
     std: float
 
 
+# Where wm_densmap_layout leaves them in its workspace (csrc/umap.hip, "Workspace of wm_densmap_layout"), in bytes:
+_WS_SCALARS = 0  # float64 mu_tot, mean, var, cov, std
+_WS_SCALE = 40  # float32 s
+_WS_VERTEX = 64 + 4 * 128 * 8  # float32 [n][4], behind the scalars and the four rows of 128 float64 slots
+
+
 def optimize_layout_densmap(y, indptr, indices, q, data, R, a: float, b: float, n_epochs: int, epoch_begin: int = 0,
                             epoch_end: Optional[int] = None, gamma: float = 1.0, learning_rate: float = 1.0, seed: int = 0,
                             negative_sample_rate: int = 5, dens_lambda: float = 2.0, dens_frac: float = 0.3,
@@ -658,8 +669,6 @@ def optimize_layout_densmap(y, indptr, indices, q, data, R, a: float, b: float, 
     `standardize_radii`).  Epochs outside the phase, and every epoch when dens_lambda = 0, are `optimize_layout`'s bit for
     bit; splitting the epoch range over several calls changes no bit.  With `return_terms` the result is
     (positions, DensityTerms or None when the call ran no phase epoch)."""
-    import ctypes
-
     import torch
 
     require_gpu(y, indptr, indices, q, data, R)
@@ -682,24 +691,19 @@ def optimize_layout_densmap(y, indptr, indices, q, data, R, a: float, b: float, 
     if need == 0:
         raise ValueError(f"optimize_layout_densmap: unsupported n = {n}")
     ws = torch.zeros(need, dtype=torch.uint8, device=y.device)
-    bufs = (y.clone(), torch.empty_like(y))
-    which = ctypes.c_int(0)
-    check(lib.wm_densmap_layout(ptr(bufs[0]), ptr(bufs[1]), ptr(indptr), ptr(indices), ptr(q), ptr(data.contiguous()),
-                                ptr(R.contiguous()), n, int(indices.numel()), dim, float(a), float(b), float(gamma),
-                                float(learning_rate), float(dens_lambda), float(dens_frac), float(dens_var_shift),
-                                int(seed) & _MASK32, int(epoch_begin), int(epoch_end), int(n_epochs), int(negative_sample_rate),
-                                ptr(ws), need, ctypes.addressof(which), stream_ptr()), "wm_densmap_layout")
-    out = bufs[which.value]
+    out = _double_buffered("wm_densmap_layout", y, lambda buf_a, buf_b, result: lib.wm_densmap_layout(
+        buf_a, buf_b, ptr(indptr), ptr(indices), ptr(q), ptr(data.contiguous()), ptr(R.contiguous()), n, int(indices.numel()), dim,
+        float(a), float(b), float(gamma), float(learning_rate), float(dens_lambda), float(dens_frac), float(dens_var_shift),
+        int(seed) & _MASK32, int(epoch_begin), int(epoch_end), int(n_epochs), int(negative_sample_rate), ptr(ws), need, result,
+        stream_ptr()))
     if not return_terms:
         return out
     if not any(in_density_phase(ep, n_epochs, dens_lambda, dens_frac) for ep in range(epoch_begin, epoch_end)):
         return out, None
-    head = 64 + 4 * 128 * 8  # (csrc/umap.hip: the workspace layout)
-    vert = ws[head:head + 16 * n].view(torch.float32).view(n, 4)
-    scal = ws[:40].view(torch.float64).cpu().tolist()
-    scale = float(ws[40:44].view(torch.float32).cpu()[0])
-    return out, DensityTerms(vert[:, 0].contiguous(), vert[:, 1].contiguous(), vert[:, 2].contiguous(), vert[:, 3].contiguous(),
-                             scale, *scal)
+    vert = ws[_WS_VERTEX:_WS_VERTEX + 16 * n].view(torch.float32).view(n, 4)
+    scal = ws[_WS_SCALARS:_WS_SCALARS + 40].view(torch.float64).cpu().tolist()
+    scale = float(ws[_WS_SCALE:_WS_SCALE + 4].view(torch.float32).cpu()[0])
+    return out, DensityTerms(*(vert[:, c].contiguous() for c in range(4)), scale, *scal)
 
 
 # ------------------------------------------------------------------------------------------------ initialisation

@@ -29,7 +29,7 @@ from parity_log import parity
 
 from test_densmap_cpu import (pearson, ref_densmap_fit, ref_density_epoch, ref_density_terms, ref_embedding_radii, ref_graph_dists,
                               ref_graph_radii, ref_live, ref_phase)
-from test_gpu_umap import AB, GOLDEN, ROOT, U, bits, dev, layout_case, rows
+from test_gpu_umap import AB, GOLDEN, LAYOUT_SHAPES, ROOT, U, bits, dev, layout_case, rows
 from test_gpu_umap import wafer_rows  # noqa: F401  (the fixture: 1 500 standardised golden rows)
 from test_umap_cpu import ref_alpha, ref_layout_epoch
 
@@ -128,8 +128,7 @@ def check_terms(name, terms, y, indptr, indices, q, data, rad, a, b, n_epochs, l
     parity(f"densmap per-vertex values {name} (fraction of the bound)", worst, 1.0)
 
 
-@pytest.mark.parametrize("dim", [1, 2, 3, 50, 64])
-@pytest.mark.parametrize("n", [2, 65, 300])
+@pytest.mark.parametrize("n,dim", LAYOUT_SHAPES)
 def test_embedding_radii_against_float64(n, dim):
     """D and re: double inside, 1 rounding to float32 each; the four per-vertex values and s of a phase epoch: formed
     in double from the double-precision radii, 1 rounding each.  The graph has an isolated vertex (D = 0 exactly,
@@ -215,8 +214,7 @@ def densmap_bound(y_ref, mag, dens_mag, pieces, alpha, deg, dim, b, rate):
     return 1.01 * U * (alpha * (big_e * mag + e_d * pieces + (adds[:, None] + 1) * (mag + dens_mag)) + np.abs(y_ref))
 
 
-@pytest.mark.parametrize("dim", [1, 2, 3, 50, 64])
-@pytest.mark.parametrize("n", [2, 65, 300])
+@pytest.mark.parametrize("n,dim", LAYOUT_SHAPES)
 def test_density_layout_teacher_forced_against_float64(n, dim):
     """20 epochs, one call each, with dens_frac 1.0 and 0.3; after every epoch the kernel's positions against one
     float64 reference epoch (plain terms + density terms) started from the kernel's own previous positions and, for

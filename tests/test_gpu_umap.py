@@ -275,10 +275,15 @@ def layout_bound(y_ref, mag, alpha, deg, dim, b, rate):
 
 
 AB = [(float(np.float32(1.57694)), float(np.float32(0.89506))), (float(np.float32(1.93281)), float(np.float32(0.79049)))]
+# The kernels are instantiated per padded dimension DP = 1, 2, 4, ..., 64.  The dims of the full n x dim grids reach
+# DP = 1, 2, 4 and 64; LADDER_DIMS, at one small n, reach the others and both sides of every step of the dim -> DP ladder
+# (4 | 5, 8 | 9, 16 | 17, 32 | 33).
+GRID_DIMS = [1, 2, 3, 50, 64]
+LADDER_DIMS = [4, 5, 8, 9, 16, 17, 32, 33]
+LAYOUT_SHAPES = [(n, dim) for dim in GRID_DIMS for n in (2, 65, 300)] + [(65, dim) for dim in LADDER_DIMS]
 
 
-@pytest.mark.parametrize("dim", [1, 2, 3, 50, 64])
-@pytest.mark.parametrize("n", [2, 65, 300])
+@pytest.mark.parametrize("n,dim", LAYOUT_SHAPES)
 def test_layout_teacher_forced_against_float64(n, dim):
     """20 epochs, one call each; after every epoch the kernel's positions against one float64 reference epoch started
     from the kernel's own previous positions (so no chaos enters the bound, and a missed or extra sample is an O(1)

@@ -22,7 +22,7 @@ import torch
 from parity_log import parity
 
 from test_cluster_cpu import lattice_points
-from test_gpu_umap import AB, bits, dev, eps, max_rel, rows, wafer_rows  # noqa: F401  (wafer_rows: a fixture)
+from test_gpu_umap import AB, GRID_DIMS, LADDER_DIMS, bits, dev, eps, max_rel, rows, wafer_rows  # noqa: F401  (wafer_rows: a fixture)
 from test_umap_cpu import ref_rates
 from test_umap_transform_cpu import (loo_knn_accuracy, pairwise64_rect, recall_at_k, ref_far_dist, ref_fit_labels,
                                      ref_label_intersect, ref_query_weights, ref_transform, ref_transform_alpha,
@@ -300,9 +300,8 @@ def transform_bound(y_ref, mag, alpha, k, dim, b, rate):
     return 1.01 * U * ((big_e + adds + 1) * alpha * mag + np.abs(y_ref))
 
 
-@pytest.mark.parametrize("dim", [1, 2, 3, 50, 64])
-@pytest.mark.parametrize("n", [2, 300])
-@pytest.mark.parametrize("m", [1, 65, 258])
+@pytest.mark.parametrize("m,n,dim", [(m, n, dim) for dim in GRID_DIMS for n in (2, 300) for m in (1, 65, 258)]
+                         + [(65, 300, dim) for dim in LADDER_DIMS])
 def test_transform_layout_teacher_forced_against_float64(m, n, dim):
     """Per k: 20 epochs, one call each; after every epoch the kernel's positions against one float64 reference epoch
     started from the kernel's own previous positions.  k = 1, 15, 33, 64 (k <= n): with EPP = 64 / DP entry slots that is
