@@ -391,6 +391,16 @@ def ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
+def workspace(need: int, what: str, device):
+    """The uint8 tensor of the `need` bytes a wm_*_workspace_bytes function asked for.  Those functions answer 0 for
+    sizes their kernels do not take: ValueError(what), `what` naming the caller and the sizes."""
+    import torch
+
+    if need == 0:
+        raise ValueError(what)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
 def require_gpu(*tensors) -> None:
     for t in tensors:
         if t is not None and not t.is_cuda:

@@ -52,7 +52,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import check, ptr, require_gpu, stream_ptr, workspace
 
 METRICS = {"euclidean": 0, "l2": 0, "manhattan": 1, "l1": 1, "cityblock": 1}
 _LISTED_NOT_BUILT = ("canberra", "braycurtis")  # in the notebook's search space; no kernel here
@@ -84,6 +84,29 @@ def _prep(x):
     return x.contiguous()
 
 
+def _check_core_comp(core, comp, n: int):
+    """The per-row operands of the min-edge kernels."""
+    import torch
+
+    if core.shape != (n,) or comp.shape != (n,) or core.dtype != torch.float32 or comp.dtype != torch.int32:
+        raise ValueError("core float32 [n] and comp int32 [n] expected")
+
+
+def _check_core_pair(core_q, m: int, core, n: int, n_name: str):
+    """The core distances of the two sides of a mutual-reachability query; `n_name`: what the message calls n."""
+    import torch
+
+    if core_q.shape != (m,) or core.shape != (n,) or core_q.dtype != torch.float32 or core.dtype != torch.float32:
+        raise ValueError(f"core_q float32 [m] and core float32 [{n_name}] expected")
+
+
+def _through_order(order, j):
+    """Column indices j (int32, -1 = none) into rows sorted by `order`, as indices into the rows as the caller gave them."""
+    import torch
+
+    return torch.where(j >= 0, order.to(torch.int32)[j.clamp(min=0).long()], j)
+
+
 # ------------------------------------------------------------------------------------------------ GPU: tree
 
 
@@ -100,9 +123,7 @@ def core_distances(x, min_samples: int, metric: str = "euclidean"):
         raise ValueError(f"min_samples ({k}) must be in [1, n_samples = {n}]")
     lib = _lib.load()
     need = lib.wm_core_distance_workspace_bytes(n, d, k)
-    if need == 0:
-        raise ValueError(f"core_distances: unsupported sizes n={n} d={d} min_samples={k} (min_samples <= 64)")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"core_distances: unsupported sizes n={n} d={d} min_samples={k} (min_samples <= 64)", x.device)
     out = torch.empty(n, dtype=torch.float32, device=x.device)
     check(lib.wm_core_distance(ptr(x), n, d, code, k, ptr(out), ptr(ws), need, stream_ptr()), "wm_core_distance")
     return out
@@ -117,8 +138,7 @@ def min_outgoing_edges(x, core, comp, metric: str = "euclidean", alpha: float = 
     x = _prep(x)
     require_gpu(core, comp)
     n, d = x.shape
-    if core.shape != (n,) or comp.shape != (n,) or core.dtype != torch.float32 or comp.dtype != torch.int32:
-        raise ValueError("core float32 [n] and comp int32 [n] expected")
+    _check_core_comp(core, comp, n)
     lib = _lib.load()
     need = lib.wm_mreach_min_edge_workspace_bytes(n, d)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
@@ -790,15 +810,12 @@ def mreach_query(xq, core_q, x, core, metric: str = "euclidean", alpha: float = 
     (m, d), n = xq.shape, x.shape[0]
     if x.shape[1] != d:
         raise ValueError(f"the new rows have {d} features (padded), the fitted rows {x.shape[1]}")
-    if core_q.shape != (m,) or core.shape != (n,) or core_q.dtype != torch.float32 or core.dtype != torch.float32:
-        raise ValueError("core_q float32 [m] and core float32 [n] expected")
+    _check_core_pair(core_q, m, core, n, "n")
     if m < 1 or n < 1:
         raise ValueError("mreach_query needs at least one row on either side")
     lib = _lib.load()
     need = lib.wm_mreach_query_workspace_bytes(m, n, d)
-    if need == 0:
-        raise ValueError(f"mreach_query: unsupported sizes m={m} n={n} d={d}")
-    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    ws = workspace(need, f"mreach_query: unsupported sizes m={m} n={n} d={d}", xq.device)
     w = torch.empty(m, dtype=torch.float32, device=xq.device)
     dist = torch.empty(m, dtype=torch.float32, device=xq.device)
     j = torch.empty(m, dtype=torch.int32, device=xq.device)
@@ -884,13 +901,10 @@ def group_min_distances(xq, xe, group, n_groups: int, metric: str = "euclidean")
     gs = group.to(xq.device)[order].to(torch.int32).contiguous()
     lib = _lib.load()
     need = lib.wm_group_min_dist_workspace_bytes(m, e, d, g)
-    if need == 0:
-        raise ValueError(f"group_min_distances: unsupported sizes m={m} e={e} d={d} n_groups={g}")
-    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    ws = workspace(need, f"group_min_distances: unsupported sizes m={m} e={e} d={d} n_groups={g}", xq.device)
     check(lib.wm_group_min_dist(ptr(xq), m, ptr(xs), ptr(gs), e, d, code, g, ptr(dist), ptr(j), ptr(ws), need, stream_ptr()),
           "wm_group_min_dist")
-    back = order.to(torch.int32)[j.clamp(min=0).long()]
-    return dist, torch.where(j >= 0, back, j)
+    return dist, _through_order(order, j)
 
 
 def _exemplar_distances(model: "HDBSCAN", xq) -> np.ndarray:
@@ -978,9 +992,7 @@ def allpoints_core_distances(x, labels, d: Optional[float] = None, metric: str =
     m, g = int(keep.size), int(enc.max()) + 1
     lib = _lib.load()
     need = lib.wm_allpoints_core_workspace_bytes(m, dim, g)
-    if need == 0:
-        raise ValueError(f"allpoints_core_distances: unsupported sizes n={m} d={dim} clusters={g}")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"allpoints_core_distances: unsupported sizes n={m} d={dim} clusters={g}", x.device)
     res = torch.empty(m, dtype=torch.float64, device=x.device)
     check(lib.wm_allpoints_core(ptr(xs), ptr(gs), m, dim, code, g, p, ptr(res), ptr(ws), need, stream_ptr()), "wm_allpoints_core")
     out[rows] = res
@@ -998,26 +1010,22 @@ def grouped_min_outgoing_edges(x, core, comp, group, n_groups: int, metric: str 
     x = _prep(x)
     require_gpu(core, comp)
     n, d = x.shape
-    if core.shape != (n,) or comp.shape != (n,) or core.dtype != torch.float32 or comp.dtype != torch.int32:
-        raise ValueError("core float32 [n] and comp int32 [n] expected")
+    _check_core_comp(core, comp, n)
     g = int(n_groups)
     order, gs = _sorted_groups(group, n, g, x.device)
     if order is not None:
         x, core, comp = x[order].contiguous(), core[order].contiguous(), comp[order].contiguous()
     lib = _lib.load()
     need = lib.wm_mreach_min_edge_grouped_workspace_bytes(n, d, g)
-    if need == 0:
-        raise ValueError(f"grouped_min_outgoing_edges: unsupported sizes n={n} d={d} n_groups={g}")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"grouped_min_outgoing_edges: unsupported sizes n={n} d={d} n_groups={g}", x.device)
     w = torch.empty(n, dtype=torch.float32, device=x.device)
     j = torch.empty(n, dtype=torch.int32, device=x.device)
     check(lib.wm_mreach_min_edge_grouped(ptr(x), ptr(core), ptr(comp), ptr(gs), n, d, code, g, ptr(w), ptr(j), ptr(ws), need,
                                          stream_ptr()), "wm_mreach_min_edge_grouped")
     if order is None:
         return w, j
-    back = torch.where(j >= 0, order.to(torch.int32)[j.clamp(min=0).long()], j)
     w_out, j_out = torch.empty_like(w), torch.empty_like(j)
-    w_out[order], j_out[order] = w, back
+    w_out[order], j_out[order] = w, _through_order(order, j)
     return w_out, j_out
 
 
@@ -1033,8 +1041,7 @@ def group_min_mreach(xq, core_q, xe, core, group, n_groups: int, metric: str = "
     (m, d), e, g = xq.shape, xe.shape[0], int(n_groups)
     if xe.shape[1] != d:
         raise ValueError(f"the rows have {d} features (padded), the grouped rows {xe.shape[1]}")
-    if core_q.shape != (m,) or core.shape != (e,) or core_q.dtype != torch.float32 or core.dtype != torch.float32:
-        raise ValueError("core_q float32 [m] and core float32 [e] expected")
+    _check_core_pair(core_q, m, core, e, "e")
     if m < 1 or e < 1:
         raise ValueError("group_min_mreach needs at least one row on either side")
     order, gs = _sorted_groups(group, e, g, xq.device)
@@ -1044,14 +1051,12 @@ def group_min_mreach(xq, core_q, xe, core, group, n_groups: int, metric: str = "
     j = torch.empty((m, g), dtype=torch.int32, device=xq.device)
     lib = _lib.load()
     need = lib.wm_group_min_mreach_workspace_bytes(m, e, d, g)
-    if need == 0:
-        raise ValueError(f"group_min_mreach: unsupported sizes m={m} e={e} d={d} n_groups={g}")
-    ws = torch.empty(need, dtype=torch.uint8, device=xq.device)
+    ws = workspace(need, f"group_min_mreach: unsupported sizes m={m} e={e} d={d} n_groups={g}", xq.device)
     check(lib.wm_group_min_mreach(ptr(xq), ptr(core_q), m, ptr(xe), ptr(core), ptr(gs), e, d, code, g, ptr(w), ptr(j), ptr(ws),
                                   need, stream_ptr()), "wm_group_min_mreach")
     if order is None:
         return w, j
-    return w, torch.where(j >= 0, order.to(torch.int32)[j.clamp(min=0).long()], j)
+    return w, _through_order(order, j)
 
 
 def validity_from_parts(sizes, n_total: int, sparseness, sep) -> Tuple[float, np.ndarray]:
@@ -1415,9 +1420,7 @@ def _kmeans_update(x, cols, dist, prev_cols, centres):
     (n, d), (r, k, _) = x.shape, centres.shape
     lib = _lib.load()
     need = lib.wm_kmeans_update_workspace_bytes(n, d, k, r)
-    if need == 0:
-        raise ValueError(f"kmeans update: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"kmeans update: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}", x.device)
     new = torch.empty_like(centres)
     counts = torch.empty((r, k), dtype=torch.int32, device=x.device)
     inertia = torch.empty(r, dtype=torch.float64, device=x.device)
@@ -1438,9 +1441,7 @@ def _kmeans_assign(x, centres):
     group = torch.arange(r, dtype=torch.int32, device=x.device).repeat_interleave(k).contiguous()
     lib = _lib.load()
     need = lib.wm_group_min_dist_workspace_bytes(n, r * k, d, r)
-    if need == 0:
-        raise ValueError(f"kmeans assignment: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"kmeans assignment: unsupported sizes n={n} d={d} n_clusters={k} restarts={r}", x.device)
     dist = torch.empty((n, r), dtype=torch.float32, device=x.device)
     cols = torch.empty((n, r), dtype=torch.int32, device=x.device)
     check(lib.wm_group_min_dist(ptr(x), n, ptr(centres), ptr(group), r * k, d, 0, r, ptr(dist), ptr(cols), ptr(ws), need,
@@ -1524,9 +1525,8 @@ def kmeans_plusplus(x, n_clusters: int, *, random_state=None, uniforms=None, n_l
             raise ValueError(f"uniforms: float64 [{k}, {t}] in [0, 1) expected")
     lib = _lib.load()
     need = lib.wm_kmeans_seed_workspace_bytes(n, d, k, t)
-    if need == 0:
-        raise ValueError(f"kmeans_plusplus: unsupported sizes n={n} d={d} n_clusters={k} n_local_trials={t} (1 .. 16 trials)")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"kmeans_plusplus: unsupported sizes n={n} d={d} n_clusters={k} n_local_trials={t} (1 .. 16 trials)",
+                   x.device)
     u_d = torch.from_numpy(u).to(x.device)
     centres = torch.empty((k, d), dtype=torch.float32, device=x.device)
     idx = torch.empty(k, dtype=torch.int32, device=x.device)

@@ -101,15 +101,18 @@
 //             bytes for t, tj and the bins, 30 KB at k = 15 (three workgroups per CU: the 134 VGPRs bound it, not the
 //             LDS) and 66 KB at k = 63 (two per CU of 160 KB, 8 waves; TM = 8 would allow one).  TM = 4 keeps the LDS
 //             array far from its limit (the group-min note above) and gives 195 row tiles on 12 449 rows.
-//             A slice stores its counts into its own [m][k] plane and cl_rank_merge adds the planes; with one slice
-//             the kernel stores straight into the output.
+//             A slice stores its counts into its own plane and cl_rank_merge adds the planes; with one slice the
+//             kernel stores straight into the output (`direct` in cl_mode).
 // Block-diagonal walk (all-points core, grouped min edge): with the rows sorted by group a row tile needs only the
 // columns from the first column of its first row's group to the last column of its last row's group.  cl_group_bounds
 // writes every present group's [first, last + 1) into the workspace (one thread per row, the run boundaries store);
 // cl_pairs reads the two ends for its row tile and cuts THAT tile range into the grid's slices, so the cost is the sum
 // of n_c^2 over the groups (rounded up to tiles) and not n^2.  Pairs of two groups inside a shared tile are masked.
-// Core, knn, min edge, query and group min split the columns into slices (grid.y) whose partial results a second small kernel combines in a
-// fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  No
+// Every mode but the sums splits the columns into slices (grid.y) whose partial results a second small kernel combines
+// in a fixed order; the sums kernel keeps one workgroup per row tile so that every out[i][c] has a single writer.  The
+// tile height of a mode, the cap on its slices, the bytes a slice keeps per entry and whether a single slice stores
+// straight into the outputs are the mode's line in cl_mode (host side, below): cl_plan makes the grid and the workspace
+// layout from it for the size function and for the entry point alike.  No
 // floating-point atomics and no atomics on global memory anywhere; the only atomics are the rank mode's integer adds
 // into its LDS bins, whose sums do not depend on the order: two calls give the same bits.
 // Roofline: float32 VALU, 3 flops (2 instructions) per pair and feature; operands come from L2 / Infinity Cache
@@ -871,6 +874,8 @@ __global__ __launch_bounds__(CL_THREADS) void cl_apcore_merge(const double* __re
   out[i] = (m == -INFINITY || nc < 2) ? 0.0 : exp(-(m + log(s) - log((double)(nc - 1))) / pw);
 }
 
+// ---- host side: one plan per mode, one set of checks, one argument head ---------------------------------------------
+
 struct ClGrid {
   int row_tiles, col_tiles, slices, tiles_per_slice;
 };
@@ -889,8 +894,70 @@ inline ClGrid cl_grid(int m, int n, int rows, bool sliced, int max_slices = 1 <<
   return g;
 }
 
-template <int MODE, int TM>
+// What the host knows about a mode, written here once and nowhere else: the TM that cl_launch instantiates (a row tile
+// is 16 * tm rows, which is what cl_grid gets), how the columns are sliced, and what every slice keeps in the workspace
+// for the merge kernel.  A new mode adds its line to cl_mode; its size function and its entry point both go through
+// cl_plan, so they cannot disagree.
+enum ClPer { CL_PER_ROW, CL_PER_ROW_K, CL_PER_ROW_GROUP };  // a slice's entries: per row, per (row, k), per (row, group)
+struct ClMode {
+  int tm;
+  bool sliced;
+  int max_slices;
+  ClPer per;
+  int entry_bytes;  // of one entry over all of the mode's planes; the planes lie one behind the other
+  bool direct;      // a single slice stores straight into the outputs and needs no plane (and no merge)
+  bool bounds;      // behind the planes: g pairs [first, last + 1) of ints (cl_group_bounds)
+};
+constexpr int CL_ANY_SLICES = 1 << 30;
+constexpr ClMode cl_mode(int mode) {
+  switch (mode) {  //            tm, sliced, max_slices, per, entry_bytes, direct, bounds
+    case CL_CORE:        return {8, true, CL_ANY_SLICES, CL_PER_ROW_K, 4, false, false};  // the k-list's distances
+    case CL_KNN:         return {8, true, CL_ANY_SLICES, CL_PER_ROW_K, 8, false, false};  // distances, then indices
+    case CL_MINEDGE:     return {8, true, CL_ANY_SLICES, CL_PER_ROW, 8, false, false};    // w, then j
+    case CL_MINEDGE_G:   return {8, true, CL_ANY_SLICES, CL_PER_ROW, 8, false, true};
+    case CL_MREACHQ:     return {8, true, CL_ANY_SLICES, CL_PER_ROW, 12, false, false};   // w, dist, j
+    case CL_APCORE:      return {4, true, CL_ANY_SLICES, CL_PER_ROW, 16, false, true};    // M, then S (doubles)
+    case CL_RANK:        return {4, true, CL_ANY_SLICES, CL_PER_ROW_K, 4, true, false};   // counts
+    case CL_GROUPMIN:
+    case CL_GROUPMIN_MR: return {4, true, CL_GROUPMIN_SLICES, CL_PER_ROW_GROUP, 8, true, false};  // distances, then columns
+    case CL_SUMS:        return {4, false, 1, CL_PER_ROW, 0, false, false};  // one workgroup per row tile, no workspace
+  }
+  return {};  // (tm = 0: cl_launch refuses to compile)
+}
+
+struct ClPlan {
+  ClGrid grid;
+  bool direct;     // the kernel's results are final: pass the outputs, launch no merge
+  size_t entries;  // of one plane: slices * m [* k or * g]; 0 when direct
+  size_t bytes;    // what the entry point needs of the workspace (the size function adds its slack of 256)
+};
+template <int MODE>
+ClPlan cl_plan(int m, int n, int k, int g) {
+  constexpr ClMode md = cl_mode(MODE);
+  ClPlan p;
+  p.grid = cl_grid(m, n, 16 * md.tm, md.sliced, md.max_slices);
+  p.direct = md.direct && p.grid.slices == 1;
+  const size_t width = md.per == CL_PER_ROW_K ? k : md.per == CL_PER_ROW_GROUP ? g : 1;
+  p.entries = p.direct ? 0 : (size_t)p.grid.slices * m * width;
+  p.bytes = p.entries * md.entry_bytes + (md.bounds ? (size_t)g * 8 : 0);
+  return p;
+}
+
+// The planes of a workspace in the order in which they lie in it.
+struct ClCarve {
+  char* at;
+  template <typename T>
+  T* take(size_t count) {
+    T* p = reinterpret_cast<T*>(at);
+    at += count * sizeof(T);
+    return p;
+  }
+};
+
+template <int MODE>
 int cl_launch(const ClArgs& a, const ClGrid& g, int metric, hipStream_t st) {
+  constexpr int TM = cl_mode(MODE).tm;
+  static_assert(TM == 4 || TM == 8, "the mode has no line in cl_mode");
   const size_t lds = cl_lds_bytes<MODE, TM>(a.kl);
   constexpr size_t lds_max = cl_lds_bytes<MODE, TM>(CL_MAXK | 1);  // the mode's largest request, allowed once
   static bool attr_set[2] = {false, false};  // per metric; idempotent; a race only repeats the call
@@ -912,390 +979,315 @@ int cl_launch(const ClArgs& a, const ClGrid& g, int metric, hipStream_t st) {
 
 inline bool cl_shape_ok(int d, int metric) { return d % 4 == 0 && d <= 1024 && (metric == 0 || metric == 1); }
 constexpr int CL_MAX_N = 1 << 24;  // (row * d and slice * n + row stay far inside size_t; tile indices inside int)
+inline bool cl_count_ok(int v) { return v > 0 && v <= CL_MAX_N; }
+inline bool cl_aligned(const void* p, uintptr_t mask = 15) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 
-}  // namespace
-
-extern "C" size_t wm_core_distance_workspace_bytes(int n, int d, int k) {
-  if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  return (size_t)cl_grid(n, n, 128, true).slices * n * k * sizeof(float) + 256;
-}
-
-extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k, float* out, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(x && out && workspace, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
-  WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, n, 128, true);
-  WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * k * sizeof(float), WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
-  a.k = k;
-  a.kl = k | 1;  // odd pitch: the owners' list accesses fall on distinct banks
-  a.part_lists = static_cast<float*>(workspace);
-  const int rc = cl_launch<CL_CORE, 8>(a, g, metric, st);
-  if (rc != WM_OK) return rc;
-  cl_core_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, g.slices, n, k, out);
-  WM_LAUNCH_CHECK();
+// The checks every entry point makes before it touches the device, in the order the callers rely on.  `valid`: the
+// entry point's own part of the first stage (no null pointer, k <= n, ...); `aligned`: its pointers' alignment.  An
+// entry point without a k or without groups passes 1.
+inline int cl_check(bool valid, int m, int n, int d, int metric, int k, int g, bool aligned) {
+  WM_REQUIRE(valid && m > 0 && n > 0 && d > 0 && k > 0 && g > 0, WM_EINVAL);
+  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
+  WM_REQUIRE(aligned, WM_EALIGN);
   return WM_OK;
 }
-
-extern "C" size_t wm_knn_graph_workspace_bytes(int n, int d, int k) {
-  if (n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  return (size_t)cl_grid(n, n, 128, true).slices * n * k * 8 + 256;
-}
-
-extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(x && dist && idx && workspace, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
-  WM_REQUIRE(k <= CL_MAXK && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, n, 128, true);
-  const size_t entries = (size_t)g.slices * n * k;
-  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
-  a.k = k;
-  a.kl = k | 1;
-  a.part_lists = static_cast<float*>(workspace);
-  a.part_idx = reinterpret_cast<int*>(a.part_lists + entries);
-  const int rc = cl_launch<CL_KNN, 8>(a, g, metric, st);
+// The same and, last, the workspace against the mode's plan, which it hands back.
+template <int MODE>
+int cl_prepare(bool valid, int m, int n, int d, int metric, int k, int g, bool aligned, size_t workspace_bytes, ClPlan* plan) {
+  const int rc = cl_check(valid, m, n, d, metric, k, g, aligned);
   if (rc != WM_OK) return rc;
-  cl_knn_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, g.slices, n, k, dist, idx);
-  WM_LAUNCH_CHECK();
+  *plan = cl_plan<MODE>(m, n, k, g);
+  WM_REQUIRE(workspace_bytes >= plan->bytes, WM_EWORKSPACE);
   return WM_OK;
 }
-
-extern "C" size_t wm_knn_query_workspace_bytes(int m, int n, int d, int k) {
-  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  return (size_t)cl_grid(m, n, 128, true).slices * m * k * 8 + 256;
+// The size functions: 0 outside the sizes the plan is made for (d and the metric are the entry point's to refuse).
+template <int MODE>
+size_t cl_workspace_bytes(int m, int n, int d, int k, int g) {
+  if (!(cl_count_ok(m) && cl_count_ok(n) && d > 0 && k > 0 && k <= CL_MAXK && cl_count_ok(g))) return 0;
+  return cl_plan<MODE>(m, n, k, g).bytes + 256;
 }
 
-extern "C" int wm_knn_query(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(xq && x && dist && idx && workspace, WM_EINVAL);
-  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0 && k <= n, WM_EINVAL);
-  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-             WM_EALIGN);
-  const ClGrid g = cl_grid(m, n, 128, true);
-  const size_t entries = (size_t)g.slices * m * k;
-  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+// The head of every mode's arguments: nr rows of xr against the n rows of x (the square modes pass x, n twice).
+inline ClArgs cl_args(const float* xr, int nr, const float* x, int n, int d, const ClGrid& g) {
   ClArgs a = {};
   a.x = x;
   a.n = n;
-  a.xr = xq;
-  a.nr = m;
+  a.xr = xr;
+  a.nr = nr;
   a.d = d;
   a.tiles_per_slice = g.tiles_per_slice;
   a.col_tiles = g.col_tiles;
-  a.k = k;
-  a.kl = k | 1;
-  a.part_lists = static_cast<float*>(workspace);
-  a.part_idx = reinterpret_cast<int*>(a.part_lists + entries);
-  const int rc = cl_launch<CL_KNN, 8>(a, g, metric, st);
+  return a;
+}
+
+// The grid of the grid-stride kernels (cl_pair_dist, cl_rank_merge, cl_group_min_merge): a thread per element, capped.
+inline unsigned cl_grid_1d(size_t total) {
+  const size_t blocks = (total + CL_THREADS - 1) / CL_THREADS;
+  return (unsigned)(blocks < 65536 ? blocks : 65536);
+}
+
+}  // namespace
+
+extern "C" size_t wm_core_distance_workspace_bytes(int n, int d, int k) { return cl_workspace_bytes<CL_CORE>(n, n, d, k, 1); }
+
+extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  ClPlan pl;
+  const int rc = cl_prepare<CL_CORE>(x && out && workspace && k <= n, n, n, d, metric, k, 1,
+                                     cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
-  cl_knn_merge<<<wm_cdiv(m, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, g.slices, m, k, dist, idx);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClArgs a = cl_args(x, n, x, n, d, pl.grid);
+  a.k = k;
+  a.kl = k | 1;  // odd pitch: the owners' list accesses fall on distinct banks
+  a.part_lists = static_cast<float*>(workspace);
+  const int lrc = cl_launch<CL_CORE>(a, pl.grid, metric, st);
+  if (lrc != WM_OK) return lrc;
+  cl_core_merge<<<wm_cdiv(n, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, pl.grid.slices, n, k, out);
   WM_LAUNCH_CHECK();
   return WM_OK;
+}
+
+namespace {
+
+// wm_knn_graph (xq = x, m = n) and wm_knn_query.
+int cl_knn_run(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
+               void* workspace, size_t workspace_bytes, void* stream) {
+  ClPlan pl;
+  const int rc = cl_prepare<CL_KNN>(xq && x && dist && idx && workspace && k <= n, m, n, d, metric, k, 1,
+                                    cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClCarve ws{static_cast<char*>(workspace)};
+  ClArgs a = cl_args(xq, m, x, n, d, pl.grid);
+  a.k = k;
+  a.kl = k | 1;  // odd pitch: the owners' list accesses fall on distinct banks
+  a.part_lists = ws.take<float>(pl.entries);
+  a.part_idx = ws.take<int>(pl.entries);
+  const int lrc = cl_launch<CL_KNN>(a, pl.grid, metric, st);
+  if (lrc != WM_OK) return lrc;
+  cl_knn_merge<<<wm_cdiv(m, CL_THREADS / 64), CL_THREADS, 0, st>>>(a.part_lists, a.part_idx, pl.grid.slices, m, k, dist, idx);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t wm_knn_graph_workspace_bytes(int n, int d, int k) { return cl_workspace_bytes<CL_KNN>(n, n, d, k, 1); }
+
+extern "C" int wm_knn_graph(const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  return cl_knn_run(x, n, x, n, d, metric, k, dist, idx, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t wm_knn_query_workspace_bytes(int m, int n, int d, int k) { return cl_workspace_bytes<CL_KNN>(m, n, d, k, 1); }
+
+extern "C" int wm_knn_query(const float* xq, int m, const float* x, int n, int d, int metric, int k, float* dist, int32_t* idx,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return cl_knn_run(xq, m, x, n, d, metric, k, dist, idx, workspace, workspace_bytes, stream);
 }
 
 extern "C" int wm_pair_dist(const float* xq, int m, const float* x, int n, int d, int metric, const int32_t* idx, int k,
                             float* out, void* stream) {
-  WM_REQUIRE(xq && x && idx && out, WM_EINVAL);
-  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0, WM_EINVAL);
-  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, WM_EALIGN);
+  const int rc = cl_check(xq && x && idx && out, m, n, d, metric, k, 1, cl_aligned(xq) && cl_aligned(x));
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t total = (size_t)m * k;
-  const size_t blocks = (total + CL_THREADS - 1) / CL_THREADS;
-  const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
   if (metric == 0)
-    cl_pair_dist<0><<<grid, CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
+    cl_pair_dist<0><<<cl_grid_1d(total), CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
   else
-    cl_pair_dist<1><<<grid, CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
+    cl_pair_dist<1><<<cl_grid_1d(total), CL_THREADS, 0, st>>>(xq, x, idx, n, d, k, total, out);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-extern "C" size_t wm_rank_query_workspace_bytes(int m, int n, int d, int k) {
-  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0 || k <= 0 || k > CL_MAXK) return 0;
-  const ClGrid g = cl_grid(m, n, 64, true);
-  return (g.slices > 1 ? (size_t)g.slices * m * k * sizeof(int) : 0) + 256;
-}
+extern "C" size_t wm_rank_query_workspace_bytes(int m, int n, int d, int k) { return cl_workspace_bytes<CL_RANK>(m, n, d, k, 1); }
 
 extern "C" int wm_rank_query(const float* xq, int m, const float* x, int n, int d, int metric, const float* t, const int32_t* tj,
                              const int32_t* skip, int k, int32_t* count, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  WM_REQUIRE(xq && x && t && tj && skip && count && workspace, WM_EINVAL);
-  WM_REQUIRE(m > 0 && n > 0 && d > 0 && k > 0, WM_EINVAL);
-  WM_REQUIRE(k <= CL_MAXK && m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-             WM_EALIGN);
-  const ClGrid g = cl_grid(m, n, 64, true);
-  const size_t entries = g.slices > 1 ? (size_t)g.slices * m * k : 0;
-  WM_REQUIRE(workspace_bytes >= entries * sizeof(int), WM_EWORKSPACE);
+  ClPlan pl;
+  const int rc = cl_prepare<CL_RANK>(xq && x && t && tj && skip && count && workspace, m, n, d, metric, k, 1,
+                                     cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = x;
-  a.n = n;
-  a.xr = xq;
-  a.nr = m;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
+  ClArgs a = cl_args(xq, m, x, n, d, pl.grid);
   a.k = k;
   a.kl = k | 1;  // odd pitch: the owners' prefix sums fall on distinct banks
   a.core_q = t;
   a.comp = tj;
   a.labels = skip;
-  a.part_idx = g.slices > 1 ? static_cast<int*>(workspace) : count;
-  const int rc = cl_launch<CL_RANK, 4>(a, g, metric, st);
-  if (rc != WM_OK || g.slices == 1) return rc;
+  a.part_idx = pl.direct ? count : static_cast<int*>(workspace);
+  const int lrc = cl_launch<CL_RANK>(a, pl.grid, metric, st);
+  if (lrc != WM_OK || pl.direct) return lrc;
   const size_t total = (size_t)m * k;
-  const size_t blocks = (total + CL_THREADS - 1) / CL_THREADS;
-  cl_rank_merge<<<(unsigned)(blocks < 65536 ? blocks : 65536), CL_THREADS, 0, st>>>(a.part_idx, g.slices, total, count);
+  cl_rank_merge<<<cl_grid_1d(total), CL_THREADS, 0, st>>>(a.part_idx, pl.grid.slices, total, count);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-extern "C" size_t wm_mreach_min_edge_workspace_bytes(int n, int d) {
-  if (n <= 0 || n > CL_MAX_N || d <= 0) return 0;
-  return (size_t)cl_grid(n, n, 128, true).slices * n * 8 + 256;
+namespace {
+
+// wm_mreach_min_edge (group = nullptr, g = 1) and wm_mreach_min_edge_grouped (inv_alpha = 1: dist * 1 is dist, so the
+// weights are wm_mreach_min_edge's bits at alpha 1).
+template <int MODE>
+int cl_min_edge_run(const float* x, const float* core, const int32_t* comp, const int32_t* group, int n, int d, int metric,
+                    int g, float inv_alpha, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  ClPlan pl;
+  const int rc = cl_prepare<MODE>(x && core && comp && (MODE == CL_MINEDGE || group) && out_w && out_j && workspace &&
+                                      inv_alpha > 0.f,
+                                  n, n, d, metric, 1, g, cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ClCarve ws{static_cast<char*>(workspace)};
+  ClArgs a = cl_args(x, n, x, n, d, pl.grid);
+  a.core = core;
+  a.comp = comp;
+  a.inv_alpha = inv_alpha;
+  a.part_w = ws.take<float>(pl.entries);
+  a.part_j = ws.take<int>(pl.entries);
+  if constexpr (MODE == CL_MINEDGE_G) {
+    int* bounds = ws.take<int>(2 * (size_t)g);
+    a.labels = group;
+    a.n_clusters = g;
+    a.bounds = bounds;
+    cl_group_bounds<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(group, n, g, bounds);
+    WM_LAUNCH_CHECK();
+  }
+  const int lrc = cl_launch<MODE>(a, pl.grid, metric, st);
+  if (lrc != WM_OK) return lrc;
+  cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, pl.grid.slices, n, out_w, out_j);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
 }
+
+}  // namespace
+
+extern "C" size_t wm_mreach_min_edge_workspace_bytes(int n, int d) { return cl_workspace_bytes<CL_MINEDGE>(n, n, d, 1, 1); }
 
 extern "C" int wm_mreach_min_edge(const float* x, const float* core, const int32_t* comp, int n, int d, int metric,
                                   float inv_alpha, float* out_w, int32_t* out_j, void* workspace, size_t workspace_bytes,
                                   void* stream) {
-  WM_REQUIRE(x && core && comp && out_w && out_j && workspace, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && inv_alpha > 0.f, WM_EINVAL);
-  WM_REQUIRE(n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid g = cl_grid(n, n, 128, true);
-  WM_REQUIRE(workspace_bytes >= (size_t)g.slices * n * 8, WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
-  a.core = core;
-  a.comp = comp;
-  a.inv_alpha = inv_alpha;
-  a.part_w = static_cast<float*>(workspace);
-  a.part_j = reinterpret_cast<int*>(a.part_w + (size_t)g.slices * n);
-  const int rc = cl_launch<CL_MINEDGE, 8>(a, g, metric, st);
-  if (rc != WM_OK) return rc;
-  cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, g.slices, n, out_w, out_j);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  return cl_min_edge_run<CL_MINEDGE>(x, core, comp, nullptr, n, d, metric, 1, inv_alpha, out_w, out_j, workspace,
+                                     workspace_bytes, stream);
 }
 
 extern "C" size_t wm_mreach_min_edge_grouped_workspace_bytes(int n, int d, int g) {
-  if (n <= 0 || n > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
-  return (size_t)cl_grid(n, n, 128, true).slices * n * 8 + (size_t)g * 8 + 256;
+  return cl_workspace_bytes<CL_MINEDGE_G>(n, n, d, 1, g);
 }
 
 extern "C" int wm_mreach_min_edge_grouped(const float* x, const float* core, const int32_t* comp, const int32_t* group, int n,
                                           int d, int metric, int g, float* out_w, int32_t* out_j, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(x && core && comp && group && out_w && out_j && workspace, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && g > 0, WM_EINVAL);
-  WM_REQUIRE(n <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, WM_EALIGN);
-  const ClGrid gr = cl_grid(n, n, 128, true);
-  const size_t entries = (size_t)gr.slices * n;
-  WM_REQUIRE(workspace_bytes >= entries * 8 + (size_t)g * 8, WM_EWORKSPACE);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = gr.tiles_per_slice;
-  a.col_tiles = gr.col_tiles;
-  a.core = core;
-  a.comp = comp;
-  a.inv_alpha = 1.f;  // (dist * 1 is dist: the weights are wm_mreach_min_edge's bits at alpha 1)
-  a.labels = group;
-  a.n_clusters = g;
-  a.part_w = static_cast<float*>(workspace);
-  a.part_j = reinterpret_cast<int*>(a.part_w + entries);
-  int* bounds = a.part_j + entries;
-  a.bounds = bounds;
-  cl_group_bounds<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(group, n, g, bounds);
-  WM_LAUNCH_CHECK();
-  const int rc = cl_launch<CL_MINEDGE_G, 8>(a, gr, metric, st);
-  if (rc != WM_OK) return rc;
-  cl_minedge_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_j, gr.slices, n, out_w, out_j);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  return cl_min_edge_run<CL_MINEDGE_G>(x, core, comp, group, n, d, metric, g, 1.f, out_w, out_j, workspace, workspace_bytes,
+                                       stream);
 }
 
-extern "C" size_t wm_allpoints_core_workspace_bytes(int n, int d, int g) {
-  if (n <= 0 || n > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
-  return (size_t)cl_grid(n, n, 64, true).slices * n * 16 + (size_t)g * 8 + 256;
-}
+extern "C" size_t wm_allpoints_core_workspace_bytes(int n, int d, int g) { return cl_workspace_bytes<CL_APCORE>(n, n, d, 1, g); }
 
 extern "C" int wm_allpoints_core(const float* x, const int32_t* group, int n, int d, int metric, int g, double p, double* out,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(x && group && out && workspace, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && g > 0 && p > 0.0 && p < (double)INFINITY, WM_EINVAL);
-  WM_REQUIRE(n <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 7) == 0,
-             WM_EALIGN);
-  const ClGrid gr = cl_grid(n, n, 64, true);
-  const size_t entries = (size_t)gr.slices * n;
-  WM_REQUIRE(workspace_bytes >= entries * 16 + (size_t)g * 8, WM_EWORKSPACE);
+  ClPlan pl;
+  const int rc = cl_prepare<CL_APCORE>(x && group && out && workspace && p > 0.0 && p < (double)INFINITY, n, n, d, metric, 1, g,
+                                       cl_aligned(x) && cl_aligned(workspace) && cl_aligned(out, 7), workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = gr.tiles_per_slice;
-  a.col_tiles = gr.col_tiles;
+  ClCarve ws{static_cast<char*>(workspace)};
+  ClArgs a = cl_args(x, n, x, n, d, pl.grid);
   a.labels = group;
   a.n_clusters = g;
   a.pw = p;
-  a.part_m = static_cast<double*>(workspace);
-  a.part_s = a.part_m + entries;
-  int* bounds = reinterpret_cast<int*>(a.part_s + entries);
+  a.part_m = ws.take<double>(pl.entries);
+  a.part_s = ws.take<double>(pl.entries);
+  int* bounds = ws.take<int>(2 * (size_t)g);
   a.bounds = bounds;
   cl_group_bounds<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(group, n, g, bounds);
   WM_LAUNCH_CHECK();
-  const int rc = cl_launch<CL_APCORE, 4>(a, gr, metric, st);
-  if (rc != WM_OK) return rc;
-  cl_apcore_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_m, a.part_s, gr.slices, n, group, bounds, g, p, out);
+  const int lrc = cl_launch<CL_APCORE>(a, pl.grid, metric, st);
+  if (lrc != WM_OK) return lrc;
+  cl_apcore_merge<<<wm_cdiv(n, CL_THREADS), CL_THREADS, 0, st>>>(a.part_m, a.part_s, pl.grid.slices, n, group, bounds, g, p, out);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-extern "C" size_t wm_mreach_query_workspace_bytes(int m, int n, int d) {
-  if (m <= 0 || m > CL_MAX_N || n <= 0 || n > CL_MAX_N || d <= 0) return 0;
-  return (size_t)cl_grid(m, n, 128, true).slices * m * 12 + 256;
-}
+extern "C" size_t wm_mreach_query_workspace_bytes(int m, int n, int d) { return cl_workspace_bytes<CL_MREACHQ>(m, n, d, 1, 1); }
 
 extern "C" int wm_mreach_query(const float* xq, const float* core_q, int m, const float* x, const float* core, int n, int d,
                                int metric, float inv_alpha, float* out_w, float* out_dist, int32_t* out_j, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  WM_REQUIRE(xq && core_q && x && core && out_w && out_dist && out_j && workspace, WM_EINVAL);
-  WM_REQUIRE(m > 0 && n > 0 && d > 0 && inv_alpha > 0.f, WM_EINVAL);
-  WM_REQUIRE(m <= CL_MAX_N && n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-             WM_EALIGN);
-  const ClGrid g = cl_grid(m, n, 128, true);
-  const size_t entries = (size_t)g.slices * m;
-  WM_REQUIRE(workspace_bytes >= entries * 12, WM_EWORKSPACE);
+  ClPlan pl;
+  const int rc = cl_prepare<CL_MREACHQ>(xq && core_q && x && core && out_w && out_dist && out_j && workspace && inv_alpha > 0.f, m,
+                                        n, d, metric, 1, 1, cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace),
+                                        workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = x;
-  a.n = n;
-  a.xr = xq;
-  a.nr = m;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
+  ClCarve ws{static_cast<char*>(workspace)};
+  ClArgs a = cl_args(xq, m, x, n, d, pl.grid);
   a.core = core;
   a.core_q = core_q;
   a.inv_alpha = inv_alpha;
-  a.part_w = static_cast<float*>(workspace);
-  a.part_d = a.part_w + entries;
-  a.part_j = reinterpret_cast<int*>(a.part_d + entries);
-  const int rc = cl_launch<CL_MREACHQ, 8>(a, g, metric, st);
-  if (rc != WM_OK) return rc;
-  cl_mreach_query_merge<<<wm_cdiv(m, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_d, a.part_j, g.slices, m, out_w, out_dist,
-                                                                      out_j);
+  a.part_w = ws.take<float>(pl.entries);
+  a.part_d = ws.take<float>(pl.entries);
+  a.part_j = ws.take<int>(pl.entries);
+  const int lrc = cl_launch<CL_MREACHQ>(a, pl.grid, metric, st);
+  if (lrc != WM_OK) return lrc;
+  cl_mreach_query_merge<<<wm_cdiv(m, CL_THREADS), CL_THREADS, 0, st>>>(a.part_w, a.part_d, a.part_j, pl.grid.slices, m, out_w,
+                                                                      out_dist, out_j);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
 extern "C" int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, int metric, int n_clusters,
                                     double* out, void* stream) {
-  WM_REQUIRE(x && labels && out, WM_EINVAL);
-  WM_REQUIRE(n > 0 && d > 0 && n_clusters >= 2 && n_clusters <= n, WM_EINVAL);
-  WM_REQUIRE(n <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0, WM_EALIGN);
+  const int rc = cl_check(x && labels && out && n_clusters >= 2 && n_clusters <= n, n, n, d, metric, 1, 1,
+                          cl_aligned(x) && cl_aligned(out, 7));
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = wm_zero_async(out, (size_t)n * n_clusters * sizeof(double), st);
   if (e != hipSuccess) return (int)e;
-  const ClGrid g = cl_grid(n, n, 64, false);
-  ClArgs a = {};
-  a.x = a.xr = x;
-  a.n = a.nr = n;
-  a.d = d;
-  a.tiles_per_slice = g.tiles_per_slice;
-  a.col_tiles = g.col_tiles;
+  const ClPlan pl = cl_plan<CL_SUMS>(n, n, 1, n_clusters);
+  ClArgs a = cl_args(x, n, x, n, d, pl.grid);
   a.labels = labels;
   a.n_clusters = n_clusters;
   a.out = out;
-  return cl_launch<CL_SUMS, 4>(a, g, metric, st);
-}
-
-extern "C" size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g) {
-  if (m <= 0 || m > CL_MAX_N || e <= 0 || e > CL_MAX_N || d <= 0 || g <= 0 || g > CL_MAX_N) return 0;
-  const ClGrid gr = cl_grid(m, e, 64, true, CL_GROUPMIN_SLICES);
-  return (gr.slices > 1 ? (size_t)gr.slices * m * g * 8 : 0) + 256;
+  return cl_launch<CL_SUMS>(a, pl.grid, metric, st);
 }
 
 namespace {
 
-// wm_group_min_dist (core_q = core = nullptr) and wm_group_min_mreach: one grid, one workspace layout, one merge.
+// wm_group_min_dist (core_q = core = nullptr) and wm_group_min_mreach.
 template <int MODE>
 int cl_group_min_run(const float* xq, const float* core_q, int m, const float* xe, const float* core, const int32_t* group,
                      int e, int d, int metric, int g, float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes,
                      void* stream) {
-  WM_REQUIRE(xq && xe && group && out_dist && out_j && workspace, WM_EINVAL);
-  WM_REQUIRE(MODE == CL_GROUPMIN || (core_q && core), WM_EINVAL);
-  WM_REQUIRE(m > 0 && e > 0 && d > 0 && g > 0, WM_EINVAL);
-  WM_REQUIRE(m <= CL_MAX_N && e <= CL_MAX_N && g <= CL_MAX_N && cl_shape_ok(d, metric), WM_EUNSUPPORTED);
-  WM_REQUIRE((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(xe) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-             WM_EALIGN);
-  const ClGrid gr = cl_grid(m, e, 64, true, CL_GROUPMIN_SLICES);
-  const size_t entries = gr.slices > 1 ? (size_t)gr.slices * m * g : 0;
-  WM_REQUIRE(workspace_bytes >= entries * 8, WM_EWORKSPACE);
+  ClPlan pl;
+  const int rc = cl_prepare<MODE>(xq && xe && group && out_dist && out_j && workspace && (MODE == CL_GROUPMIN || (core_q && core)),
+                                  m, e, d, metric, 1, g, cl_aligned(xq) && cl_aligned(xe) && cl_aligned(workspace),
+                                  workspace_bytes, &pl);
+  if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ClArgs a = {};
-  a.x = xe;
-  a.n = e;
-  a.xr = xq;
-  a.nr = m;
-  a.d = d;
-  a.tiles_per_slice = gr.tiles_per_slice;
-  a.col_tiles = gr.col_tiles;
+  ClCarve ws{static_cast<char*>(workspace)};
+  ClArgs a = cl_args(xq, m, xe, e, d, pl.grid);
   a.core_q = core_q;
   a.core = core;
   a.labels = group;
   a.n_clusters = g;
-  a.group_d = gr.slices > 1 ? static_cast<float*>(workspace) : out_dist;
-  a.group_j = gr.slices > 1 ? reinterpret_cast<int*>(a.group_d + entries) : out_j;
-  const int rc = cl_launch<MODE, 4>(a, gr, metric, st);
-  if (rc != WM_OK || gr.slices == 1) return rc;
-  const size_t blocks = ((size_t)m * g + CL_THREADS - 1) / CL_THREADS;
-  cl_group_min_merge<<<(unsigned)(blocks < 65536 ? blocks : 65536), CL_THREADS, 0, st>>>(a.group_d, a.group_j, group, gr.slices,
-                                                                                       gr.tiles_per_slice, m, e, g, out_dist,
-                                                                                       out_j);
+  a.group_d = pl.direct ? out_dist : ws.take<float>(pl.entries);
+  a.group_j = pl.direct ? out_j : ws.take<int>(pl.entries);
+  const int lrc = cl_launch<MODE>(a, pl.grid, metric, st);
+  if (lrc != WM_OK || pl.direct) return lrc;
+  cl_group_min_merge<<<cl_grid_1d((size_t)m * g), CL_THREADS, 0, st>>>(a.group_d, a.group_j, group, pl.grid.slices,
+                                                                      pl.grid.tiles_per_slice, m, e, g, out_dist, out_j);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
 }  // namespace
+
+extern "C" size_t wm_group_min_dist_workspace_bytes(int m, int e, int d, int g) {
+  return cl_workspace_bytes<CL_GROUPMIN>(m, e, d, 1, g);
+}
 
 extern "C" int wm_group_min_dist(const float* xq, int m, const float* xe, const int32_t* group, int e, int d, int metric, int g,
                                  float* out_dist, int32_t* out_j, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1313,3 +1305,4 @@ extern "C" int wm_group_min_mreach(const float* xq, const float* core_q, int m, 
   return cl_group_min_run<CL_GROUPMIN_MR>(xq, core_q, m, xe, core, group, e, d, metric, g, out_w, out_j, workspace,
                                           workspace_bytes, stream);
 }
+

@@ -26,7 +26,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import check, ptr, require_gpu, stream_ptr, workspace
 
 MAX_FEATURES = 4096
 
@@ -61,21 +61,13 @@ def _f64_on(v, device, cols: Optional[int] = None):
     return t.contiguous()
 
 
-def _workspace(need: int, what: str, device):
-    import torch
-
-    if need == 0:
-        raise ValueError(f"{what}: unsupported sizes")
-    return torch.empty(need, dtype=torch.uint8, device=device)
-
-
 def _means(xp):
     import torch
 
     n, d = xp.shape
     lib = _lib.load()
     need = lib.wm_pca_mean_workspace_bytes(n, d)
-    ws = _workspace(need, f"column_means n={n} d={d}", xp.device)
+    ws = workspace(need, f"column_means n={n} d={d}: unsupported sizes", xp.device)
     mean = torch.empty(d, dtype=torch.float64, device=xp.device)
     check(lib.wm_pca_mean(ptr(xp), n, d, ptr(mean), ptr(ws), need, stream_ptr()), "wm_pca_mean")
     return mean
@@ -87,7 +79,7 @@ def _gram(xp, mean):
     n, d = xp.shape
     lib = _lib.load()
     need = lib.wm_pca_gram_workspace_bytes(n, d)
-    ws = _workspace(need, f"covariance n={n} d={d}", xp.device)
+    ws = workspace(need, f"covariance n={n} d={d}: unsupported sizes", xp.device)
     out = torch.empty((d, d), dtype=torch.float64, device=xp.device)
     check(lib.wm_pca_gram(ptr(xp), n, d, ptr(mean), ptr(out), ptr(ws), need, stream_ptr()), "wm_pca_gram")
     return out
@@ -99,7 +91,7 @@ def _project(xp, w, mean):
     (n, d), m = xp.shape, w.shape[0]
     lib = _lib.load()
     need = lib.wm_pca_project_workspace_bytes(n, d, m)
-    ws = _workspace(need, f"project n={n} d={d} m={m}", xp.device)
+    ws = workspace(need, f"project n={n} d={d} m={m}: unsupported sizes", xp.device)
     out = torch.empty((n, m), dtype=torch.float32, device=xp.device)
     check(lib.wm_pca_project(ptr(xp), n, d, ptr(mean), ptr(w), m, ptr(out), ptr(ws), need, stream_ptr()), "wm_pca_project")
     return out
@@ -172,7 +164,7 @@ def reconstruct(y, components, mean=None):
     mp = None if mean is None else _f64_on(mean, y.device, dp)
     lib = _lib.load()
     need = lib.wm_pca_reconstruct_workspace_bytes(n, m, dp)
-    ws = _workspace(need, f"reconstruct n={n} m={m} d={dp}", y.device)
+    ws = workspace(need, f"reconstruct n={n} m={m} d={dp}: unsupported sizes", y.device)
     out = torch.empty((n, dp), dtype=torch.float32, device=y.device)
     check(lib.wm_pca_reconstruct(ptr(y), n, m, ptr(w), dp, ptr(mp), ptr(out), ptr(ws), need, stream_ptr()),
           "wm_pca_reconstruct")

@@ -53,7 +53,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr, require_gpu, stream_ptr
+from ._lib import check, ptr, require_gpu, stream_ptr, workspace
 from .cluster import _prep, metric_code
 
 MAX_NEIGHBORS = 64
@@ -176,9 +176,7 @@ def knn_graph(x, k: int, metric: str = "euclidean"):
         raise ValueError(f"k ({k}) must be in [1, n_samples = {n}]")
     lib = _lib.load()
     need = lib.wm_knn_graph_workspace_bytes(n, d, k)
-    if need == 0:
-        raise ValueError(f"knn_graph: unsupported sizes n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"knn_graph: unsupported sizes n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})", x.device)
     dist = torch.empty((n, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
     check(lib.wm_knn_graph(ptr(x), n, d, code, k, ptr(dist), ptr(idx), ptr(ws), need, stream_ptr()), "wm_knn_graph")
@@ -223,9 +221,7 @@ def knn_query(xq, x, k: int, metric: str = "euclidean"):
         raise ValueError(f"k ({k}) must be in [1, n_samples = {n}]")
     lib = _lib.load()
     need = lib.wm_knn_query_workspace_bytes(m, n, d, k)
-    if need == 0:
-        raise ValueError(f"knn_query: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = workspace(need, f"knn_query: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})", x.device)
     dist = torch.empty((m, k), dtype=torch.float32, device=x.device)
     idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
     check(lib.wm_knn_query(ptr(xq), m, ptr(x), n, d, code, k, ptr(dist), ptr(idx), ptr(ws), need, stream_ptr()), "wm_knn_query")
@@ -277,8 +273,7 @@ def neighbor_ranks(xq, x, idx, metric: str = "euclidean", exclude_self: bool = F
         raise ValueError(f"exclude_self needs the rows of x themselves as queries (m = {m}, n = {n})")
     lib = _lib.load()
     need = lib.wm_rank_query_workspace_bytes(m, n, d, k)
-    if need == 0:
-        raise ValueError(f"neighbor_ranks: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})")
+    ws = workspace(need, f"neighbor_ranks: unsupported sizes m={m} n={n} d={d} k={k} (k <= {MAX_NEIGHBORS})", x.device)
     thr = pair_distances(xq, x, idx, metric)
     # the kernel wants every row's thresholds sorted by (distance, index): a stable sort by the index, then by the distance
     by_j = torch.sort(idx, dim=1, stable=True).indices
@@ -286,7 +281,6 @@ def neighbor_ranks(xq, x, idx, metric: str = "euclidean", exclude_self: bool = F
     t_sorted, j_sorted = thr.gather(1, order).contiguous(), idx.gather(1, order).contiguous()
     skip = (torch.arange(m, dtype=torch.int32, device=x.device) if exclude_self
             else torch.full((m,), -1, dtype=torch.int32, device=x.device))
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
     count = torch.empty((m, k), dtype=torch.int32, device=x.device)
     check(lib.wm_rank_query(ptr(xq), m, ptr(x), n, d, code, ptr(t_sorted), ptr(j_sorted), ptr(skip), k, ptr(count), ptr(ws),
                             need, stream_ptr()), "wm_rank_query")

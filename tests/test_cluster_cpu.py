@@ -289,6 +289,50 @@ def test_entry_points_validate_before_any_launch():
     assert lib.wm_mreach_min_edge_workspace_bytes(0, 512) == 0
 
 
+def test_every_entry_point_checks_in_one_order_against_its_own_size_function():
+    """Invalid, then unsupported, then misaligned, then workspace too small, for every entry point of cluster.hip; and
+    every size function is exactly its entry point's requirement plus 256.  9 or 65 rows against 65 columns are two
+    column slices, so every mode needs its planes.  The pointers are stand-ins: every call returns before a launch."""
+    from ssl_wafermap_amd import _lib
+
+    lib = _lib.load()
+    a, cols, k, g = 4096, 65, 2, 3
+    # name -> (rows of the first matrix, the size function of (rows, d) or None, the call of (x, rows, d, ws_bytes))
+    table = {
+        "wm_core_distance": (65, lambda r, d: lib.wm_core_distance_workspace_bytes(r, d, k),
+                             lambda x, r, d, wb: lib.wm_core_distance(x, r, d, 0, k, a, a, wb, None)),
+        "wm_knn_graph": (65, lambda r, d: lib.wm_knn_graph_workspace_bytes(r, d, k),
+                         lambda x, r, d, wb: lib.wm_knn_graph(x, r, d, 0, k, a, a, a, wb, None)),
+        "wm_knn_query": (9, lambda r, d: lib.wm_knn_query_workspace_bytes(r, cols, d, k),
+                         lambda x, r, d, wb: lib.wm_knn_query(x, r, a, cols, d, 0, k, a, a, a, wb, None)),
+        "wm_rank_query": (9, lambda r, d: lib.wm_rank_query_workspace_bytes(r, cols, d, k),
+                          lambda x, r, d, wb: lib.wm_rank_query(x, r, a, cols, d, 0, a, a, a, k, a, a, wb, None)),
+        "wm_mreach_min_edge": (65, lambda r, d: lib.wm_mreach_min_edge_workspace_bytes(r, d),
+                               lambda x, r, d, wb: lib.wm_mreach_min_edge(x, a, a, r, d, 0, 1.0, a, a, a, wb, None)),
+        "wm_mreach_min_edge_grouped": (65, lambda r, d: lib.wm_mreach_min_edge_grouped_workspace_bytes(r, d, g),
+                                       lambda x, r, d, wb: lib.wm_mreach_min_edge_grouped(x, a, a, a, r, d, 0, g, a, a, a, wb, None)),
+        "wm_allpoints_core": (65, lambda r, d: lib.wm_allpoints_core_workspace_bytes(r, d, g),
+                              lambda x, r, d, wb: lib.wm_allpoints_core(x, a, r, d, 0, g, 8.0, a, a, wb, None)),
+        "wm_mreach_query": (9, lambda r, d: lib.wm_mreach_query_workspace_bytes(r, cols, d),
+                            lambda x, r, d, wb: lib.wm_mreach_query(x, a, r, a, a, cols, d, 0, 1.0, a, a, a, a, wb, None)),
+        "wm_group_min_dist": (9, lambda r, d: lib.wm_group_min_dist_workspace_bytes(r, cols, d, g),
+                              lambda x, r, d, wb: lib.wm_group_min_dist(x, r, a, a, cols, d, 0, g, a, a, a, wb, None)),
+        "wm_group_min_mreach": (9, lambda r, d: lib.wm_group_min_mreach_workspace_bytes(r, cols, d, g),
+                                lambda x, r, d, wb: lib.wm_group_min_mreach(x, a, r, a, a, a, cols, d, 0, g, a, a, a, wb, None)),
+        "wm_pair_dist": (9, None, lambda x, r, d, wb: lib.wm_pair_dist(x, r, a, cols, d, 0, a, k, a, None)),
+        "wm_cluster_dist_sums": (65, None, lambda x, r, d, wb: lib.wm_cluster_dist_sums(x, a, r, d, 0, g, a, None)),
+    }
+    assert len(table) == 12 and sum(size is not None for _, size, _ in table.values()) == 10
+    for name, (rows, size, call) in table.items():
+        need = size(rows, 8) if size else 0
+        if size:
+            assert need > 257, name
+            assert call(a, rows, 8, need - 257) == -3, name  # one byte short of need - 256
+        assert call(a + 8, rows, 8, need) == -4, name  # misaligned first matrix, everything else valid
+        assert call(a + 8, rows, 6, need) == -2, name  # d = 6 wins over the misaligned pointer
+        assert call(a + 8, 0, 6, need) == -1, name  # no rows wins over both
+
+
 def test_host_scores_match_sklearn(blobs):
     from sklearn import metrics
 
