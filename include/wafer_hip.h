@@ -1044,6 +1044,51 @@ size_t wm_pca_reconstruct_workspace_bytes(int n, int m, int d);
 int wm_pca_reconstruct(const float* y, int n, int m, const double* w, int d, const double* mean, float* out, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian mixture on an embedding matrix (sklearn.mixture.GaussianMixture; mixture.py): the passes over the rows of
+ * the E-step and the M-step in float64.  The Cholesky factors of the k covariance matrices are host code.  Tile
+ * sizes, slab / slice rules and summation orders are stated in csrc/gmm.hip.
+ *
+ * Common to all: x float32 [n][ld] row-major with the true feature count d and the row pitch ld, d <= ld, ld % 4 == 0
+ * and x 16-byte aligned; whatever columns d .. ld-1 hold is never used.  Parameters are float64 with pitch d:
+ * mean [k][d], inv_var [k][d], pchol [k][d][d], resp / out of the E-step [n][k].  1 <= n <= 2^24, 1 <= k <= 1024,
+ * d <= 1024 (logprob_diag, weighted_sums, scatter_diag) or d <= 256 (logprob_full, scatter_full).  Every pointer is
+ * aligned to its element, the workspace to 16 bytes; the workspace is owned by the caller and holds at least the
+ * companion's byte count (0: unsupported sizes; the companions launch nothing; the log-probability kernels report a
+ * fixed token size and store nothing there).  No atomics, no allocation, no synchronisation; every sum has an order
+ * that depends on the sizes alone: two calls give the same bits.
+ *
+ * wm_gmm_logprob_diag: out[i][c] = cst[c] - 0.5 * sum_f (double(x[i][f]) - mean[c][f])^2 * inv_var[c][f], one double
+ * accumulator, f ascending. */
+size_t wm_gmm_logprob_diag_workspace_bytes(int n, int d, int ld, int k);
+int wm_gmm_logprob_diag(const float* x, int n, int d, int ld, const double* mean, const double* inv_var, const double* cst,
+                        int k, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* out[i][c] = cst[c] - 0.5 * || (x_i - mean_c) P_c ||^2 with P_c = pchol[c] upper triangular: only pchol[c][f][j] with
+ * f <= j is read.  The row is centred before it is multiplied. */
+size_t wm_gmm_logprob_full_workspace_bytes(int n, int d, int ld, int k);
+int wm_gmm_logprob_full(const float* x, int n, int d, int ld, const double* mean, const double* pchol, const double* cst,
+                        int k, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Per row of wlp [n][k]: m = max_c, lpn[i] = m + log(sum_c exp(wlp - m)) with the sum in component order, the row
+ * overwritten with exp(wlp - lpn[i]), label[i] = the argmax (the lowest index wins a tie); *lpn_sum = the sum of lpn
+ * over slabs of 256 rows (a fixed tree inside a slab), the slabs added in slab order.  k == 1: resp == 1, lpn == wlp. */
+size_t wm_gmm_normalize_workspace_bytes(int n, int k);
+int wm_gmm_normalize(double* wlp_inout, int n, int k, double* lpn, int32_t* label, double* lpn_sum, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* nk[c] = sum_i resp[i][c], sx[c][f] = sum_i resp[i][c] * x[i][f] (sx [k][d]); nk is column d of the same product (a
+ * column of exact ones).  Rows are cut into slices, the slices' partial planes added in slice order. */
+size_t wm_gmm_weighted_sums_workspace_bytes(int n, int d, int ld, int k);
+int wm_gmm_weighted_sums(const float* x, int n, int d, int ld, const double* resp, int k, double* nk, double* sx,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* out[c][f] = sum_i resp[i][c] * (x[i][f] - mean[c][f])^2: slabs of rows in row order, the slabs added in slab order. */
+size_t wm_gmm_scatter_diag_workspace_bytes(int n, int d, int ld, int k);
+int wm_gmm_scatter_diag(const float* x, int n, int d, int ld, const double* resp, int k, const double* mean, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* out[c][d][d] = sum_i resp[i][c] (x_i - mean_c)(x_i - mean_c)^T; exactly symmetric (tiles on and below the diagonal
+ * are computed, the merge mirrors them). */
+size_t wm_gmm_scatter_full_workspace_bytes(int n, int d, int ld, int k);
+int wm_gmm_scatter_full(const float* x, int n, int d, int ld, const double* resp, int k, const double* mean, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

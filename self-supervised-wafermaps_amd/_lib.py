@@ -328,8 +328,26 @@ SIGNATURES = {
     "wm_pca_project": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wm_pca_reconstruct_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wm_pca_reconstruct": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- Gaussian mixture
+    "wm_gmm_logprob_diag_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_gmm_logprob_diag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "wm_gmm_logprob_full_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_gmm_logprob_full": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "wm_gmm_normalize_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_gmm_normalize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_gmm_weighted_sums_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_gmm_weighted_sums": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    "wm_gmm_scatter_diag_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_gmm_scatter_diag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "wm_gmm_scatter_full_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_gmm_scatter_full": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
     # ---- UMAP
-    "wm_umap_smooth_knn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wm_umap_smooth_knn":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
                                c_double, c_uint32, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "wm_umap_label_intersect": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p,
