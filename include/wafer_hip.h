@@ -1089,6 +1089,42 @@ size_t wm_gmm_scatter_full_workspace_bytes(int n, int d, int ld, int k);
 int wm_gmm_scatter_full(const float* x, int n, int d, int ld, const double* resp, int k, const double* mean, double* out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Laplacian eigenmaps (manifold.py: laplacian_eigenpairs, spectral_layout, SpectralEmbedding): the device side of a
+ * thick-restart Lanczos iteration with full reorthogonalisation on N = D^-1/2 G D^-1/2 in float64.  The small
+ * eigenproblem of T and the component search are host code.  Every summation order is stated in csrc/spectral.hip.
+ *
+ * Common to the four: G is a symmetric CSR graph, indptr int32 [n + 1] rising from 0 to nnz, indices int32 [nnz] in
+ * [0, n), data float32 [nnz] (the kernels trust them: manifold.py checks them once); 1 <= n <= 2^24; a basis is
+ * row-major [n][ld] float64 with ld <= 256; every pointer aligned to its element, the workspace to 16 bytes; the
+ * workspace is owned by the caller and holds at least the companion's byte count (0: unsupported sizes; the companions
+ * launch nothing; degree, matvec and rotate report a fixed token size and store nothing there).  No atomics, no
+ * allocation, no synchronisation: two calls give the same bits.
+ *
+ * wm_spec_degree: deg[i] = the double sum of row i in column order; dinv[i] = 1 / sqrt(deg[i]), 0 for an empty row. */
+size_t wm_spec_degree_workspace_bytes(int n);
+int wm_spec_degree(const int32_t* indptr, const float* data, int n, double* deg, double* dinv, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* w[i] = dinv[i] * sum_p data[p] * (dinv[col[p]] * v[col[p] * ldv]): v is a column of a basis of pitch ldv (1: a plain
+ * vector), w a plain vector; v and w must not overlap. */
+size_t wm_spec_matvec_workspace_bytes(int n);
+int wm_spec_matvec(const int32_t* indptr, const int32_t* indices, const float* data, const double* dinv, const double* v,
+                   int ldv, int n, double* w, void* workspace, size_t workspace_bytes, void* stream);
+/* The tail of Lanczos step j (0 <= j < m < ldv).  comp int32 [n]: the component label of every row in [0, ncomp),
+ * 1 <= ncomp <= 256; u float64 [n]: the unit trivial vectors of the components (disjoint supports) in one array.  Twice:
+ * w -= u (u . w) per component, then w -= V[:, 0..j] (V[:, 0..j]^T w).  The coefficients of the two passes are added
+ * into T[0..j][j], beta = |w| goes to T[j + 1][j] (if j + 1 < m) and to the double behind T's m x m cells, and
+ * V[:, j + 1] = w / beta.  beta < n 2^-53: the int64 behind that double is set to j + 1 if it was 0 and the new column
+ * is exact zeros.  w is overwritten with the unnormalised residual.  T: row-major [m][m] + 2 cells of 8 bytes. */
+size_t wm_spec_orthonormalise_workspace_bytes(int n, int ldv, int ncomp);
+int wm_spec_orthonormalise(double* w, double* V, int n, int ldv, int j, const int32_t* comp, int ncomp, const double* u,
+                           double* T, int m, void* workspace, size_t workspace_bytes, void* stream);
+/* out[n][q] (pitch ldo) = V[n][m] (pitch ldv) @ S[m][q] (pitch lds) on float64 MFMA tiles, k ascending; out is a second
+ * buffer (V == out: WM_EINVAL); m, q <= 256. */
+size_t wm_spec_rotate_workspace_bytes(int n, int m, int q);
+int wm_spec_rotate(const double* V, int ldv, const double* S, int lds, int n, int m, int q, double* out, int ldo,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -5,7 +5,7 @@ path (ssl_wafermap_amd.manifold).
 
     python scripts/embedding_umap_amd.py --embeddings tests/golden/simsiam_preds_subset.npz
                                          [--neighbors 15] [--components 2] [--min-dist 0.1] [--epochs N]
-                                         [--init spectral|pca|random] [--seed 0] [--no-scale] [--rows N] [--out DIR]
+                                         [--init spectral|spectral_device|pca|random] [--seed 0] [--no-scale] [--rows N] [--out DIR]
                                          [--densmap [--dens-lambda 2.0] [--dens-frac 0.3] [--dens-var-shift 0.1]]
                                          [--label-frac F] [--holdout N]
 
@@ -96,7 +96,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--holdout", type=int, default=0, help="fit on all but the last N rows and transform those")
     ap.add_argument("--quality", action="store_true",
                     help="trustworthiness, continuity and neighbour preservation on ALL fitted rows (HIP rank kernels)")
-    ap.add_argument("--init", choices=["spectral", "pca", "random"], default="spectral")
+    ap.add_argument("--init", choices=["spectral", "spectral_device", "pca", "random"], default="spectral")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rows", type=int, default=0, help="use the first N rows only")
     ap.add_argument("--no-scale", action="store_true")

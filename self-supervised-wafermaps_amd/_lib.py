@@ -346,6 +346,18 @@ SIGNATURES = {
     "wm_gmm_scatter_full_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_gmm_scatter_full": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    # ---- Laplacian eigenmaps
+    "wm_spec_degree_workspace_bytes": (c_size_t, [c_int]),
+    "wm_spec_degree": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_spec_matvec_workspace_bytes": (c_size_t, [c_int]),
+    "wm_spec_matvec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "wm_spec_orthonormalise_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_spec_orthonormalise": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p, c_size_t, c_void_p]),
+    "wm_spec_rotate_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_spec_rotate": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                               c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,

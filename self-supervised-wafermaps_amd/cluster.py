@@ -1713,3 +1713,36 @@ class KMeans:
         c = self._centres_padded.unsqueeze(0)
         cols, dist = _kmeans_assign(xp, c)
         return -float(_kmeans_update(xp, cols, dist, None, c)[2][0])
+
+
+class SpectralClustering:
+    """sklearn.cluster.SpectralClustering on device tensors with a nearest-neighbour affinity and
+    assign_labels="kmeans": the rows of the first `n_clusters` columns of the spectral embedding of the affinity graph
+    (`manifold.spectral_embedding`, the first column kept) are clustered by `KMeans` (k-means++, `n_init` restarts).
+    affinity: "connectivity" (sklearn's nearest_neighbors, 0.5 (A + A^T) of the 0/1 kNN graph, self included) or
+    "fuzzy" (UMAP's fuzzy simplicial set); the kNN graph is exact.  `fit(x)` sets `labels_` (numpy int64 [n]),
+    `affinity_matrix_` (manifold.CSR), `embedding_` (float32 [n, n_clusters] on the device) and `converged_`."""
+
+    def __init__(self, n_clusters: int = 8, *, n_neighbors: int = 10, affinity: str = "connectivity", metric: str = "euclidean",
+                 n_init: int = 10, random_state=0, tol: float = 1e-6):
+        metric_code(metric)
+        if affinity not in ("connectivity", "fuzzy"):
+            raise ValueError(f"affinity must be 'connectivity' or 'fuzzy' ({affinity!r} given)")
+        if int(n_clusters) < 1 or int(n_neighbors) < 1 or int(n_init) < 1:
+            raise ValueError("n_clusters, n_neighbors and n_init must be at least 1")
+        self.n_clusters, self.n_neighbors, self.affinity, self.metric = int(n_clusters), int(n_neighbors), affinity, metric
+        self.n_init, self.random_state, self.tol = int(n_init), random_state, float(tol)
+        self.labels_ = self.affinity_matrix_ = self.embedding_ = self.converged_ = None
+
+    def fit(self, x, y=None) -> "SpectralClustering":
+        from . import manifold
+
+        graph = manifold.affinity_graph(x, min(self.n_neighbors, x.shape[0]), self.metric, self.affinity)
+        emb, _, _, self.converged_ = manifold.spectral_embedding(graph, self.n_clusters, self.tol, drop_first=False)
+        self.affinity_matrix_ = graph
+        self.embedding_ = emb.float().contiguous()
+        self.labels_ = KMeans(self.n_clusters, n_init=self.n_init, random_state=self.random_state).fit(self.embedding_).labels_
+        return self
+
+    def fit_predict(self, x, y=None) -> np.ndarray:
+        return self.fit(x).labels_

@@ -41,6 +41,14 @@ and its converse) is scored on ALL rows:
      (distance, index) order (wm_rank_query, one all-pairs pass with integer counts); the scores are float64 arithmetic
      on those integer ranks on the host (`quality_from_ranks`).
 
+Laplacian eigenmaps of a graph (`laplacian_eigenpairs`, `spectral_layout`, `SpectralEmbedding`, and
+`cluster.SpectralClustering` on top of them; `init="spectral_device"` of the estimators above):
+  8. a thick-restart Lanczos eigensolver with full reorthogonalisation on N = D^-1/2 G D^-1/2 in float64
+     (csrc/spectral.hip: wm_spec_degree, wm_spec_matvec, wm_spec_orthonormalise, wm_spec_rotate); the eigenvalue-0 pairs of
+     the connected components (found by scipy on the host) are deflated in closed form; the host takes numpy's eigh of the
+     small matrix T once per restart cycle, the cycle's only synchronisation.  Two solves give the same bits.
+`init="spectral"` keeps the host path below.
+
 Not built: target_metric other than "categorical", inverse_transform, update (NotImplementedError naming the feature).
 Only local_connectivity = 1 and set_op_mix_ratio = 1 are supported.
 """
@@ -738,14 +746,543 @@ def _pca_init(x, dim: int):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Laplacian eigenmaps
+
+SPEC_MAX_BASIS = 255  # Lanczos steps per cycle the kernels take (the basis has one more column, 256 at most)
+SPEC_MAX_COMPONENTS = 256  # connected components whose trivial vectors the device solver deflates
+SPEC_DENSE_ROWS = 512  # graphs of at most this many rows are solved densely on the host
+
+
+def _check_graph(graph: CSR) -> int:
+    """What the spectral kernels trust about a graph, checked once on the host; returns n."""
+    import torch
+
+    require_gpu(graph.indptr, graph.indices, graph.data)
+    if graph.indptr.dtype != torch.int32 or graph.indices.dtype != torch.int32 or graph.data.dtype != torch.float32:
+        raise ValueError("graph: indptr, indices int32 and data float32 expected")
+    if graph.indptr.dim() != 1 or graph.indptr.numel() < 2 or graph.indices.dim() != 1 or graph.indices.shape != graph.data.shape:
+        raise ValueError("graph: indptr [n + 1], indices [nnz] and data [nnz] expected")
+    n = graph.indptr.numel() - 1
+    _check_csr(graph.indptr, graph.indices.numel())
+    if graph.indices.numel() and (int(graph.indices.min()) < 0 or int(graph.indices.max()) >= n):
+        raise ValueError("indices must lie in [0, n)")
+    return n
+
+
+def _token_ws(need: int, what: str, device, ws=None):
+    """(workspace, byte count) of an entry point that stores nothing in its workspace: `ws` when the caller keeps one
+    (`token_workspace`, once per solve), else a new tensor.  ValueError(what) for sizes the kernel does not take."""
+    if ws is None or need == 0 or ws.numel() < need:
+        ws = workspace(need, what, device)
+    return ws, need
+
+
+def token_workspace(device):
+    """The 256 bytes that `laplacian_degree`, `laplacian_matvec` and `basis_rotate` ask for and never touch; a caller
+    that issues many of them allocates it once and passes it as `ws`."""
+    return workspace(256, "token workspace", device)
+
+
+def laplacian_degree(graph: CSR, ws=None):
+    """(deg, dinv) float64 [n] on the device: the row sums of `graph` in column order and 1 / sqrt(deg), 0 for an empty
+    row (csrc/spectral.hip: wm_spec_degree)."""
+    import torch
+
+    n = _check_graph(graph)
+    lib = _lib.load()
+    ws, need = _token_ws(lib.wm_spec_degree_workspace_bytes(n), f"laplacian_degree: unsupported n = {n}", graph.data.device, ws)
+    deg = torch.empty(n, dtype=torch.float64, device=graph.data.device)
+    dinv = torch.empty_like(deg)
+    check(lib.wm_spec_degree(ptr(graph.indptr), ptr(graph.data), n, ptr(deg), ptr(dinv), ptr(ws), need, stream_ptr()),
+          "wm_spec_degree")
+    return deg, dinv
+
+
+def _basis_column(v, col: int):
+    """(pointer, pitch) of column `col` of a row-major float64 basis [n, ld], or of a plain vector [n] (col = 0)."""
+    import torch
+
+    require_gpu(v)
+    if v.dtype != torch.float64 or v.dim() not in (1, 2):
+        raise ValueError("a float64 vector [n] or basis [n, ld] expected")
+    ld = 1 if v.dim() == 1 else v.shape[1]
+    if not 0 <= col < ld:
+        raise ValueError(f"column {col} outside the basis of {ld}")
+    return ptr(v) + 8 * col, ld
+
+
+def laplacian_matvec(graph: CSR, dinv, v, col: int = 0, out=None, checked: bool = False, ws=None):
+    """w = D^-1/2 G D^-1/2 v float64 [n] on the device (wm_spec_matvec); v is a vector [n] or column `col` of a basis
+    [n, ld].  `checked`: the caller has validated the graph already; `ws`: the caller's `token_workspace`."""
+    import torch
+
+    n = graph.indptr.numel() - 1 if checked else _check_graph(graph)
+    vp, ld = _basis_column(v, col)
+    require_gpu(dinv)
+    if dinv.dtype != torch.float64 or dinv.shape != (n,) or v.shape[0] != n:
+        raise ValueError(f"dinv float64 [{n}] and v with {n} rows expected")
+    out = torch.empty(n, dtype=torch.float64, device=v.device) if out is None else out
+    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous():
+        raise ValueError(f"out float64 [{n}] expected")
+    lib = _lib.load()
+    ws, need = _token_ws(lib.wm_spec_matvec_workspace_bytes(n), f"laplacian_matvec: unsupported n = {n}", v.device, ws)
+    check(lib.wm_spec_matvec(ptr(graph.indptr), ptr(graph.indices), ptr(graph.data), ptr(dinv), vp, ld, n, ptr(out), ptr(ws),
+                             need, stream_ptr()), "wm_spec_matvec")
+    return out
+
+
+def lanczos_workspace(n: int, ldv: int, ncomp: int, device):
+    """The workspace of `lanczos_orthonormalise` for these sizes, allocated once per solve."""
+    need = _lib.load().wm_spec_orthonormalise_workspace_bytes(int(n), int(ldv), int(ncomp))
+    return workspace(need, f"lanczos: unsupported sizes n={n} basis={ldv} (<= {SPEC_MAX_BASIS + 1}) components={ncomp} "
+                           f"(<= {SPEC_MAX_COMPONENTS})", device)
+
+
+def lanczos_orthonormalise(w, V, j: int, comp, ncomp: int, u, T, m: int, ws=None):
+    """The tail of Lanczos step j in place (wm_spec_orthonormalise): w float64 [n] is orthogonalised twice against the
+    unit trivial vectors u float64 [n] (component labels comp int32 [n] in [0, ncomp)) and against V[:, :j + 1] (V float64
+    [n, ldv], m < ldv); the summed coefficients go to T[:j + 1, j], |w| to T[j + 1, j] and T.flat[m m], w / |w| to
+    V[:, j + 1].  T float64 [m m + 2]: the flag word T[m m + 1] (int64) is set to j + 1 on a breakdown."""
+    import torch
+
+    require_gpu(w, V, comp, u, T)
+    if V.dim() != 2 or V.dtype != torch.float64 or w.dtype != torch.float64 or u.dtype != torch.float64 or T.dtype != torch.float64:
+        raise ValueError("w, u float64 [n], V float64 [n, ldv] and T float64 expected")
+    n, ldv = V.shape
+    if w.shape != (n,) or u.shape != (n,) or comp.shape != (n,) or comp.dtype != torch.int32:
+        raise ValueError(f"w, u float64 [{n}] and comp int32 [{n}] expected")
+    if not (0 <= j < m < ldv) or T.numel() != m * m + 2:
+        raise ValueError("0 <= j < m < ldv and T of m m + 2 cells expected")
+    ws = lanczos_workspace(n, ldv, ncomp, V.device) if ws is None else ws
+    check(_lib.load().wm_spec_orthonormalise(ptr(w), ptr(V), n, ldv, int(j), ptr(comp), int(ncomp), ptr(u), ptr(T), int(m), ptr(ws),
+                                             ws.numel(), stream_ptr()), "wm_spec_orthonormalise")
+
+
+def basis_rotate(V, S, m: Optional[int] = None, out=None, ws=None):
+    """out[:, :q] = V[:, :m] @ S float64 on the device (wm_spec_rotate): V [n, ldv], S [m, q] (tensor or numpy array);
+    `out` a second buffer [n, ldo >= q] (a new [n, q] when None).  Returns out."""
+    import torch
+
+    S = torch.as_tensor(np.ascontiguousarray(S) if isinstance(S, np.ndarray) else S, dtype=torch.float64).to(V.device).contiguous()
+    require_gpu(V, S)
+    if V.dim() != 2 or S.dim() != 2 or V.dtype != torch.float64:
+        raise ValueError("V float64 [n, ldv] and S float64 [m, q] expected")
+    m = S.shape[0] if m is None else int(m)
+    (n, ldv), q = V.shape, S.shape[1]
+    if S.shape[0] != m or not 1 <= m <= ldv or q < 1:
+        raise ValueError(f"S [{m}, q >= 1] with m <= {ldv} expected")
+    out = torch.empty((n, q), dtype=torch.float64, device=V.device) if out is None else out
+    require_gpu(out)
+    if out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < q or out.data_ptr() == V.data_ptr():
+        raise ValueError(f"out float64 [{n}, >= {q}], not V itself, expected")
+    lib = _lib.load()
+    ws, need = _token_ws(lib.wm_spec_rotate_workspace_bytes(n, m, q), f"basis_rotate: unsupported sizes n={n} m={m} q={q}", V.device, ws)
+    check(lib.wm_spec_rotate(ptr(V), ldv, ptr(S), q, n, m, q, ptr(out), out.shape[1], ptr(ws), need, stream_ptr()), "wm_spec_rotate")
+    return out
+
+
+def graph_components(graph: CSR):
+    """(ncomp, labels int32 [n]) of the graph's connected components on the host (scipy), explicit zeros being no edges;
+    the labels are numbered by each component's smallest row."""
+    import scipy.sparse.csgraph
+
+    g = graph.to_scipy().copy()  # (host tensors share their memory with scipy's arrays: never edit the caller's graph)
+    g.eliminate_zeros()
+    ncomp, labels = scipy.sparse.csgraph.connected_components(g, directed=False)
+    first = np.unique(labels, return_index=True)[1]
+    rank = np.empty(ncomp, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(ncomp)
+    return int(ncomp), rank[labels].astype(np.int32)
+
+
+def trivial_vectors(deg, labels, ncomp: int):
+    """u float64 [n] (numpy): sqrt(deg) normalised within each component -- the eigenvalue-0 vectors of the normalised
+    Laplacian, all in one array because their supports are disjoint."""
+    deg = np.asarray(deg, dtype=np.float64)
+    return np.sqrt(deg) / np.sqrt(np.bincount(labels, weights=deg, minlength=ncomp))[labels]
+
+
+def lanczos_start(labels, ncomp: int, u):
+    """The fixed start vector float64 [n] (numpy): 1 + frac(i phi), a low-discrepancy function of the row index alone, made
+    orthogonal to every component's u and normalised.  It has mass in every component of at least two rows."""
+    n = labels.shape[0]
+    x = 1.0 + np.modf(np.arange(n, dtype=np.float64) * 0.6180339887498949)[0]
+    for _ in range(2):
+        x = x - u * np.bincount(labels, weights=u * x, minlength=ncomp)[labels]
+    return x / np.linalg.norm(x)
+
+
+class Eigenpairs(NamedTuple):
+    """What `laplacian_eigenpairs` returns: the k smallest NONTRIVIAL eigenvalues of I - D^-1/2 G D^-1/2 ascending (numpy
+    float64 [k]) with their unit eigenvectors (float64 [n, k] on the device) and the residuals |N y - theta y| the solver
+    stopped on (numpy [k]); the trivial pairs (eigenvalue 0, one per component) as `trivial` float64 [n] on the device
+    with `labels` int32 [n] -- column c of the trivial vectors is `trivial` on the rows labelled c, components numbered by
+    their smallest row (`trivial_matrix`); the counts; `converged`."""
+    eigenvalues: np.ndarray
+    eigenvectors: "object"
+    residuals: np.ndarray
+    trivial: "object"
+    labels: "object"
+    n_components: int
+    cycles: int
+    matvecs: int
+    converged: bool
+
+    def trivial_matrix(self):
+        """The trivial eigenvectors as float64 [n, n_components] on the device."""
+        return _trivial_matrix(self.trivial, self.labels, self.n_components)
+
+
+def _trivial_matrix(u, comp, ncomp: int):
+    """u float64 [n] spread over the columns its labels comp int32 [n] name: float64 [n, ncomp] on u's device."""
+    import torch
+
+    out = torch.zeros((u.shape[0], ncomp), dtype=torch.float64, device=u.device)
+    out.scatter_(1, comp.long().unsqueeze(1), u.unsqueeze(1))
+    return out
+
+
+def _dense_eigenpairs(graph: CSR, k: int, labels, ncomp: int, u):
+    """The host solve of small problems: numpy eigh of the float64 N with the trivial vectors shifted to -3, below its
+    spectrum [-1, 1].  (theta descending [k], vectors [n, k])."""
+    g = graph.to_scipy().astype(np.float64)
+    deg = np.asarray(g.sum(axis=1)).ravel()
+    dinv = 1.0 / np.sqrt(deg)
+    dense = dinv[:, None] * g.toarray() * dinv[None, :]
+    dense = 0.5 * (dense + dense.T)
+    um = np.zeros((labels.shape[0], ncomp))
+    um[np.arange(labels.shape[0]), labels] = u
+    theta, vecs = np.linalg.eigh(dense - 3.0 * (um @ um.T))
+    return theta[::-1][:k].copy(), np.ascontiguousarray(vecs[:, ::-1][:, :k])
+
+
+def laplacian_eigenpairs(graph: CSR, k: int, tol: float = 1e-6, ncv: Optional[int] = None, max_cycles: int = 300) -> Eigenpairs:
+    """The k smallest nontrivial eigenpairs of the normalised Laplacian I - N, N = D^-1/2 G D^-1/2, of the symmetric CSR
+    `graph`: thick-restart Lanczos with full reorthogonalisation on the device in float64 (csrc/spectral.hip).  The trivial
+    pairs (one per connected component, found on the host) are known in closed form and deflated, so one Krylov sequence
+    serves a disconnected graph.  A cycle runs Lanczos steps up to m = ncv or max(2k + 2, 64) basis vectors, reads T, beta
+    and the breakdown flag in one copy (the only synchronisation), takes numpy's eigh of T, and stops when the first k
+    residuals |beta S[m - 1, i]| are at most `tol` (absolute: |N| = 1); otherwise it keeps q = k + (m - k) // 2 Ritz
+    vectors (wm_spec_rotate) and the residual vector, resets T to diag(theta) and goes on from column q, whose step
+    computes the arrow coefficients itself.  The start vector is a fixed function of
+    the row index: two calls give the same bits.  Graphs of at most 512 rows, and sizes with n - components <= m + 1, are
+    solved densely on the host.  `converged` is False when `max_cycles` ran out (the pairs are the current Ritz pairs)."""
+    import torch
+
+    n = _check_graph(graph)
+    k, max_cycles = int(k), int(max_cycles)
+    if k < 1 or max_cycles < 1 or not tol >= 0:
+        raise ValueError("k >= 1, max_cycles >= 1 and tol >= 0 expected")
+    m = int(ncv) if ncv is not None else max(2 * k + 2, 64)
+    if m <= k:
+        raise ValueError(f"ncv ({m}) must exceed k ({k})")
+    dev = graph.data.device
+    ncomp, labels = graph_components(graph)
+    if k > n - ncomp:
+        raise ValueError(f"k ({k}) exceeds the {n - ncomp} nontrivial eigenpairs of {n} rows in {ncomp} components")
+    token = token_workspace(dev)  # what degree, matvec and rotate ask for and never touch: once per solve
+    deg, dinv = laplacian_degree(graph, token)
+    deg_h = deg.cpu().numpy()
+    if not (deg_h > 0).all():
+        raise ValueError("every row of the graph needs a positive degree")
+    u_h = trivial_vectors(deg_h, labels, ncomp)
+    u, comp = torch.from_numpy(u_h).to(dev), torch.from_numpy(labels).to(dev)
+    if n <= SPEC_DENSE_ROWS or n - ncomp <= m + 1:
+        theta, vecs = _dense_eigenpairs(graph, k, labels, ncomp, u_h)
+        return Eigenpairs(1.0 - theta, torch.from_numpy(vecs).to(dev), np.zeros(k), u, comp, ncomp, 0, 0, True)
+    if m > SPEC_MAX_BASIS or ncomp > SPEC_MAX_COMPONENTS:
+        raise ValueError(f"the device solver takes at most {SPEC_MAX_BASIS} basis vectors ({m} asked for: lower k or ncv) and "
+                         f"{SPEC_MAX_COMPONENTS} connected components ({ncomp} found: raise n_neighbors)")
+    ldv = m + 1
+    V, spare = torch.zeros((n, ldv), dtype=torch.float64, device=dev), torch.zeros((n, ldv), dtype=torch.float64, device=dev)
+    V[:, 0] = torch.from_numpy(lanczos_start(labels, ncomp, u_h)).to(dev)
+    w = torch.empty(n, dtype=torch.float64, device=dev)
+    T = torch.zeros(m * m + 2, dtype=torch.float64, device=dev)
+    ws = lanczos_workspace(n, ldv, ncomp, dev)
+    begin, matvecs = 0, 0
+    for cycle in range(1, max_cycles + 1):
+        for j in range(begin, m):
+            laplacian_matvec(graph, dinv, V, j, out=w, checked=True, ws=token)
+            lanczos_orthonormalise(w, V, j, comp, ncomp, u, T, m, ws)
+        matvecs += m - begin
+        t_h = T.cpu().numpy()  # the cycle's one synchronisation
+        flag = int(t_h[m * m + 1:].view(np.int64)[0])
+        mm, beta = (flag, 0.0) if flag else (m, float(t_h[m * m]))  # a breakdown at step flag - 1: an invariant subspace
+        theta, S = np.linalg.eigh(t_h[:m * m].reshape(m, m)[:mm, :mm], UPLO="U")
+        theta, S = theta[::-1], S[:, ::-1]
+        kk = min(k, mm)
+        resid = np.abs(beta * S[mm - 1, :kk])
+        done = bool(flag) or bool((resid <= tol).all())
+        if done or cycle == max_cycles:
+            break
+        q = k + (m - k) // 2
+        basis_rotate(V, S[:, :q], m, out=spare, ws=token)
+        spare[:, q] = V[:, m]
+        V, spare = spare, V
+        # T restarts as diag(theta); the arrow beta S[m - 1, :q] is not filled in: step q's full orthogonalisation computes
+        # V[:, :q]^T N v_q, which is that arrow, into column q above the diagonal, the triangle eigh reads
+        t_new = np.zeros(m * m + 2)
+        t_new[:m * m].reshape(m, m)[np.arange(q), np.arange(q)] = theta[:q]
+        T.copy_(torch.from_numpy(t_new))
+        begin = q
+    vecs = basis_rotate(V, S[:, :kk], mm, ws=token)
+    return Eigenpairs(1.0 - theta[:kk], vecs, resid, u, comp, ncomp, cycle, matvecs, done and kk == k)
+
+
+def meta_positions(ncomp: int, dim: int, centroids=None):
+    """umap-learn's component_layout: where each of `ncomp` > 1 connected components goes, float64 [ncomp, dim] (numpy).
+    Up to 2 dim components sit on the axes: the rows of vstack([B, -B])[:ncomp], B = hstack([eye(ceil(ncomp / 2)), zeros]).
+    More than that: the eigenvectors 1 .. dim of the dense normalised Laplacian of exp(-d^2) (no self-loops), d the
+    Euclidean distances of the components' centroids (float64 [ncomp, features]), divided by their maximum; each vector's
+    sign is fixed so that its entry of largest magnitude is positive."""
+    if ncomp <= 2 * dim:
+        half = -(-ncomp // 2)
+        base = np.hstack([np.eye(half), np.zeros((half, dim - half))])
+        return np.vstack([base, -base])[:ncomp]
+    c = np.asarray(centroids, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != ncomp:
+        raise ValueError(f"centroids [{ncomp}, features] expected")
+    d2 = ((c[:, None, :] - c[None, :, :]) ** 2).sum(axis=2)
+    off = ~np.eye(ncomp, dtype=bool)
+    # scipy's normalised Laplacian (which umap-learn reaches through sklearn) ignores self-loops, and a / sqrt(w_i w_j) does
+    # not change when every affinity is scaled: exp(-(d^2 - min d^2)) is the same matrix without the underflow of far centroids
+    aff = np.where(off, np.exp(-(d2 - d2[off].min())), 0.0)
+    w = aff.sum(axis=1)
+    alone = w == 0
+    dinv = 1.0 / np.sqrt(np.where(alone, 1.0, w))
+    lap = np.diag(1.0 - alone) - dinv[:, None] * aff * dinv[None, :]
+    vecs = np.linalg.eigh(0.5 * (lap + lap.T))[1][:, 1:dim + 1]
+    vecs = vecs * np.sign(vecs[np.abs(vecs).argmax(axis=0), np.arange(dim)])
+    return vecs / vecs.max()
+
+
+def component_ranges(meta):
+    """data_range float64 [ncomp]: half the smallest positive distance from a component's meta position to another's
+    (1 when every meta position coincides with it)."""
+    meta = np.asarray(meta, dtype=np.float64)
+    d = np.sqrt(((meta[:, None, :] - meta[None, :, :]) ** 2).sum(axis=2))
+    return np.array([row[row > 0].min() / 2.0 if (row > 0).any() else 1.0 for row in d])
+
+
+def component_is_small(size: int, dim: int) -> bool:
+    """Whether a component is placed at random around its meta position and not by its own eigenvectors."""
+    return size < 2 * dim or size <= dim + 1
+
+
+def component_plan(x, labels, ncomp: int, dim: int):
+    """(meta positions [ncomp, dim], data_range [ncomp]) of a disconnected graph's components; x [n, d] on the device
+    gives the centroids when there are more than 2 dim components."""
+    import torch
+
+    centroids = None
+    if ncomp > 2 * dim:
+        lab = torch.from_numpy(labels).to(x.device)
+        centroids = np.stack([x[lab == c].double().mean(dim=0).cpu().numpy() for c in range(ncomp)])
+    meta = meta_positions(ncomp, dim, centroids)
+    return meta, component_ranges(meta)
+
+
+def _entry_rows(graph: CSR):
+    """The row of every stored entry, int64 [nnz] on the graph's device."""
+    import torch
+
+    n = graph.indptr.numel() - 1
+    return torch.repeat_interleave(torch.arange(n, device=graph.data.device), (graph.indptr[1:] - graph.indptr[:-1]).long())
+
+
+def _select_entries(graph: CSR, head, keep) -> CSR:
+    """The graph with only the stored entries that `keep` (bool [nnz]) marks; `head`: `_entry_rows(graph)`."""
+    import torch
+
+    if bool(keep.all()):
+        return graph
+    n = graph.indptr.numel() - 1
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=graph.data.device)
+    indptr[1:] = torch.cumsum(torch.bincount(head[keep], minlength=n), 0)
+    return CSR(indptr.to(torch.int32), graph.indices[keep].contiguous(), graph.data[keep].contiguous())
+
+
+def _without_zeros(graph: CSR) -> CSR:
+    """The graph without its explicit zeros: the entries a label intersection leaves are no edges (`graph_components`
+    does not follow them either), so the two ends of every entry that stays share a component."""
+    return _select_entries(graph, _entry_rows(graph), graph.data != 0)
+
+
+def _component_subgraph(graph: CSR, comp, head, c: int):
+    """(rows int64 ascending, the CSR of component c in its own numbering), by torch indexing on the device.  comp: the
+    labels of `graph_components`; head: `_entry_rows(graph)`.  An entry is kept when both its ends are in the component
+    and it is no explicit zero, and the row pointers are counted from the kept entries."""
+    import torch
+
+    n = graph.indptr.numel() - 1
+    rows = torch.nonzero(comp == c).squeeze(1)
+    renumber = torch.full((n,), -1, dtype=torch.int64, device=comp.device)
+    renumber[rows] = torch.arange(rows.numel(), device=comp.device)
+    cols = graph.indices.long()
+    keep = (comp[head] == c) & (comp[cols] == c) & (graph.data != 0)
+    indptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=comp.device)
+    indptr[1:] = torch.cumsum(torch.bincount(head[keep], minlength=n)[rows], 0)
+    return rows, CSR(indptr.to(torch.int32), renumber[cols[keep]].to(torch.int32).contiguous(), graph.data[keep].contiguous())
+
+
+def spectral_layout(x, graph: CSR, dim: int, random_state: int = 0, tol: float = 1e-4):
+    """umap-learn's spectral_layout with multi_component_layout, float64 [n, dim] on the device, or None when a solve did
+    not converge.  One component: the eigenvectors 1 .. dim of the normalised Laplacian (`laplacian_eigenpairs`).  More:
+    every component gets a meta position and a data_range (`component_plan`); a small one (`component_is_small`) is
+    drawn uniformly within its data_range around its meta position from default_rng(random_state), in component order; any
+    other gets its own eigenvectors 1 .. dim from its sub-graph, scaled to data_range / max|.| and moved to its meta
+    position.  Components are numbered by their smallest row."""
+    import torch
+
+    n = _check_graph(graph)
+    dim = int(dim)
+    graph = _without_zeros(graph)  # (a label-intersected graph: its explicit zeros are no edges)
+    ncomp, labels = graph_components(graph)
+    if ncomp == 1:
+        if n <= dim + 1:
+            return None
+        res = laplacian_eigenpairs(graph, dim, tol)
+        return res.eigenvectors if res.converged else None
+    dev = graph.data.device
+    meta, ranges = component_plan(x, labels, ncomp, dim)
+    rng = np.random.default_rng(random_state)
+    comp = torch.from_numpy(labels).to(dev)
+    head = _entry_rows(graph)
+    out = torch.empty((n, dim), dtype=torch.float64, device=dev)
+    sizes = np.bincount(labels, minlength=ncomp)
+    for c in range(ncomp):
+        centre = torch.from_numpy(meta[c]).to(dev)
+        if component_is_small(int(sizes[c]), dim):
+            out[comp == c] = torch.from_numpy(rng.uniform(-ranges[c], ranges[c], (int(sizes[c]), dim))).to(dev) + centre
+            continue
+        rows, sub = _component_subgraph(graph, comp, head, c)
+        res = laplacian_eigenpairs(sub, dim, tol)
+        if not res.converged:
+            return None
+        vecs = res.eigenvectors
+        out[rows] = vecs * (float(ranges[c]) / float(vecs.abs().max())) + centre
+    return out
+
+
+def _sign_flip(vecs):
+    """sklearn's _deterministic_vector_sign_flip on columns: the entry of largest magnitude of every column is positive."""
+    import torch
+
+    top = vecs.abs().argmax(dim=0)
+    sign = torch.sign(vecs[top, torch.arange(vecs.shape[1], device=vecs.device)])
+    return vecs * torch.where(sign == 0, torch.ones_like(sign), sign)
+
+
+def connectivity_graph(x, n_neighbors: int, metric: str = "euclidean") -> CSR:
+    """sklearn's kneighbors_graph(include_self=True) symmetrised, 0.5 (A + A^T), as CSR on the device: entries 1.0 where
+    both rows list each other (the diagonal among them) and 0.5 where one does."""
+    import torch
+
+    _, idx = knn_graph(x, n_neighbors, metric)
+    n, k = idx.shape
+    dev = idx.device
+    key = torch.unique(torch.arange(n, device=dev, dtype=torch.int64).unsqueeze(1) * n + idx.long())
+    both = torch.unique(torch.cat([key, (key % n) * n + key // n]))
+
+    def has(want):
+        at = torch.searchsorted(key, want).clamp_(max=key.numel() - 1)
+        return (key[at] == want).float()
+
+    data = 0.5 * (has(both) + has((both % n) * n + both // n))
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(torch.bincount(both // n, minlength=n), 0)
+    return CSR(indptr.to(torch.int32), (both % n).to(torch.int32).contiguous(), data.contiguous())
+
+
+def affinity_graph(x, n_neighbors: int, metric: str, affinity: str) -> CSR:
+    """The affinity matrix of the spectral estimators: "fuzzy" (`fuzzy_simplicial_set`) or "connectivity"
+    (`connectivity_graph`)."""
+    if affinity not in ("fuzzy", "connectivity"):
+        raise ValueError(f"affinity must be 'fuzzy' or 'connectivity' ({affinity!r} given)")
+    x = _prep(x)
+    k = int(n_neighbors)
+    if not 1 <= k <= min(x.shape[0], MAX_NEIGHBORS):
+        raise ValueError(f"n_neighbors ({k}) must be in [1, min(n_samples, {MAX_NEIGHBORS})]")
+    return fuzzy_simplicial_set(x, k, metric) if affinity == "fuzzy" else connectivity_graph(x, k, metric)
+
+
+def _without_diagonal(graph: CSR) -> CSR:
+    """The graph without its diagonal entries (scipy's normalised Laplacian, which sklearn uses, ignores self-loops)."""
+    head = _entry_rows(graph)
+    return _select_entries(graph, head, head != graph.indices.long())
+
+
+def spectral_embedding(graph: CSR, n_components: int, tol: float = 1e-6, drop_first: bool = True):
+    """sklearn.manifold.spectral_embedding (norm_laplacian=True) of an affinity CSR: (embedding float64 [n, n_components]
+    on the device, eigenvalues numpy, n_connected_components, converged).  Self-loops are dropped first, as scipy's
+    normalised Laplacian does.  The columns are the trivial vectors (one per component, ordered by its smallest row) and
+    then the nontrivial ones ascending, the first column dropped with `drop_first`; every eigenvector is divided by
+    sqrt(deg) (sklearn's recovery) and its sign fixed by `_sign_flip`."""
+    import torch
+
+    n = _check_graph(graph)
+    want = int(n_components) + (1 if drop_first else 0)
+    if not 1 <= int(n_components) or want > n:
+        raise ValueError(f"n_components ({n_components}) must be at least 1 and leave room in {n} rows")
+    graph = _without_diagonal(graph)
+    ncomp, labels = graph_components(graph)
+    deg, _ = laplacian_degree(graph)
+    if want <= ncomp:  # the closed-form vectors fill every column: nothing to iterate, nothing that could fail to converge
+        deg_h = deg.cpu().numpy()
+        if not (deg_h > 0).all():
+            raise ValueError("every row of the graph needs a positive degree")
+        u = torch.from_numpy(trivial_vectors(deg_h, labels, ncomp)).to(deg.device)
+        full, vals, converged = _trivial_matrix(u, torch.from_numpy(labels).to(deg.device), ncomp)[:, :want], np.zeros(want), True
+    else:
+        res = laplacian_eigenpairs(graph, want - ncomp, tol)
+        full = torch.cat([res.trivial_matrix(), res.eigenvectors], dim=1)
+        vals, converged = np.concatenate([np.zeros(ncomp), res.eigenvalues]), bool(res.converged)
+    full = _sign_flip(full / torch.sqrt(deg).unsqueeze(1))
+    first = 1 if drop_first else 0
+    return full[:, first:].contiguous(), vals[first:], ncomp, converged
+
+
+class SpectralEmbedding:
+    """sklearn.manifold.SpectralEmbedding on device tensors, with the exact kNN graph: `fit(x)` / `fit_transform(x)` give
+    `embedding_` float32 [n, n_components] on the device and set `eigenvalues_` (numpy, of the kept columns),
+    `n_connected_components_`, `converged_` and `affinity_matrix_` (CSR).  affinity: "fuzzy" (UMAP's fuzzy simplicial
+    set) or "connectivity" (sklearn's nearest_neighbors affinity, self included)."""
+
+    def __init__(self, n_components: int = 2, n_neighbors: int = 15, metric: str = "euclidean", affinity: str = "fuzzy",
+                 tol: float = 1e-6):
+        metric_code(metric)
+        if affinity not in ("fuzzy", "connectivity"):
+            raise ValueError(f"affinity must be 'fuzzy' or 'connectivity' ({affinity!r} given)")
+        if int(n_components) < 1 or not 1 <= int(n_neighbors) <= MAX_NEIGHBORS or not tol >= 0:
+            raise ValueError(f"n_components >= 1, n_neighbors in [1, {MAX_NEIGHBORS}] and tol >= 0 required")
+        self.n_components, self.n_neighbors, self.metric = int(n_components), int(n_neighbors), metric
+        self.affinity, self.tol = affinity, float(tol)
+        self.embedding_ = self.eigenvalues_ = self.n_connected_components_ = self.converged_ = self.affinity_matrix_ = None
+
+    def fit(self, x, y=None) -> "SpectralEmbedding":
+        graph = affinity_graph(x, min(self.n_neighbors, x.shape[0]), self.metric, self.affinity)
+        emb, self.eigenvalues_, self.n_connected_components_, self.converged_ = spectral_embedding(graph, self.n_components,
+                                                                                                  self.tol)
+        self.affinity_matrix_ = graph
+        self.embedding_ = emb.float().contiguous()
+        return self
+
+    def fit_transform(self, x, y=None):
+        return self.fit(x).embedding_
+
+
 # ------------------------------------------------------------------------------------------------ estimator
+
+_INITS = ("spectral", "spectral_device", "pca", "random")
 
 
 class UMAP:
     """umap.UMAP on device tensors: `.fit(x)` / `.fit_transform(x)` give float32 [n, n_components] on the device and
     set `embedding_`, `graph_` (CSR), `a_`, `b_`.  `n_epochs=None` means 500 for at most 10 000 rows and 200 above.
     `init`: "spectral" (falls back to "pca" with a warning when the graph is disconnected or eigsh does not
-    converge), "pca", "random" or an [n, n_components] array."""
+    converge), "spectral_device" (`spectral_layout`: the same start from the device eigensolver, every connected
+    component of a disconnected graph laid out on its own; falls back to "pca" with a warning only when the solver does
+    not converge), "pca", "random" or an [n, n_components] array."""
 
     def __init__(self, n_neighbors: int = 15, n_components: int = 2, metric: str = "euclidean", n_epochs: Optional[int] = None,
                  learning_rate: float = 1.0, init="spectral", min_dist: float = 0.1, spread: float = 1.0,
@@ -766,8 +1303,8 @@ class UMAP:
             raise ValueError("0 <= min_dist <= spread and spread > 0 required")
         if not (learning_rate > 0 and repulsion_strength >= 0 and 0 <= int(negative_sample_rate) <= 64):
             raise ValueError("learning_rate > 0, repulsion_strength >= 0 and 0 <= negative_sample_rate <= 64 required")
-        if isinstance(init, str) and init not in ("spectral", "pca", "random"):
-            raise ValueError("init must be 'spectral', 'pca', 'random' or an array")
+        if isinstance(init, str) and init not in _INITS:
+            raise ValueError("init must be 'spectral', 'spectral_device', 'pca', 'random' or an array")
         self.n_neighbors, self.n_components, self.metric = int(n_neighbors), int(n_components), metric
         self.n_epochs = None if n_epochs is None else int(n_epochs)
         self.learning_rate, self.init, self.min_dist, self.spread = float(learning_rate), init, float(min_dist), float(spread)
@@ -798,6 +1335,11 @@ class UMAP:
                                   "converge); falling back to init='pca'")
                 else:
                     y = torch.from_numpy(vecs).to(x.device)
+            elif init == "spectral_device":
+                y = spectral_layout(x, graph, dim, self.random_state)
+                if y is None:
+                    warnings.warn("UMAP: the device eigensolver of init='spectral_device' did not converge; falling back to "
+                                  "init='pca'")
             if y is None:
                 y = _pca_init(x, dim)
             top = float(y.abs().max())
