@@ -1125,6 +1125,48 @@ size_t wm_spec_rotate_workspace_bytes(int n, int m, int q);
 int wm_spec_rotate(const double* V, int ldv, const double* S, int lds, int n, int m, int q, double* out, int ldo,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Label spreading and propagation over a graph (semi_supervised.py: LabelSpreading, LabelPropagation) in float64.
+ * Every summation order is stated in csrc/propagate.hip.
+ *
+ * Common to the four: the graph is as above (symmetric CSR, int32 / float32, trusted, 1 <= n <= 2^24) and dinv comes
+ * from wm_spec_degree.  F is row-major [n][ldf] float64 with cols = groups * classes <= 256 and ldf >= cols; column
+ * q = g * classes + c belongs to alpha group g and class c; columns behind cols are never read or written.  labels int32
+ * [n] in -1 .. classes - 1 (trusted), -1: unknown.  Pointers aligned to their element, the workspace to 16 bytes and at
+ * least the companion's byte count (0: unsupported sizes; init, finalize and neighbor_mean report a fixed token size
+ * and store nothing there).  No atomics, no allocation, no synchronisation: two calls give the same bits.
+ *
+ * wm_lp_init: F[i][g * classes + c] = 1.0 if labels[i] == c, else 0.0, for every group. */
+size_t wm_lp_init_workspace_bytes(int n, int classes, int groups);
+int wm_lp_init(const int32_t* labels, int n, int classes, int groups, double* F, int ldf, void* workspace,
+               size_t workspace_bytes, void* stream);
+/* iters >= 1 steps Fa -> Fb -> Fa -> ... (the result is in Fb when iters is odd).  With s = sum_p data[p] * (cs[col[p]] *
+ * Fin[col[p]][q]) over the row's entries in storage order and y the one-hot of labels[i] (0 for an unknown row):
+ *   hard == 0 (spreading)    cs = dinv, Fout = alpha[g] * (dinv[i] * s) + (1 - alpha[g]) * y;
+ *   hard != 0 (propagation)  a labelled row gets y; an unlabelled one cs = 1, t = (dinv[i] * dinv[i]) * s and
+ *                            Fout = t / (the sum of t over the group's classes, class order; 1 if that is 0), as
+ *                            sklearn's LabelPropagation renormalises every row at every step;
+ *   active[g] == 0           the group's columns are copied from Fin bit for bit.
+ * alpha float64 [groups] and active int32 [groups] are device arrays.  resid float64 [iters][groups] receives, per step,
+ * the sum over the rows and the group's classes of |Fout - Fin| (exactly 0 for a frozen group); its order depends on n
+ * and classes alone, not on the number of groups.  Fa and Fb must not overlap. */
+size_t wm_lp_iterate_workspace_bytes(int n, int classes, int groups);
+int wm_lp_iterate(const int32_t* indptr, const int32_t* indices, const float* data, const double* dinv,
+                  const int32_t* labels, int n, int classes, int groups, const double* alpha, const int32_t* active,
+                  int hard, int iters, double* Fa, double* Fb, int ldf, double* resid, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* One group's columns (F points at the group's first column, pitch ldf): rowsum[i] = the sum of the classes in column
+ * order; dist[i][c] (pitch classes) = F / rowsum, zeros where rowsum == 0; pred[i] = the first maximum (0 for an all-zero
+ * row); unreached[i] (one byte) = (rowsum == 0). */
+size_t wm_lp_finalize_workspace_bytes(int n, int classes);
+int wm_lp_finalize(const double* F, int ldf, int n, int classes, double* dist, double* rowsum, int32_t* pred,
+                   uint8_t* unreached, void* workspace, size_t workspace_bytes, void* stream);
+/* out[r][c] = (sum_t dist[idx[r][t]][c], t ascending) / (its sum over c, c ascending); rows whose sum is 0 stay 0.
+ * idx int32 [m][k] in [0, n) (trusted), 1 <= m <= 2^24, 1 <= k <= 64; dist float64 [n][classes], out [m][classes]. */
+size_t wm_lp_neighbor_mean_workspace_bytes(int m, int k, int classes);
+int wm_lp_neighbor_mean(const int32_t* idx, int m, int k, const double* dist, int n, int classes, double* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -358,6 +358,17 @@ SIGNATURES = {
     "wm_spec_rotate_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wm_spec_rotate": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                c_void_p]),
+    # ---- label spreading / propagation
+    "wm_lp_init_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lp_init": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "wm_lp_iterate_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lp_iterate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                              c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_lp_finalize_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "wm_lp_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "wm_lp_neighbor_mean_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lp_neighbor_mean": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
