@@ -8,9 +8,10 @@
 // else.  Roofline: HBM (algorithmic bytes = n*d*elsize per query batch, SURVEY §8d formula (ii)).
 //
 // Geometry.  A row of either operand is cut into 256-byte slabs (128 bf16 / 64 f32).  LDS images
-// keep 256-byte rows, the 16-byte chunk index XOR-swizzled with (row & 15) so that the
-// ds_read_b128 fragment reads (lane (r,h) -> row r, chunk 2s+h) are bank-conflict free
-// (cdna_hip_programming.md T2).  MFMA orientation is "swapped": A = 32 bank rows, B = 32 queries,
+// keep 256-byte rows, the 16-byte chunk index XOR-swizzled with a key of the row (query tile:
+// row & 15; bank tile: bank_swz) so that the ds_read_b128 fragment reads (lane (r,h) -> query row
+// r / bank row tile_row(r), chunk 2s+h) are bank-conflict free (cdna_hip_programming.md T2).
+// MFMA orientation is "swapped": A = 32 bank rows, B = 32 queries,
 // so the accumulator puts the QUERY on the lane (col = lane&31) and 16 bank rows in registers —
 // the top-k list of a query is lane-local and needs no cross-lane traffic in the hot loop.
 //   bf16: v_mfma_f32_32x32x16_bf16, one 16-byte fragment = one MFMA (k = 8h+j)
@@ -18,11 +19,13 @@
 //
 // Selection is two-stage so that the streaming loop is branch-free: a lane folds the 16 values an
 // accumulator tile gives it into a running MAXIMUM over a fixed group of 64 bank rows (4 chunks x 16
-// rows) and offers that one (max, group id) pair to its sorted list once per group.  The k best
-// elements always lie inside the k groups with the largest maxima (each group whose max reaches
-// the k-th best value holds at least one of the k best), so after the cross-block merge a small
-// rescoring kernel recomputes the <= K*64 candidate rows of every query exactly and orders them
-// (value descending, bank index ascending).
+// rows) and offers that one (max, group id) pair to its sorted list once per group.  The group id
+// is the first row of the 16 consecutive bank rows (a lane's share of one chunk) that attained the
+// maximum first, so groups rank as their best elements do under the list order (value descending,
+// bank index ascending).  The k best elements then always lie inside the k best groups (a group outside them has k groups, hence k
+// distinct rows, ahead of its best element) -- exact ties included -- so after the cross-block
+// merge a small rescoring kernel recomputes the <= K*64 candidate rows of every query exactly and
+// orders them (value descending, bank index ascending).
 #include "common.h"
 #include <limits.h>
 #include <stdlib.h>
@@ -151,37 +154,56 @@ __device__ __forceinline__ void block_merge_store(float (&lv)[QT][K], int (&li)[
   }
 }
 
-__device__ __forceinline__ int acc_row(int reg, int half) {
-  // C/D map of the 32x32 MFMA family: row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-  return (reg & 3) + 8 * (reg >> 2) + 4 * half;
-}
+// Which bank row of a wave's 32-row sub-tile a lane feeds to the MFMA as A row r.  The C/D map of the 32x32 MFMA family
+// puts output row i into register (i&3) + 4*(i>>3) of half (i>>2)&1, i.e. a half owns the quads 0-3, 8-11, ... or
+// 4-7, 12-15, ... of the A rows.  Feeding row tile_row(r) as A row r turns that into 16 CONSECUTIVE bank rows per half,
+// in register order: half h, register e <-> bank row 16*h + e (acc_row).
+__device__ __forceinline__ int tile_row(int r) { return (r & 3) | ((r >> 3) << 2) | (((r >> 2) & 1) << 4); }
+__device__ __forceinline__ int acc_row(int reg, int half) { return reg + 16 * half; }
+// XOR-swizzle key of an LDS bank-tile row: the 16-byte piece p of row `row` lives in slot p ^ bank_swz(row).  A
+// ds_read_b128 is served in four groups of 16 lanes, r in {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of either half;
+// they read the rows tile_row(r) = {0-3, 20-23, 24-27, 12-15} and {16-19, 4-7, 8-11, 28-31}, over each of which the
+// key takes 16 distinct values, so the reads stay bank-conflict free.
+__device__ __forceinline__ int bank_swz(int row) { return (row & 7) | ((row >> 1) & 8); }
 
 // ---- pieces the two streaming kernels share; operands are taken the way the kernels form them.  (The list
 // initialisation, the group offer and the query-tile staging stay spelled out in both kernels: as helpers each of them
 // changed the kernels' code, profiles/knn_refactor.md section 1.)
 
-// Fold the 16 values an accumulator tile gives this lane into the running group maxima.  nb = first bank row of the
-// wave's 32-row sub-tile; the test is wave-uniform, and only the bank's last chunk masks rows past the end.
+// Fold the 16 values an accumulator tile gives this lane into the running group maxima, and keep beside every maximum
+// the first bank row of the 16-row set (this lane's rows of one chunk) that attained it first.  The sets are disjoint
+// aligned ranges of consecutive rows, so (maximum descending, set row ascending) ranks groups exactly as their best
+// elements rank under the list order (value descending, bank index ascending), and the k best rows lie in the k best
+// groups also among exact ties.  The row doubles as the group's id: chunk, wave and half are read back from it
+// (knn_select).  A later chunk of the group holds higher rows, so only a strictly larger maximum replaces the row.
+// nb = first bank row of the wave's 32-row sub-tile; the test is wave-uniform, and only the bank's last chunk masks
+// rows past the end.
+// (one accumulator tile; row0 = the lane's first bank row of the chunk, acc_row(0, h); MASKED: the bank's last chunk)
+template <bool MASKED>
+__device__ __forceinline__ void fold_tile(const f32x16_t& acc, float& gmax, int& grow, int row0, int n) {
+  float m = gmax;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) m = fmaxf(m, (!MASKED || row0 + e < n) ? acc[e] : -INFINITY);
+  grow = m != gmax ? row0 : grow;  // the maximum moved: strictly larger than every earlier chunk's
+  gmax = m;
+}
+
 template <int QT>
-__device__ __forceinline__ void fold_group_max(const f32x16_t (&acc)[QT], float (&gmax)[QT], int nb, int n, int h) {
+__device__ __forceinline__ void fold_group_max(const f32x16_t (&acc)[QT], float (&gmax)[QT], int (&grow)[QT], int nb,
+                                               int n, int h) {
+  const int row0 = nb + acc_row(0, h);
   if (nb + 32 <= n) {
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      float m = gmax[t];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) m = fmaxf(m, acc[t][e]);
-      gmax[t] = m;
-    }
+    for (int t = 0; t < QT; ++t) fold_tile<false>(acc[t], gmax[t], grow[t], row0, n);
   } else {
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      float m = gmax[t];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) m = fmaxf(m, (nb + acc_row(e, h) < n) ? acc[t][e] : -INFINITY);
-      gmax[t] = m;
-    }
+    for (int t = 0; t < QT; ++t) fold_tile<true>(acc[t], gmax[t], grow[t], row0, n);
   }
 }
+
+// A group's id is a bank row of it (fold_group_max).  Read back where the group lies: the slice's chunks are
+// slice, slice + nslices, ..., a group is four consecutive ones of them.
+__device__ __forceinline__ int group_run(int id, int nslices) { return (id >> 7) % nslices; }
 
 // The oldest stage of an S-stage ring has landed: while the ring is still being refilled (`more`), the S-2 younger
 // stages (8 DMA instructions each) may stay in flight.
@@ -241,7 +263,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
 #pragma unroll
   for (int i = 0; i < PER_STAGE; ++i) {
     const int row = wave * 32 + i * 4 + drow;  // a wave fetches exactly the 32 rows it multiplies
-    soff[i] = (dpc ^ (row & 15)) * 16;  // logical chunk that lands at physical slot dpc
+    soff[i] = (dpc ^ bank_swz(row)) * 16;  // logical chunk that lands at physical slot dpc
     srcp[i] = bank + ((size_t)slice * KNN_ROWS + row) * rowbytes + soff[i];
   }
   // issue() is called once per ring step, in order: (chunk, slab) advance by a carry instead of a division,
@@ -297,8 +319,12 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
     }
   f32x16_t acc[QT];
   float gmax[QT];
+  int grow[QT];  // the group's id: first row of the 16-row set that attained gmax first
 #pragma unroll
-  for (int t = 0; t < QT; ++t) gmax[t] = -INFINITY;
+  for (int t = 0; t < QT; ++t) {
+    gmax[t] = -INFINITY;
+    grow[t] = INT_MAX;
+  }
 
   __syncthreads();  // query tile staged
 
@@ -318,13 +344,13 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
     }
-    const uint8_t* abuf = ring + (it % S) * KNN_BUF + (wave * 32 + r) * KNN_SLAB;
+    const uint8_t* abuf = ring + (it % S) * KNN_BUF + (wave * 32 + tile_row(r)) * KNN_SLAB;
     {
       const uint8_t* qrow = qbuf + (size_t)r * rowbytes + slab * KNN_SLAB;
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
         const int off = ((2 * s + h) ^ (r & 15)) << 4;
-        const uint4 a = *reinterpret_cast<const uint4*>(abuf + off);
+        const uint4 a = *reinterpret_cast<const uint4*>(abuf + (((2 * s + h) ^ bank_swz(tile_row(r))) << 4));
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
           const uint4 b = *reinterpret_cast<const uint4*>(qrow + (size_t)t * 32 * rowbytes + off);
@@ -344,12 +370,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
     if (slab == nslab - 1) {
       const int crel = it / nslab;  // chunk index inside this slice
       const int nb = (slice + crel * nslices) * KNN_ROWS + wave * 32;
-      fold_group_max<QT>(acc, gmax, nb, n, h);
+      fold_group_max<QT>(acc, gmax, grow, nb, n, h);
       if ((crel & 3) == 3 || it == iters - 1) {  // group of 4 chunks complete (or slice ends)
-        const int gid = ((slice + (crel & ~3) * nslices) << 3) | (wave << 1) | h;
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-          if (gmax[t] > lv[t][K - 1]) topk_insert<K>(lv[t], li[t], gmax[t], gid);
+          if (gmax[t] > lv[t][K - 1]) topk_insert<K>(lv[t], li[t], gmax[t], grow[t]);
           gmax[t] = -INFINITY;
         }
       }
@@ -364,7 +389,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
 // instruction stream cut to the bone.  A wave's 32 rows of a chunk are 8 KB contiguous in HBM, so
 // a stage is ONE asm statement: M0 once, eight global_load_lds_dwordx4 that share a scalar base
 // (advanced by one s_add per chunk) and four loop-invariant per-lane offsets (the XOR swizzle depends
-// on i & 3 only); the instruction's immediate offset moves the global source and the LDS
+// on i & 1 and i >> 2 only); the instruction's immediate offset moves the global source and the LDS
 // destination together by 1 KiB per instruction.  The ring slot is a compile-time constant (loop
 // unrolled by S), so ds_read addresses are loop-invariant registers + immediates and the query
 // fragments stay in registers.
@@ -372,10 +397,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream(
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\t"                                                       \
                "global_load_lds_dwordx4 %1, %5 offset:-4096 nt\n\t"                                    \
                "global_load_lds_dwordx4 %2, %5 offset:-3072 nt\n\t"                                    \
-               "global_load_lds_dwordx4 %3, %5 offset:-2048 nt\n\t"                                    \
-               "global_load_lds_dwordx4 %4, %5 offset:-1024 nt\n\t"                                    \
-               "global_load_lds_dwordx4 %1, %5 nt\n\t"                                                 \
-               "global_load_lds_dwordx4 %2, %5 offset:1024 nt\n\t"                                     \
+               "global_load_lds_dwordx4 %1, %5 offset:-2048 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %2, %5 offset:-1024 nt\n\t"                                    \
+               "global_load_lds_dwordx4 %3, %5 nt\n\t"                                                 \
+               "global_load_lds_dwordx4 %4, %5 offset:1024 nt\n\t"                                     \
                "global_load_lds_dwordx4 %3, %5 offset:2048 nt\n\t"                                     \
                "global_load_lds_dwordx4 %4, %5 offset:3072 nt"                                         \
                :                                                                                       \
@@ -403,7 +428,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
   const int drow = lane >> 4, dpc = lane & 15;
   uint32_t voff[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) voff[i] = (uint32_t)(drow * RB + ((dpc ^ ((4 * i + drow) & 15)) << 4));
+  for (int j = 0; j < 4; ++j)  // the swizzle key of row 4 i + drow depends on (i & 1, i >> 2) only: j = (i & 1) + 2 (i >> 2)
+    voff[j] = (uint32_t)(drow * RB + ((dpc ^ bank_swz(4 * (j & 1) + 16 * (j >> 1) + drow)) << 4));
   const uint64_t chunk_stride_bytes = (uint64_t)nslices * KNN_ROWS * RB;
   // +4096: the eight immediates are -4096 .. +3072
   uint64_t sbase = reinterpret_cast<uint64_t>(bank) + ((uint64_t)slice * KNN_ROWS + wave * 32) * RB + 4096;
@@ -419,7 +445,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
       for (int i = 0; i < 8; ++i) {
         int row = nb + wave * 32 + i * 4 + drow;
         row = row < n ? row : n - 1;
-        const uint8_t* src = bank + (size_t)row * RB + ((dpc ^ ((4 * i + drow) & 15)) << 4);
+        const uint8_t* src = bank + (size_t)row * RB + ((dpc ^ bank_swz(4 * i + drow)) << 4);
         glds16_nt_at(src, m0v - 4096 + i * 1024);
       }
     } else {
@@ -450,12 +476,17 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
     }
   f32x16_t acc[QT];
   float gmax[QT];
+  int grow[QT];  // the group's id: first row of the 16-row set that attained gmax first
 #pragma unroll
-  for (int t = 0; t < QT; ++t) gmax[t] = -INFINITY;
+  for (int t = 0; t < QT; ++t) {
+    gmax[t] = -INFINITY;
+    grow[t] = INT_MAX;
+  }
 
-  uint32_t aoff[8];  // this lane's eight fragment offsets inside a stage (row wave*32 + r)
+  uint32_t aoff[8];  // this lane's eight fragment offsets inside a stage (row wave*32 + tile_row(r))
 #pragma unroll
-  for (int s8 = 0; s8 < 8; ++s8) aoff[s8] = (uint32_t)((wave * 32 + r) * RB + (((2 * s8 + h) ^ (r & 15)) << 4));
+  for (int s8 = 0; s8 < 8; ++s8)
+    aoff[s8] = (uint32_t)((wave * 32 + tile_row(r)) * RB + (((2 * s8 + h) ^ bank_swz(tile_row(r))) << 4));
   // the query tile passes through LDS once (coalesced 16-byte loads; per-lane fragment loads straight from
   // global memory were measured 2 us slower) and then lives in registers
   uint4 qreg[QT][8];
@@ -493,12 +524,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_stream_b128(
         }
       }
       const int nb = (slice + it * nslices) * KNN_ROWS + wave * 32;
-      fold_group_max<QT>(acc, gmax, nb, n, h);
+      fold_group_max<QT>(acc, gmax, grow, nb, n, h);
       if ((it & 3) == 3 || it == iters - 1) {  // group of 4 chunks complete (or slice ends)
-        const int gid = ((slice + (it & ~3) * nslices) << 3) | (wave << 1) | h;
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-          if (gmax[t] > lv[t][K - 1]) topk_insert<K>(lv[t], li[t], gmax[t], gid);
+          if (gmax[t] > lv[t][K - 1]) topk_insert<K>(lv[t], li[t], gmax[t], grow[t]);
           gmax[t] = -INFINITY;
         }
       }
@@ -611,7 +641,7 @@ __device__ __forceinline__ int key_id(unsigned long long key) { return key != 0u
 //  1. the K best GROUPS can only come from the K runs (slices) with the best heads: every wave picks the K best
 //     heads of its share of the `nslices` sorted runs (two per lane), wave 0 the K best of those 4 K; group ids are
 //     unique across runs, so (value, group id) as one 64-bit key is a total order and the run of a winner is
-//     (group id >> 3) % nslices (a streaming block's chunks are slice, slice + nslices, ...);
+//     (group id >> 7) % nslices (the id is a bank row; a streaming block's chunks are slice, slice + nslices, ...);
 //  2. the K x K entries of those runs -> the K best groups (K = 8: one entry per lane of wave 0; K = 16: one per
 //     thread, two-level as for the heads);
 //  3. recompute the K*64 candidate rows exactly (4 lanes per row, 16-byte pieces, xor-shuffle sum);
@@ -683,7 +713,7 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
       const int rg = key_id(rk);
       unsigned long long e[1] = {0ull};
       if (rg != INT_MAX) {
-        const size_t o = qbase + (size_t)((rg >> 3) % nslices) * K + (lane % K);
+        const size_t o = qbase + (size_t)group_run(rg, nslices) * K + (lane % K);
         e[0] = group_key(part_sim[o], part_idx[o]);
       }
       wave_topk<1, K>(e, win);
@@ -696,7 +726,7 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
 #pragma unroll
         for (int t = 0; t < K; ++t) {
           const int rg = key_id(win[t]);
-          topg[t] = rg != INT_MAX ? (rg >> 3) % nslices : INT_MAX;
+          topg[t] = rg != INT_MAX ? group_run(rg, nslices) : INT_MAX;
         }
       }
     }
@@ -749,7 +779,10 @@ __global__ __launch_bounds__(TH, (K == 8 && TH == 256) ? 6 : 1) void knn_select(
       const int j = c & 63, cc = j >> 4, e = j & 15;
       int row = INT_MAX;
       if (gid != INT_MAX) {
-        const int c0 = gid >> 3, w = (gid >> 1) & 3, hh = gid & 1;
+        // the id is a row of the group: its chunk is the (chunk / stride)-th of its slice, the group starts at that
+        // count rounded down to a multiple of four
+        const int gc = gid >> 7, w = (gid >> 5) & 3, hh = (gid >> 4) & 1;
+        const int c0 = gc - ((gc / chunk_stride) & 3) * chunk_stride;
         const int chunk = c0 + cc * chunk_stride;  // the streaming block's next chunks
         const int rr = chunk * KNN_ROWS + w * 32 + acc_row(e, hh);
         // (unsigned: a corrupt group id must not turn into an address)
@@ -847,7 +880,13 @@ __global__ void knn_vote_kernel(const float* __restrict__ sim, const int* __rest
     // reference order of operations: (sim / t).exp(), then a sum over the k neighbours in order
     const int nb = idx[(size_t)q * k + j];
     if (nb < 0 || nb >= n_labels) continue;  // padding entry of a short shard list (sim = -inf): no vote
-    const float w = expf(sim[(size_t)q * k + j] / t);
+    // exp multiplies the rounding of the quotient by |sim / t| (14 at t = 0.07): carry the quotient's remainder,
+    // exact by fma, into the weight, exp(x + r) = exp(x) (1 + r), so that a weight is good to the 2 ulp of expf
+    const float s = sim[(size_t)q * k + j];
+    const float x = s / t;
+    float w = expf(x);
+    const float r = fmaf(-x, t, s) / t;
+    if (fabsf(r) < 1.f) w = fmaf(w, r, w);  // (not for an infinite quotient: r is NaN there)
     const int lab = (int)labels[nb];
     for (int c = 0; c < nc; ++c) score[c] += (c == lab) ? w : 0.f;
   }

@@ -8,9 +8,9 @@ nearest neighbours of query embeddings by L2 and by cosine distance.
 
 Here: `embed_dataset` runs the eval-mode backbone over a WaferLoader and keeps the features on the
 GPU; `StandardScaler` is two kernels (column statistics, standardise); `nearest_neighbors` is the
-streaming top-k kernel.  L2 ranking rides on the same inner-product kernel: argmin ||q - x||^2 =
-argmax (q.x - ||x||^2 / 2), so the bank gets one extra column -||x||^2/2 and the query a 1 (padded to
-the kernel's 64-float granularity), in float32 so the ranking is exact.
+streaming top-k kernel for cosine distance and the difference-form query kernel (manifold.knn_query)
+for L2: the inner-product form argmax (q.x - ||x||^2 / 2) cancels in float32 where the features share
+an offset.
 """
 from __future__ import annotations
 
@@ -108,33 +108,38 @@ def nearest_neighbors(query: torch.Tensor, bank: torch.Tensor, k: int, metric: s
     index [nq, k] int64).  metric "cosine": 1 - cos; "l2": Euclidean distance.
 
     Cosine with rows the streaming kernel takes (d % 64 == 0, d <= 512, k <= 8 above 256 features)
-    runs on wm_knn_topk; everything else, and every L2 query, on the general float32 kernel, which
-    scores q.x - ||x||^2/2 for the Euclidean ranking."""
+    runs on wm_knn_topk, every other cosine query on the general float32 kernel; L2 on
+    manifold.knn_query (d <= 1024): relative error at most (d + 3) 2^-24, bit-duplicates of a query at
+    exactly 0, rows ordered by (distance, index)."""
     require_gpu(query, bank)
     if metric not in ("cosine", "l2"):
         raise ValueError("metric must be 'cosine' or 'l2'")
     q, b = query.float().contiguous(), bank.float().contiguous()
+    if metric == "l2":
+        # The difference form sum (q - x)^2 of the UMAP query kernel (relative error at most (d + 3) 2^-24, a query
+        # equal to a bank row leads with exactly 0, rows ordered by (distance, index)).  The inner-product form
+        # |q|^2 - 2 (q.x - |x|^2 / 2) cancels at |x|^2 in float32: with a common offset in the features (mean 10,
+        # d = 512: |x|^2 ~ 5e4) it ranks and reports neighbours closer than ~0.1 wrongly.
+        from . import manifold
+
+        dist, idx = [], []
+        for s in range(0, q.shape[0], query_block):
+            dd, ii = manifold.knn_query(q[s:s + query_block], b, k, metric="euclidean")
+            dist.append(dd)
+            idx.append(ii.long())
+        return torch.cat(dist), torch.cat(idx)
     d = q.shape[1]
     if d % 4:
         pad = 4 - d % 4
         q = torch.nn.functional.pad(q, (0, pad)).contiguous()
         b = torch.nn.functional.pad(b, (0, pad)).contiguous()
-    bias = None
-    if metric == "cosine":
-        q, b = F_hip.l2_normalize(q), F_hip.l2_normalize(b)
-        fast = q.shape[1] % 64 == 0 and q.shape[1] <= 512 and (k <= 8 or q.shape[1] <= 256)
-    else:
-        bias = -0.5 * (b * b).sum(dim=1)
-        fast = False
+    q, b = F_hip.l2_normalize(q), F_hip.l2_normalize(b)
+    fast = q.shape[1] % 64 == 0 and q.shape[1] <= 512 and (k <= 8 or q.shape[1] <= 256)
     dist, idx = [], []
     for s in range(0, q.shape[0], query_block):
         qs = q[s:s + query_block].contiguous()
         # (the fast path pipelines its query batches over several HIP streams: functional.knn_topk_batched)
-        sim, ind = F_hip.knn_topk_batched(qs, b, k, batch=256) if fast else _topk_general(qs, b, bias, k)
-        if metric == "cosine":
-            dist.append((1.0 - sim).clamp_min_(0.0))
-        else:
-            qq = (qs * qs).sum(dim=1, keepdim=True)
-            dist.append((qq - 2.0 * sim).clamp_min_(0.0).sqrt_())
+        sim, ind = F_hip.knn_topk_batched(qs, b, k, batch=256) if fast else _topk_general(qs, b, None, k)
+        dist.append((1.0 - sim).clamp_min_(0.0))
         idx.append(ind.long())
     return torch.cat(dist), torch.cat(idx)

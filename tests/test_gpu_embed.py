@@ -253,7 +253,11 @@ def test_knn_edge_sizes(nq, n, d, k, dtype):
     sim_ref, idx_ref = full.topk(k, dim=1)
     sim, idx = F.knn_topk(q.to(_dev()), bank.to(_dev()), k)
     torch.testing.assert_close(sim.cpu(), sim_ref, atol=5e-6, rtol=0)
-    assert torch.equal(torch.sort(idx.cpu().long(), 1).values, torch.sort(idx_ref, 1).values) or k < n
+    # every row: the indices name their scores within the derived bound, in order, and nothing nearer is left out
+    import knn_cases
+
+    knn_cases.check_topk(sim, idx, q.float().to(_dev()), bank.float().to(_dev()), k, name=f"edge sizes nq{nq} n{n} d{d} k{k}")
+    assert torch.equal(torch.sort(idx.cpu().long(), 1).values, torch.sort(idx_ref, 1).values)
     with pytest.raises(Exception):
         F.knn_topk(q.to(_dev()), bank.to(_dev()), n + 1)  # k > n is rejected, not silently clipped
 
