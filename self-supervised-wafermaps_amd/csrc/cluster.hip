@@ -980,7 +980,6 @@ int cl_launch(const ClArgs& a, const ClGrid& g, int metric, hipStream_t st) {
 inline bool cl_shape_ok(int d, int metric) { return d % 4 == 0 && d <= 1024 && (metric == 0 || metric == 1); }
 constexpr int CL_MAX_N = 1 << 24;  // (row * d and slice * n + row stay far inside size_t; tile indices inside int)
 inline bool cl_count_ok(int v) { return v > 0 && v <= CL_MAX_N; }
-inline bool cl_aligned(const void* p, uintptr_t mask = 15) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 
 // The checks every entry point makes before it touches the device, in the order the callers rely on.  `valid`: the
 // entry point's own part of the first stage (no null pointer, k <= n, ...); `aligned`: its pointers' alignment.  An
@@ -1034,7 +1033,7 @@ extern "C" int wm_core_distance(const float* x, int n, int d, int metric, int k,
                                 size_t workspace_bytes, void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<CL_CORE>(x && out && workspace && k <= n, n, n, d, metric, k, 1,
-                                     cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+                                     wm_aligned(x, 15) && wm_aligned(workspace, 15), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClArgs a = cl_args(x, n, x, n, d, pl.grid);
@@ -1055,7 +1054,7 @@ int cl_knn_run(const float* xq, int m, const float* x, int n, int d, int metric,
                void* workspace, size_t workspace_bytes, void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<CL_KNN>(xq && x && dist && idx && workspace && k <= n, m, n, d, metric, k, 1,
-                                    cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+                                    wm_aligned(xq, 15) && wm_aligned(x, 15) && wm_aligned(workspace, 15), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClCarve ws{static_cast<char*>(workspace)};
@@ -1089,7 +1088,7 @@ extern "C" int wm_knn_query(const float* xq, int m, const float* x, int n, int d
 
 extern "C" int wm_pair_dist(const float* xq, int m, const float* x, int n, int d, int metric, const int32_t* idx, int k,
                             float* out, void* stream) {
-  const int rc = cl_check(xq && x && idx && out, m, n, d, metric, k, 1, cl_aligned(xq) && cl_aligned(x));
+  const int rc = cl_check(xq && x && idx && out, m, n, d, metric, k, 1, wm_aligned(xq, 15) && wm_aligned(x, 15));
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t total = (size_t)m * k;
@@ -1108,7 +1107,7 @@ extern "C" int wm_rank_query(const float* xq, int m, const float* x, int n, int 
                              void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<CL_RANK>(xq && x && t && tj && skip && count && workspace, m, n, d, metric, k, 1,
-                                     cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+                                     wm_aligned(xq, 15) && wm_aligned(x, 15) && wm_aligned(workspace, 15), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClArgs a = cl_args(xq, m, x, n, d, pl.grid);
@@ -1137,7 +1136,7 @@ int cl_min_edge_run(const float* x, const float* core, const int32_t* comp, cons
   ClPlan pl;
   const int rc = cl_prepare<MODE>(x && core && comp && (MODE == CL_MINEDGE || group) && out_w && out_j && workspace &&
                                       inv_alpha > 0.f,
-                                  n, n, d, metric, 1, g, cl_aligned(x) && cl_aligned(workspace), workspace_bytes, &pl);
+                                  n, n, d, metric, 1, g, wm_aligned(x, 15) && wm_aligned(workspace, 15), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClCarve ws{static_cast<char*>(workspace)};
@@ -1190,7 +1189,7 @@ extern "C" int wm_allpoints_core(const float* x, const int32_t* group, int n, in
                                  void* workspace, size_t workspace_bytes, void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<CL_APCORE>(x && group && out && workspace && p > 0.0 && p < (double)INFINITY, n, n, d, metric, 1, g,
-                                       cl_aligned(x) && cl_aligned(workspace) && cl_aligned(out, 7), workspace_bytes, &pl);
+                                       wm_aligned(x, 15) && wm_aligned(workspace, 15) && wm_aligned(out, 7), workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ClCarve ws{static_cast<char*>(workspace)};
@@ -1218,7 +1217,7 @@ extern "C" int wm_mreach_query(const float* xq, const float* core_q, int m, cons
                                size_t workspace_bytes, void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<CL_MREACHQ>(xq && core_q && x && core && out_w && out_dist && out_j && workspace && inv_alpha > 0.f, m,
-                                        n, d, metric, 1, 1, cl_aligned(xq) && cl_aligned(x) && cl_aligned(workspace),
+                                        n, d, metric, 1, 1, wm_aligned(xq, 15) && wm_aligned(x, 15) && wm_aligned(workspace, 15),
                                         workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1241,7 +1240,7 @@ extern "C" int wm_mreach_query(const float* xq, const float* core_q, int m, cons
 extern "C" int wm_cluster_dist_sums(const float* x, const int32_t* labels, int n, int d, int metric, int n_clusters,
                                     double* out, void* stream) {
   const int rc = cl_check(x && labels && out && n_clusters >= 2 && n_clusters <= n, n, n, d, metric, 1, 1,
-                          cl_aligned(x) && cl_aligned(out, 7));
+                          wm_aligned(x, 15) && wm_aligned(out, 7));
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = wm_zero_async(out, (size_t)n * n_clusters * sizeof(double), st);
@@ -1263,7 +1262,7 @@ int cl_group_min_run(const float* xq, const float* core_q, int m, const float* x
                      void* stream) {
   ClPlan pl;
   const int rc = cl_prepare<MODE>(xq && xe && group && out_dist && out_j && workspace && (MODE == CL_GROUPMIN || (core_q && core)),
-                                  m, e, d, metric, 1, g, cl_aligned(xq) && cl_aligned(xe) && cl_aligned(workspace),
+                                  m, e, d, metric, 1, g, wm_aligned(xq, 15) && wm_aligned(xe, 15) && wm_aligned(workspace, 15),
                                   workspace_bytes, &pl);
   if (rc != WM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);

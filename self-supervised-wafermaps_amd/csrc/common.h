@@ -226,6 +226,12 @@ __device__ __forceinline__ float rand01(uint32_t seed, uint32_t idx) {
 
 static inline int wm_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// The entry points' alignment test (mask = alignment - 1; a null pointer passes, for the optional operands).
+static inline bool wm_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
+
+// An entry point that uses no workspace still takes one (one calling convention for all): its companion reports this token size.
+constexpr size_t WM_TOKEN_WS = 256;
+
 // Division of a 31-bit index by a run-time constant (image sides, channels / 8, images per group) as a multiply-high,
 // an add and a shift instead of the ~40-instruction expansion of an integer division: with l = ceil(log2 d) and
 // m = ceil(2^(32+l) / d) - 2^32, floor(x / d) = (umulhi(x, m) + x) >> l for every x < 2^31 (the error term

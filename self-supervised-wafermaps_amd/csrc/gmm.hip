@@ -16,13 +16,9 @@
 // in nothing.  That matters here as it does not for distances: a padded column that reached a covariance would add
 // log reg_covar to every log-determinant.  The parameters are float64 with pitch d.
 //
-// ---- the MFMA tile (restated from pca.hip, whose tests settled the fragment maps; this file shares no code with it).
-// A workgroup is 4 waves and owns a 64 x 64 tile of C = A B; wave w owns the 32 x 32 quadrant (w >> 1, w & 1) as 2 x 2
-// tiles of v_mfma_f64_16x16x4_f64, 32 accumulator registers per lane.  Both panels are staged in LDS as doubles,
-// panel[k][64 + 2], widened, centred and (scatter_full) weighted ONCE by the thread that fetched the element; the next
-// step's elements are requested into registers before the MFMAs of the current one.  Fragment maps: A: lane l holds
-// A[l & 15][k = l >> 4]; B: lane l holds B[k = l >> 4][l & 15]; C/D: register r of lane l is row (l >> 4) + 4 r, column
-// l & 15.  Order of every sum: k ascending in steps of 4, inside an MFMA the hardware's fixed order.
+// ---- the MFMA kernels run on the workgroup tile of f64.h (64 x 64 per workgroup, panels [k][64 + 2] doubles in LDS,
+// the fragment maps and the order of the sum over k are stated there).  An element is widened, centred and
+// (scatter_full) weighted ONCE, by the thread that fetched it.
 //
 //   logprob_full    grid (row tiles, k).  M = 64 rows, N = K = d.  The workgroup walks the column tiles tn = 0, 1, ..
 //                   in ascending order; column tile tn needs only K < min(d, 64 tn + 64), because P_c[f][j] with f > j
@@ -74,24 +70,21 @@
 //                   thread 0 the 256 run sums).  A lane's row is k doubles away from its neighbour's, so the loads do
 //                   not coalesce; the rows are short (k <= 1024) and walked three times out of L1 / L2.  Not measured
 //                   against a transposing LDS stage.
-#include "common.h"
+#include "f64.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 
 constexpr int GM_MAX_N = 1 << 24;
 constexpr int GM_MAX_K = 1024;
 constexpr int GM_MAX_D_DIAG = 1024;
 constexpr int GM_MAX_D_FULL = 256;
-constexpr int GM_TILE = 64;
-constexpr int GM_LD = GM_TILE + 2;  // LDS row stride in doubles
-constexpr int GM_THREADS = 256;
+constexpr int GM_TILE = F64_TILE;   // logprob_diag's VALU tile has the MFMA tile's shape, pitch and thread count
+constexpr int GM_LD = F64_LD;
+constexpr int GM_THREADS = F64_THREADS;
 constexpr int GM_KT_FEAT = 16;      // K per staged step where K = the features
 constexpr int GM_KT_ROWS = 32;      // ... where K = the rows
 constexpr int GM_TARGET_WG = 1024;
 constexpr size_t GM_WS_CAP = (size_t)256 << 20;
-constexpr size_t GM_NO_WS = 256;    // the log-probability kernels use no workspace; their companions report this token
 constexpr int GM_CT = 16;           // components per tile of scatter_diag
 constexpr int GM_SLAB_TARGET = 512;
 constexpr int GM_NORM_SLAB = 256;
@@ -100,26 +93,11 @@ inline bool gm_ok(int n, int d, int ld, int k, int dmax) {
   return n >= 1 && n <= GM_MAX_N && k >= 1 && k <= GM_MAX_K && d >= 1 && d <= dmax && ld >= d && ld % 4 == 0 &&
          ld <= dmax + 3;
 }
-inline bool gm_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 
-struct GmSlices {
-  int slices, slice_rows;
-};
-// `want` slices at most, never more than ceil(n / 256) nor than the byte cap allows; rows rounded up to `round`.
-inline GmSlices gm_cut(int n, long long want, long long by_rows, long long by_bytes, int round) {
-  if (want > by_rows) want = by_rows;
-  if (want > by_bytes) want = by_bytes;
-  if (want < 1) want = 1;
-  const long long rows = (n + want - 1) / want;
-  GmSlices s;
-  s.slice_rows = (int)((rows + round - 1) / round * round);
-  s.slices = (n + s.slice_rows - 1) / s.slice_rows;
-  return s;
-}
-inline GmSlices gm_wsum_shape(int n, int d) {
+inline F64Slices gm_wsum_shape(int n, int d) {
   const int tn = (d + 1 + GM_TILE - 1) / GM_TILE;
-  return gm_cut(n, (GM_TARGET_WG + tn - 1) / tn, (n + 255) / 256,
-                (long long)(GM_WS_CAP / ((size_t)GM_MAX_K * (d + 1) * sizeof(double))), GM_KT_ROWS);
+  return f64_cut(n, (GM_TARGET_WG + tn - 1) / tn, (n + 255) / 256,
+                 (long long)(GM_WS_CAP / ((size_t)GM_MAX_K * (d + 1) * sizeof(double))), GM_KT_ROWS);
 }
 struct GmScatterShape {
   int tiles, slices, slice_rows, batch;
@@ -129,8 +107,8 @@ inline GmScatterShape gm_scatter_full_shape(int n, int d, int k) {
   const int T = (d + GM_TILE - 1) / GM_TILE;
   s.tiles = T * (T + 1) / 2;
   const size_t plane = (size_t)d * d * sizeof(double);
-  const GmSlices c = gm_cut(n, (GM_TARGET_WG + s.tiles - 1) / s.tiles, (n + 255) / 256, (long long)(GM_WS_CAP / plane),
-                            GM_KT_ROWS);
+  const F64Slices c = f64_cut(n, (GM_TARGET_WG + s.tiles - 1) / s.tiles, (n + 255) / 256, (long long)(GM_WS_CAP / plane),
+                              GM_KT_ROWS);
   s.slices = c.slices;
   s.slice_rows = c.slice_rows;
   long long b = (long long)(GM_WS_CAP / (plane * c.slices));
@@ -138,13 +116,14 @@ inline GmScatterShape gm_scatter_full_shape(int n, int d, int k) {
   s.batch = (int)(b < k ? b : k);
   return s;
 }
-inline GmSlices gm_scatter_diag_shape(int n, int d) {
+inline F64Slices gm_scatter_diag_shape(int n, int d) {
   const int chunks = (d + 63) / 64;
-  return gm_cut(n, (GM_SLAB_TARGET + chunks - 1) / chunks, (n + 63) / 64,
-                (long long)(GM_WS_CAP / ((size_t)GM_MAX_K * d * sizeof(double))), 1);
+  return f64_cut(n, (GM_SLAB_TARGET + chunks - 1) / chunks, (n + 63) / 64,
+                 (long long)(GM_WS_CAP / ((size_t)GM_MAX_K * d * sizeof(double))), 1);
 }
 
-// One staged step of a workgroup's 64 x 64 tile: KT / 4 MFMAs deep, 2 x 2 tiles per wave.
+// One staged step of a workgroup's 64 x 64 tile: KT / 4 MFMAs deep, 2 x 2 tiles per wave.  (pca_tile has this loop
+// written out: as a call of this function, shared, its projection measured 0.5 - 2.5 % slower, profiles/f64_refactor.md.)
 template <int KT>
 __device__ __forceinline__ void gm_mma(const double (*As)[GM_LD], const double (*Bs)[GM_LD], f64x4_t (&acc)[2][2], int wm,
                                        int wn, int fk, int fc) {
@@ -298,20 +277,6 @@ __global__ __launch_bounds__(GM_THREADS) void gm_logprob_full(const float* __res
   }
 }
 
-// The sum of a workgroup's 256 values in a fixed tree (the result in every thread).
-__device__ __forceinline__ double gm_block_tree_sum(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int w = GM_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-  const double out = sh[0];
-  __syncthreads();
-  return out;
-}
-
 __global__ __launch_bounds__(GM_THREADS) void gm_normalize(double* __restrict__ wlp, int n, int k, double* __restrict__ lpn,
                                                            int* __restrict__ label, double* __restrict__ part) {
   __shared__ double sh[GM_THREADS];
@@ -332,11 +297,14 @@ __global__ __launch_bounds__(GM_THREADS) void gm_normalize(double* __restrict__ 
     lpn[i] = lp;
     label[i] = arg;
   }
-  const double tot = gm_block_tree_sum(lp, sh);
+  const double tot = block_tree_sum<GM_THREADS>(lp, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
 // One workgroup: thread t adds its run of ceil(count / 256) consecutive values in order, thread 0 the 256 run sums.
+// (kmeans.hip's km_ordered_sum without the offsets.  As a call of that function wm_gmm_normalize took 1.3 - 1.7 us
+// longer per call, 0.7 % .. 5 %: its thread 0 also stores every running total for the offsets' sake --
+// profiles/f64_refactor.md.)
 __global__ __launch_bounds__(GM_THREADS) void gm_ordered_total(const double* __restrict__ v, int count, double* __restrict__ out) {
   __shared__ double sh[GM_THREADS];
   const int t = threadIdx.x;
@@ -375,12 +343,8 @@ __global__ __launch_bounds__(GM_THREADS) void gm_rows_tile(GmRowsArgs a) {
   int tm, tn, slice, comp = 0;
   if constexpr (MODE == GM_WSUM) {
     tm = blockIdx.x, tn = blockIdx.y, slice = blockIdx.z;
-  } else {  // blockIdx.x walks the tiles on and below the diagonal, row by row
-    const int b = blockIdx.x;
-    int ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= b) ++ti;
-    tm = ti;
-    tn = b - ti * (ti + 1) / 2;
+  } else {
+    f64_tri_tile(blockIdx.x, tm, tn);
     slice = blockIdx.y;
     comp = a.c0 + blockIdx.z;
   }
@@ -523,7 +487,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_slab_fold(const double* __restr
 }  // namespace
 
 extern "C" size_t wm_gmm_logprob_diag_workspace_bytes(int n, int d, int ld, int k) {
-  return gm_ok(n, d, ld, k, GM_MAX_D_DIAG) ? GM_NO_WS : 0;
+  return gm_ok(n, d, ld, k, GM_MAX_D_DIAG) ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_gmm_logprob_diag(const float* x, int n, int d, int ld, const double* mean, const double* inv_var,
@@ -531,9 +495,9 @@ extern "C" int wm_gmm_logprob_diag(const float* x, int n, int d, int ld, const d
                                    void* stream) {
   WM_REQUIRE(x && mean && inv_var && cst && out && workspace && n > 0 && d > 0 && k > 0 && ld >= d, WM_EINVAL);
   WM_REQUIRE(gm_ok(n, d, ld, k, GM_MAX_D_DIAG), WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(x, 15) && gm_aligned(mean, 7) && gm_aligned(inv_var, 7) && gm_aligned(cst, 7) && gm_aligned(out, 7),
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(mean, 7) && wm_aligned(inv_var, 7) && wm_aligned(cst, 7) && wm_aligned(out, 7),
              WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= GM_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   gm_logprob_diag<<<dim3((n + GM_TILE - 1) / GM_TILE, (k + GM_TILE - 1) / GM_TILE), GM_THREADS, 0, st>>>(x, n, d, ld, mean,
                                                                                                        inv_var, cst, k, out);
@@ -542,7 +506,7 @@ extern "C" int wm_gmm_logprob_diag(const float* x, int n, int d, int ld, const d
 }
 
 extern "C" size_t wm_gmm_logprob_full_workspace_bytes(int n, int d, int ld, int k) {
-  return gm_ok(n, d, ld, k, GM_MAX_D_FULL) ? GM_NO_WS : 0;
+  return gm_ok(n, d, ld, k, GM_MAX_D_FULL) ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_gmm_logprob_full(const float* x, int n, int d, int ld, const double* mean, const double* pchol,
@@ -550,9 +514,9 @@ extern "C" int wm_gmm_logprob_full(const float* x, int n, int d, int ld, const d
                                    void* stream) {
   WM_REQUIRE(x && mean && pchol && cst && out && workspace && n > 0 && d > 0 && k > 0 && ld >= d, WM_EINVAL);
   WM_REQUIRE(gm_ok(n, d, ld, k, GM_MAX_D_FULL), WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(x, 15) && gm_aligned(mean, 7) && gm_aligned(pchol, 7) && gm_aligned(cst, 7) && gm_aligned(out, 7),
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(mean, 7) && wm_aligned(pchol, 7) && wm_aligned(cst, 7) && wm_aligned(out, 7),
              WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= GM_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   gm_logprob_full<<<dim3((n + GM_TILE - 1) / GM_TILE, k), GM_THREADS, 0, st>>>(x, n, d, ld, mean, pchol, cst, k, out);
   WM_LAUNCH_CHECK();
@@ -568,8 +532,8 @@ extern "C" int wm_gmm_normalize(double* wlp_inout, int n, int k, double* lpn, in
                                 void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(wlp_inout && lpn && label && lpn_sum && workspace && n > 0 && k > 0, WM_EINVAL);
   WM_REQUIRE(n <= GM_MAX_N && k <= GM_MAX_K, WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(wlp_inout, 7) && gm_aligned(lpn, 7) && gm_aligned(label, 3) && gm_aligned(lpn_sum, 7) &&
-                 gm_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(wlp_inout, 7) && wm_aligned(lpn, 7) && wm_aligned(label, 3) && wm_aligned(lpn_sum, 7) &&
+                 wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_gmm_normalize_workspace_bytes(n, k), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -591,10 +555,10 @@ extern "C" int wm_gmm_weighted_sums(const float* x, int n, int d, int ld, const 
                                     void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(x && resp && nk && sx && workspace && n > 0 && d > 0 && k > 0 && ld >= d, WM_EINVAL);
   WM_REQUIRE(gm_ok(n, d, ld, k, GM_MAX_D_DIAG), WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(x, 15) && gm_aligned(resp, 7) && gm_aligned(nk, 7) && gm_aligned(sx, 7) && gm_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(resp, 7) && wm_aligned(nk, 7) && wm_aligned(sx, 7) && wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_gmm_weighted_sums_workspace_bytes(n, d, ld, k), WM_EWORKSPACE);
-  const GmSlices s = gm_wsum_shape(n, d);
+  const F64Slices s = gm_wsum_shape(n, d);
   hipStream_t st = static_cast<hipStream_t>(stream);
   GmRowsArgs a{x, resp, nullptr, static_cast<double*>(workspace), n, d, ld, k, s.slice_rows, 0};
   gm_rows_tile<GM_WSUM><<<dim3((k + GM_TILE - 1) / GM_TILE, (d + 1 + GM_TILE - 1) / GM_TILE, s.slices), GM_THREADS, 0, st>>>(a);
@@ -614,10 +578,10 @@ extern "C" int wm_gmm_scatter_diag(const float* x, int n, int d, int ld, const d
                                    double* out, void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(x && resp && mean && out && workspace && n > 0 && d > 0 && k > 0 && ld >= d, WM_EINVAL);
   WM_REQUIRE(gm_ok(n, d, ld, k, GM_MAX_D_DIAG), WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(x, 15) && gm_aligned(resp, 7) && gm_aligned(mean, 7) && gm_aligned(out, 7) && gm_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(resp, 7) && wm_aligned(mean, 7) && wm_aligned(out, 7) && wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_gmm_scatter_diag_workspace_bytes(n, d, ld, k), WM_EWORKSPACE);
-  const GmSlices s = gm_scatter_diag_shape(n, d);
+  const F64Slices s = gm_scatter_diag_shape(n, d);
   const int chunks = (d + 63) / 64, ctiles = (k + GM_CT - 1) / GM_CT;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(workspace);
@@ -639,7 +603,7 @@ extern "C" int wm_gmm_scatter_full(const float* x, int n, int d, int ld, const d
                                    double* out, void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(x && resp && mean && out && workspace && n > 0 && d > 0 && k > 0 && ld >= d, WM_EINVAL);
   WM_REQUIRE(gm_ok(n, d, ld, k, GM_MAX_D_FULL), WM_EUNSUPPORTED);
-  WM_REQUIRE(gm_aligned(x, 15) && gm_aligned(resp, 7) && gm_aligned(mean, 7) && gm_aligned(out, 7) && gm_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(resp, 7) && wm_aligned(mean, 7) && wm_aligned(out, 7) && wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_gmm_scatter_full_workspace_bytes(n, d, ld, k), WM_EWORKSPACE);
   const GmScatterShape s = gm_scatter_full_shape(n, d, k);

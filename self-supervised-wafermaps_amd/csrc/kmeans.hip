@@ -42,7 +42,8 @@
 //               256 CUs from R = 1 on, and the partial sums stay small (S * R * k * d * 8 bytes: 13 MB per restart at
 //               k = 50, d = 512).
 //   km_fold     a thread per (restart, cluster, feature) adds the S partial sums in slab order, divides and rounds, keeps
-//               the old centre where the count is 0, and the 256 squared moves of a workgroup are added in a fixed tree.
+//               the old centre where the count is 0, and the 256 squared moves of a workgroup are added in a fixed tree
+//               (block_tree_sum, f64.h).
 //   km_finish   a workgroup per restart adds the slabs' inertia and changed counts and the fold's shift partials: thread t
 //               takes the values t, t + 256, ... in index order and the 256 sums go through the same fixed tree.
 //
@@ -64,7 +65,7 @@
 #include <limits.h>
 
 #include "cl_dist.h"
-#include "common.h"
+#include "f64.h"
 
 namespace {
 
@@ -207,20 +208,6 @@ __global__ __launch_bounds__(64) void km_partial(const float* __restrict__ x, co
   }
 }
 
-// The sum of a workgroup's KM_BLOCK values in a fixed tree (the result in every thread).
-__device__ __forceinline__ double km_block_tree_sum(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int w = KM_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-  const double out = sh[0];
-  __syncthreads();
-  return out;
-}
-
 __global__ __launch_bounds__(KM_BLOCK) void km_fold(const double* __restrict__ psum, const int* __restrict__ pcnt, int S,
                                                     int k, int d, const float* __restrict__ old, float* __restrict__ out,
                                                     int* __restrict__ counts, double* __restrict__ pshift) {
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(KM_BLOCK) void km_fold(const double* __restrict__ p
     const double mv = (double)now - (double)was;
     sq = mv * mv;
   }
-  const double tot = km_block_tree_sum(sq, sh);
+  const double tot = block_tree_sum<KM_BLOCK>(sq, sh);
   if (threadIdx.x == 0) pshift[(size_t)r * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -262,9 +249,9 @@ __global__ __launch_bounds__(KM_BLOCK) void km_finish(const double* __restrict__
     ch += (double)pch[(size_t)r * S + s];
   }
   for (int b = t; b < fold_blocks; b += KM_BLOCK) sf += pshift[(size_t)r * fold_blocks + b];
-  in = km_block_tree_sum(in, sh);
-  ch = km_block_tree_sum(ch, sh);
-  sf = km_block_tree_sum(sf, sh);
+  in = block_tree_sum<KM_BLOCK>(in, sh);
+  ch = block_tree_sum<KM_BLOCK>(ch, sh);
+  sf = block_tree_sum<KM_BLOCK>(sf, sh);
   if (t == 0) {
     inertia[r] = in;
     n_changed[r] = (int)ch;
@@ -437,7 +424,7 @@ __global__ __launch_bounds__(KM_BLOCK) void km_seed_eval(const float* __restrict
     if (c2) m = fmin(m, c2[i]);
     planes[(size_t)q * n + i] = m;
   }
-  const double tot = km_block_tree_sum(m, sh);
+  const double tot = block_tree_sum<KM_BLOCK>(m, sh);
   if (t == 0) bpot[(size_t)q * nb + blockIdx.x] = tot;
 }
 

@@ -9,11 +9,10 @@
 // operands fetched as float32 or float64, widened to double (minus a float64 mean where the mode has one) while they
 // are staged, accumulated in double.
 //
-// ---- the tile routine.  A workgroup is 4 waves and owns a 64 x 64 tile of C over ONE slice of K; wave w owns the
-// 32 x 32 quadrant (w >> 1, w & 1) as 2 x 2 MFMA tiles: 4 x 4 doubles = 32 accumulator registers per lane.  K goes in
-// steps of 32 (gram) or 16 (project, reconstruct): every thread requests its share of the A and B panels of the NEXT
-// step into registers before the MFMAs of the current one, and widens, centres and stores it to LDS behind the barrier
-// that follows.
+// ---- the tile routine.  The workgroup tile of f64.h (64 x 64 per workgroup of 4 waves, LDS panels [k][64 + 2] doubles,
+// the fragment maps and the tests that settle them are stated there) over ONE slice of K.  K goes in steps of 32 (gram)
+// or 16 (project, reconstruct): every thread requests its share of the A and B panels of the NEXT step into registers
+// before the MFMAs of the current one, and widens, centres and stores it to LDS behind the barrier that follows.
 //   Why 64 x 64 and not wider: a f64 16x16x4 MFMA is 2048 flops over 16 passes, so 4 fragment reads of 8 bytes per 4
 //   MFMAs hide behind it; a wider tile would save traffic that is not the limit and would leave d = 512 (8 x 8 tiles, 36
 //   on or below the diagonal) with too few tiles to cut.
@@ -28,12 +27,6 @@
 //   fragment read is one ds_read_b64 with no conversion between it and the MFMA.  Cost: 2 panels x 32 x 66 x 8 bytes =
 //   33 KB per workgroup (gram; half of it for the row passes): four workgroups in a CU's 160 KB, and the registers
 //   (136 with the accumulators) allow three waves per SIMD.
-//   LDS layout: panel[k][64 + 2] doubles, the tile index contiguous: lane l of a fragment read takes
-//   panel[4 kk + (l >> 4)][16 t + (l & 15)], sixteen consecutive doubles per k.  The pad of 2 keeps the transposing
-//   stores of the K-contiguous operands (x in project, y in reconstruct, W in project) off a single bank.
-// Fragment maps of v_mfma_f64_16x16x4_f64 (they differ from every other MFMA here; tests/test_gpu_pca.py settles them
-// with exact integer data): A: lane l holds A[l & 15][k = l >> 4]; B: lane l holds B[k = l >> 4][l & 15]; C/D: register
-// r of lane l is row (l >> 4) + 4 r, column l & 15.
 // Padding: a position behind the operand's rows, columns or the slice's end is staged as an exact 0.0 and the mean is
 // NOT subtracted there (a padded row centred to -mean would corrupt every entry); stores are guarded by the same limits.
 // The Gram pass has no branch around a load: the address of such a position is clamped to the slice's last row / the
@@ -58,24 +51,18 @@
 // (64 consecutive features per wave: coalesced); pca_mean_merge adds the slabs' sums in slab order and divides by n in
 // double.  Slab size: 256 rows while that gives at most 1024 slabs (n <= 262 144); above, ceil(n / 1024) rounded up to a
 // multiple of 256.  The workspace is slabs x d doubles (at most 32 MiB).
-#include "common.h"
+#include "f64.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
-
 constexpr int PCA_MAX_N = 1 << 24;
 constexpr int PCA_MAX_D = 4096;
-constexpr int PCA_TILE = 64;             // C tile of a workgroup (4 waves, 32 x 32 each)
 constexpr int PCA_KT_GRAM = 32;          // K per staged step of the Gram pass (8 MFMAs deep)
 constexpr int PCA_KT_ROWS = 16;          // ... of project / reconstruct (4 deep)
-constexpr int PCA_LD = PCA_TILE + 2;     // LDS row stride in doubles
-constexpr int PCA_THREADS = 256;
 constexpr int PCA_TARGET_WG = 1024;      // workgroups the Gram slice count aims at
 constexpr size_t PCA_GRAM_WS_CAP = (size_t)256 << 20;
 constexpr int PCA_SLAB = 256;            // rows per slab of the mean
 constexpr int PCA_MAX_SLABS = 1024;
-constexpr size_t PCA_NO_WS = 256;        // project / reconstruct use no workspace; their companions report this token size
 
 enum { PCA_GRAM = 0, PCA_PROJECT = 1, PCA_RECON = 2 };
 
@@ -90,17 +77,12 @@ struct PcaGramShape {
 };
 inline PcaGramShape pca_gram_shape(int n, int d) {
   PcaGramShape s;
-  s.T = (d + PCA_TILE - 1) / PCA_TILE;
+  s.T = (d + F64_TILE - 1) / F64_TILE;
   s.tiles = s.T * (s.T + 1) / 2;
-  long long want = (PCA_TARGET_WG + s.tiles - 1) / s.tiles;
-  const long long by_rows = (n + 255) / 256;
-  const long long by_bytes = (long long)(PCA_GRAM_WS_CAP / ((size_t)d * d * sizeof(double)));
-  if (want > by_rows) want = by_rows;
-  if (want > by_bytes) want = by_bytes;
-  if (want < 1) want = 1;
-  const long long rows = (n + want - 1) / want;
-  s.slice_rows = (int)((rows + PCA_KT_GRAM - 1) / PCA_KT_GRAM * PCA_KT_GRAM);
-  s.slices = (n + s.slice_rows - 1) / s.slice_rows;
+  const F64Slices c = f64_cut(n, (PCA_TARGET_WG + s.tiles - 1) / s.tiles, (n + 255) / 256,
+                              (long long)(PCA_GRAM_WS_CAP / ((size_t)d * d * sizeof(double))), PCA_KT_GRAM);
+  s.slices = c.slices;
+  s.slice_rows = c.slice_rows;
   return s;
 }
 
@@ -143,20 +125,16 @@ __device__ __forceinline__ double pca_b(const PcaArgs& a, int k, int c, int k1) 
 }
 
 template <int MODE>
-__global__ __launch_bounds__(PCA_THREADS) void pca_tile(PcaArgs a) {
+__global__ __launch_bounds__(F64_THREADS) void pca_tile(PcaArgs a) {
   constexpr int PCA_KT = MODE == PCA_GRAM ? PCA_KT_GRAM : PCA_KT_ROWS;
-  constexpr int PCA_EL = PCA_KT * PCA_TILE / PCA_THREADS;  // single elements per thread, panel and step
-  __shared__ __attribute__((aligned(16))) double As[PCA_KT][PCA_LD];
-  __shared__ __attribute__((aligned(16))) double Bs[PCA_KT][PCA_LD];
+  constexpr int PCA_EL = PCA_KT * F64_TILE / F64_THREADS;  // single elements per thread, panel and step
+  __shared__ __attribute__((aligned(16))) double As[PCA_KT][F64_LD];
+  __shared__ __attribute__((aligned(16))) double Bs[PCA_KT][F64_LD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   int tm, tn, k0, k1;
-  if constexpr (MODE == PCA_GRAM) {  // blockIdx.x walks the tiles on and below the diagonal, row by row
-    const int b = blockIdx.x;
-    int ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= b) ++ti;
-    tm = ti;
-    tn = b - ti * (ti + 1) / 2;
+  if constexpr (MODE == PCA_GRAM) {
+    f64_tri_tile(blockIdx.x, tm, tn);
     k0 = blockIdx.y * a.slice_rows;
     k1 = min(a.n, k0 + a.slice_rows);
   } else {
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_tile(PcaArgs a) {
     k0 = 0;
     k1 = MODE == PCA_PROJECT ? a.d : a.m;
   }
-  const int m0 = tm * PCA_TILE, n0 = tn * PCA_TILE;
+  const int m0 = tm * F64_TILE, n0 = tn * F64_TILE;
   // ---- staging.  fetch(kb) requests the step's elements into registers, stage(kb) widens, centres and stores them.
   // gram: both panels are 64 consecutive floats of a row of x per k.  A thread takes ONE float4 per 16 rows and panel:
   // 16 lanes cover a row's 256 bytes, a wave instruction four rows.  The load's address is clamped into the slice and
@@ -180,9 +158,9 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_tile(PcaArgs a) {
   // which one the lanes of a wave walk
   constexpr bool A_K_FAST = MODE != PCA_GRAM, B_K_FAST = MODE == PCA_PROJECT;
   [[maybe_unused]] double ra[PCA_EL], rb[PCA_EL];
-  auto ai = [&](int u) { return A_K_FAST ? (t / PCA_KT) + (PCA_THREADS / PCA_KT) * u : (t & 63); };
+  auto ai = [&](int u) { return A_K_FAST ? (t / PCA_KT) + (F64_THREADS / PCA_KT) * u : (t & 63); };
   auto ak = [&](int u) { return A_K_FAST ? (t % PCA_KT) : (t >> 6) + 4 * u; };
-  auto bi = [&](int u) { return B_K_FAST ? (t / PCA_KT) + (PCA_THREADS / PCA_KT) * u : (t & 63); };
+  auto bi = [&](int u) { return B_K_FAST ? (t / PCA_KT) + (F64_THREADS / PCA_KT) * u : (t & 63); };
   auto bk = [&](int u) { return B_K_FAST ? (t % PCA_KT) : (t >> 6) + 4 * u; };
   if constexpr (MODE == PCA_GRAM) {
     a_in = m0 + c4 < a.d;  // (d % 4 == 0: a float4 is inside or outside as a whole)
@@ -244,6 +222,9 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_tile(PcaArgs a) {
     stage(kb);
     __syncthreads();
     if (kb + PCA_KT < k1) fetch(kb + PCA_KT);  // in flight during the MFMAs
+    // gmm.hip's gm_mma<PCA_KT> written out: as a call of a shared helper the projection of 172 950 x 512 onto 50
+    // components took 0.417 ms against 0.407 ms (2.5 %; 0.5 % at 811 457 rows), twice in alternation with this form --
+    // same instruction counts, another register allocation (profiles/f64_refactor.md)
 #pragma unroll
     for (int kk = 0; kk < PCA_KT / 4; ++kk) {
       double fa[2], fb[2];
@@ -277,9 +258,11 @@ __global__ __launch_bounds__(PCA_THREADS) void pca_tile(PcaArgs a) {
 }
 
 // out[i][j] = sum over the slices, in slice order, of the lower triangle's cell (max(i, j), min(i, j)).
-__global__ __launch_bounds__(PCA_THREADS) void pca_gram_merge(const double* __restrict__ planes, int slices, int d,
+// (gmm.hip's gm_scatter_full_merge at batch 1, kept apart: that kernel pays a 64-bit division per thread for its batch
+// index, and with it the Gram pass of 12 449 x 512 was not inside the run-to-run spread -- profiles/f64_refactor.md.)
+__global__ __launch_bounds__(F64_THREADS) void pca_gram_merge(const double* __restrict__ planes, int slices, int d,
                                                               double* __restrict__ out) {
-  const long long e = (long long)blockIdx.x * PCA_THREADS + threadIdx.x;
+  const long long e = (long long)blockIdx.x * F64_THREADS + threadIdx.x;
   if (e >= (long long)d * d) return;
   const int i = (int)(e / d), j = (int)(e - (long long)i * d);
   const size_t cell = (size_t)max(i, j) * d + min(i, j);
@@ -307,8 +290,6 @@ __global__ __launch_bounds__(64) void pca_mean_merge(const double* __restrict__ 
   mean[f] = sum / (double)n;
 }
 
-inline bool pca_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
-
 }  // namespace
 
 extern "C" size_t wm_pca_mean_workspace_bytes(int n, int d) {
@@ -321,7 +302,7 @@ extern "C" int wm_pca_mean(const float* x, int n, int d, double* mean_out, void*
                            void* stream) {
   WM_REQUIRE(x && mean_out && workspace && n > 0 && d > 0, WM_EINVAL);
   WM_REQUIRE(pca_nd_ok(n, d), WM_EUNSUPPORTED);
-  WM_REQUIRE(pca_aligned(x, 3) && pca_aligned(mean_out, 7) && pca_aligned(workspace, 15), WM_EALIGN);
+  WM_REQUIRE(wm_aligned(x, 3) && wm_aligned(mean_out, 7) && wm_aligned(workspace, 15), WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_pca_mean_workspace_bytes(n, d), WM_EWORKSPACE);
   const int rows = pca_slab_rows(n), slabs = (n + rows - 1) / rows;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -342,48 +323,48 @@ extern "C" int wm_pca_gram(const float* x, int n, int d, const double* mean, dou
                            size_t workspace_bytes, void* stream) {
   WM_REQUIRE(x && out && workspace && n > 0 && d > 0, WM_EINVAL);
   WM_REQUIRE(pca_nd_ok(n, d), WM_EUNSUPPORTED);
-  WM_REQUIRE(pca_aligned(x, 15) && pca_aligned(mean, 7) && pca_aligned(out, 7) && pca_aligned(workspace, 15), WM_EALIGN);
+  WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(mean, 7) && wm_aligned(out, 7) && wm_aligned(workspace, 15), WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_pca_gram_workspace_bytes(n, d), WM_EWORKSPACE);
   const PcaGramShape s = pca_gram_shape(n, d);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PcaArgs a{x, nullptr, mean, static_cast<double*>(workspace), nullptr, n, d, 0, s.slice_rows};
-  pca_tile<PCA_GRAM><<<dim3(s.tiles, s.slices), PCA_THREADS, 0, st>>>(a);
+  pca_tile<PCA_GRAM><<<dim3(s.tiles, s.slices), F64_THREADS, 0, st>>>(a);
   WM_LAUNCH_CHECK();
-  pca_gram_merge<<<(int)(((long long)d * d + PCA_THREADS - 1) / PCA_THREADS), PCA_THREADS, 0, st>>>(a.planes, s.slices, d, out);
+  pca_gram_merge<<<(int)(((long long)d * d + F64_THREADS - 1) / F64_THREADS), F64_THREADS, 0, st>>>(a.planes, s.slices, d, out);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
 extern "C" size_t wm_pca_project_workspace_bytes(int n, int d, int m) {
-  return pca_nd_ok(n, d) && m >= 1 && m <= d ? PCA_NO_WS : 0;
+  return pca_nd_ok(n, d) && m >= 1 && m <= d ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_pca_project(const float* x, int n, int d, const double* mean, const double* w, int m, float* out,
                               void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(x && w && out && workspace && n > 0 && d > 0 && m > 0, WM_EINVAL);
   WM_REQUIRE(pca_nd_ok(n, d) && m <= d, WM_EUNSUPPORTED);
-  WM_REQUIRE(pca_aligned(x, 3) && pca_aligned(mean, 7) && pca_aligned(w, 7) && pca_aligned(out, 3), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= PCA_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(x, 3) && wm_aligned(mean, 7) && wm_aligned(w, 7) && wm_aligned(out, 3), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PcaArgs a{x, w, mean, nullptr, out, n, d, m, 0};
-  pca_tile<PCA_PROJECT><<<dim3((n + PCA_TILE - 1) / PCA_TILE, (m + PCA_TILE - 1) / PCA_TILE), PCA_THREADS, 0, st>>>(a);
+  pca_tile<PCA_PROJECT><<<dim3((n + F64_TILE - 1) / F64_TILE, (m + F64_TILE - 1) / F64_TILE), F64_THREADS, 0, st>>>(a);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
 extern "C" size_t wm_pca_reconstruct_workspace_bytes(int n, int m, int d) {
-  return pca_nd_ok(n, d) && m >= 1 && m <= d ? PCA_NO_WS : 0;
+  return pca_nd_ok(n, d) && m >= 1 && m <= d ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_pca_reconstruct(const float* y, int n, int m, const double* w, int d, const double* mean, float* out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(y && w && out && workspace && n > 0 && d > 0 && m > 0, WM_EINVAL);
   WM_REQUIRE(pca_nd_ok(n, d) && m <= d, WM_EUNSUPPORTED);
-  WM_REQUIRE(pca_aligned(y, 3) && pca_aligned(mean, 7) && pca_aligned(w, 7) && pca_aligned(out, 3), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= PCA_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(y, 3) && wm_aligned(mean, 7) && wm_aligned(w, 7) && wm_aligned(out, 3), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   PcaArgs a{y, w, mean, nullptr, out, n, d, m, 0};
-  pca_tile<PCA_RECON><<<dim3((n + PCA_TILE - 1) / PCA_TILE, (d + PCA_TILE - 1) / PCA_TILE), PCA_THREADS, 0, st>>>(a);
+  pca_tile<PCA_RECON><<<dim3((n + F64_TILE - 1) / F64_TILE, (d + F64_TILE - 1) / F64_TILE), F64_THREADS, 0, st>>>(a);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }

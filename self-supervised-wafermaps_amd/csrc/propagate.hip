@@ -44,9 +44,7 @@ constexpr int LP_MAX_COLS = 256;     // groups * classes (a lane owns at most LP
 constexpr int LP_MAX_K = 64;         // neighbours per new row (manifold.MAX_NEIGHBORS)
 constexpr int LP_THREADS = 256;
 constexpr int LP_QUAD = 4;           // rows per residual partial
-constexpr size_t LP_NO_WS = 256;     // init, finalize and neighbor_mean use no workspace; their companions report this token size
 
-inline bool lp_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 inline int lp_quads(int n) { return (n + LP_QUAD - 1) / LP_QUAD; }
 inline bool lp_sizes_ok(int n, int classes, int groups) {
   return n >= 1 && n <= LP_MAX_N && classes >= 1 && groups >= 1 && classes <= LP_MAX_COLS && groups <= LP_MAX_COLS &&
@@ -173,6 +171,8 @@ __global__ __launch_bounds__(LP_THREADS) void lp_resid_merge(const double* __res
   const double* p = part + (size_t)g * quads;
   double sum = 0.0;
   for (int j = t; j < quads; j += LP_THREADS) sum += p[j];
+  // (the tree of f64.h's block_tree_sum without its last barrier, which leaves the result in every thread: with it a step
+  // measured 0.2 - 0.4 us outside the run-to-run spread, profiles/f64_refactor.md)
   s[t] = sum;
   __syncthreads();
   for (int h = LP_THREADS / 2; h >= 1; h >>= 1) {
@@ -248,15 +248,15 @@ void lp_launch_step(int nc, dim3 grid, hipStream_t st, const int32_t* indptr, co
 
 }  // namespace
 
-extern "C" size_t wm_lp_init_workspace_bytes(int n, int classes, int groups) { return lp_sizes_ok(n, classes, groups) ? LP_NO_WS : 0; }
+extern "C" size_t wm_lp_init_workspace_bytes(int n, int classes, int groups) { return lp_sizes_ok(n, classes, groups) ? WM_TOKEN_WS : 0; }
 
 extern "C" int wm_lp_init(const int32_t* labels, int n, int classes, int groups, double* F, int ldf, void* workspace,
                           size_t workspace_bytes, void* stream) {
   WM_REQUIRE(labels && F && workspace && n > 0 && classes > 0 && groups > 0, WM_EINVAL);
   WM_REQUIRE(lp_sizes_ok(n, classes, groups), WM_EUNSUPPORTED);
   WM_REQUIRE(ldf >= classes * groups, WM_EINVAL);
-  WM_REQUIRE(lp_aligned(labels, 3) && lp_aligned(F, 7), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= LP_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(labels, 3) && wm_aligned(F, 7), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   const int cols = classes * groups;
   const long long cells = (long long)n * cols;
   lp_init<<<(unsigned)((cells + LP_THREADS - 1) / LP_THREADS), LP_THREADS, 0, static_cast<hipStream_t>(stream)>>>(labels, n, classes,
@@ -278,9 +278,9 @@ extern "C" int wm_lp_iterate(const int32_t* indptr, const int32_t* indices, cons
   WM_REQUIRE(n > 0 && classes > 0 && groups > 0 && iters >= 1 && Fa != Fb, WM_EINVAL);
   WM_REQUIRE(lp_sizes_ok(n, classes, groups), WM_EUNSUPPORTED);
   WM_REQUIRE(ldf >= classes * groups, WM_EINVAL);
-  WM_REQUIRE(lp_aligned(indptr, 3) && lp_aligned(indices, 3) && lp_aligned(data, 3) && lp_aligned(dinv, 7) && lp_aligned(labels, 3) &&
-                 lp_aligned(alpha, 7) && lp_aligned(active, 3) && lp_aligned(Fa, 7) && lp_aligned(Fb, 7) && lp_aligned(resid, 7) &&
-                 lp_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(indptr, 3) && wm_aligned(indices, 3) && wm_aligned(data, 3) && wm_aligned(dinv, 7) && wm_aligned(labels, 3) &&
+                 wm_aligned(alpha, 7) && wm_aligned(active, 3) && wm_aligned(Fa, 7) && wm_aligned(Fb, 7) && wm_aligned(resid, 7) &&
+                 wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_lp_iterate_workspace_bytes(n, classes, groups), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -303,15 +303,15 @@ extern "C" int wm_lp_iterate(const int32_t* indptr, const int32_t* indices, cons
   return WM_OK;
 }
 
-extern "C" size_t wm_lp_finalize_workspace_bytes(int n, int classes) { return lp_sizes_ok(n, classes, 1) ? LP_NO_WS : 0; }
+extern "C" size_t wm_lp_finalize_workspace_bytes(int n, int classes) { return lp_sizes_ok(n, classes, 1) ? WM_TOKEN_WS : 0; }
 
 extern "C" int wm_lp_finalize(const double* F, int ldf, int n, int classes, double* dist, double* rowsum, int32_t* pred,
                               uint8_t* unreached, void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(F && dist && rowsum && pred && unreached && workspace && n > 0 && classes > 0, WM_EINVAL);
   WM_REQUIRE(lp_sizes_ok(n, classes, 1), WM_EUNSUPPORTED);
   WM_REQUIRE(ldf >= classes && F != dist, WM_EINVAL);
-  WM_REQUIRE(lp_aligned(F, 7) && lp_aligned(dist, 7) && lp_aligned(rowsum, 7) && lp_aligned(pred, 3), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= LP_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(F, 7) && wm_aligned(dist, 7) && wm_aligned(rowsum, 7) && wm_aligned(pred, 3), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   lp_finalize<<<wm_cdiv(n, LP_THREADS), LP_THREADS, 0, static_cast<hipStream_t>(stream)>>>(F, ldf, n, classes, dist, rowsum, pred,
                                                                                           unreached);
   WM_LAUNCH_CHECK();
@@ -319,15 +319,15 @@ extern "C" int wm_lp_finalize(const double* F, int ldf, int n, int classes, doub
 }
 
 extern "C" size_t wm_lp_neighbor_mean_workspace_bytes(int m, int k, int classes) {
-  return lp_sizes_ok(m, classes, 1) && k >= 1 && k <= LP_MAX_K ? LP_NO_WS : 0;
+  return lp_sizes_ok(m, classes, 1) && k >= 1 && k <= LP_MAX_K ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_lp_neighbor_mean(const int32_t* idx, int m, int k, const double* dist, int n, int classes, double* out,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   WM_REQUIRE(idx && dist && out && workspace && m > 0 && k > 0 && n > 0 && classes > 0 && dist != out, WM_EINVAL);
   WM_REQUIRE(wm_lp_neighbor_mean_workspace_bytes(m, k, classes) != 0 && n <= LP_MAX_N, WM_EUNSUPPORTED);
-  WM_REQUIRE(lp_aligned(idx, 3) && lp_aligned(dist, 7) && lp_aligned(out, 7), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= LP_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(idx, 3) && wm_aligned(dist, 7) && wm_aligned(out, 7), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long cells = (long long)m * classes;
   lp_neighbor_sum<<<(unsigned)((cells + LP_THREADS - 1) / LP_THREADS), LP_THREADS, 0, st>>>(idx, m, k, dist, classes, out);

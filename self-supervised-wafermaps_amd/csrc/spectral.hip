@@ -42,22 +42,17 @@
 //           otherwise V[:, j + 1] = w / beta, beta read from device memory by the dividing kernel.
 // T is row-major [m][m] doubles followed by one double (the last beta) and one int64 (the breakdown flag).
 //
-// Fragment maps of v_mfma_f64_16x16x4_f64 as in csrc/pca.hip: A: lane l holds A[l & 15][k = l >> 4]; B: lane l holds
-// B[k = l >> 4][l & 15]; C/D: register r of lane l is row (l >> 4) + 4 r, column l & 15.
-#include "common.h"
+// Fragment maps of v_mfma_f64_16x16x4_f64 (spec_rotate: fk, fc, the store walk): as stated in f64.h.
+#include "f64.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 
 constexpr int SPEC_MAX_N = 1 << 24;
 constexpr int SPEC_MAX_LDV = 256;    // columns of a basis (the LDS partials of a slab are [4][SPEC_MAX_LDV])
 constexpr int SPEC_MAX_COMP = 256;   // connected components whose trivial vectors one call projects out
 constexpr int SPEC_SLAB = 256;       // rows per slab = threads per workgroup
 constexpr int SPEC_THREADS = 256;
-constexpr size_t SPEC_NO_WS = 256;   // degree, matvec and rotate use no workspace; their companions report this token size
 
-inline bool spec_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
 inline int spec_slabs(int n) { return (n + SPEC_SLAB - 1) / SPEC_SLAB; }
 
 __device__ __forceinline__ double spec_group16_sum(double v) {
@@ -219,30 +214,30 @@ inline bool spec_ortho_ok(int n, int ldv, int j, int ncomp, int m) {
 
 }  // namespace
 
-extern "C" size_t wm_spec_degree_workspace_bytes(int n) { return n >= 1 && n <= SPEC_MAX_N ? SPEC_NO_WS : 0; }
+extern "C" size_t wm_spec_degree_workspace_bytes(int n) { return n >= 1 && n <= SPEC_MAX_N ? WM_TOKEN_WS : 0; }
 
 extern "C" int wm_spec_degree(const int32_t* indptr, const float* data, int n, double* deg, double* dinv, void* workspace,
                               size_t workspace_bytes, void* stream) {
   WM_REQUIRE(indptr && data && deg && dinv && workspace && n > 0, WM_EINVAL);
   WM_REQUIRE(n <= SPEC_MAX_N, WM_EUNSUPPORTED);
-  WM_REQUIRE(spec_aligned(indptr, 3) && spec_aligned(data, 3) && spec_aligned(deg, 7) && spec_aligned(dinv, 7), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= SPEC_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(indptr, 3) && wm_aligned(data, 3) && wm_aligned(deg, 7) && wm_aligned(dinv, 7), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   spec_degree<<<wm_cdiv(n, SPEC_THREADS), SPEC_THREADS, 0, static_cast<hipStream_t>(stream)>>>(indptr, data, n, deg, dinv);
   WM_LAUNCH_CHECK();
   return WM_OK;
 }
 
-extern "C" size_t wm_spec_matvec_workspace_bytes(int n) { return n >= 1 && n <= SPEC_MAX_N ? SPEC_NO_WS : 0; }
+extern "C" size_t wm_spec_matvec_workspace_bytes(int n) { return n >= 1 && n <= SPEC_MAX_N ? WM_TOKEN_WS : 0; }
 
 extern "C" int wm_spec_matvec(const int32_t* indptr, const int32_t* indices, const float* data, const double* dinv,
                               const double* v, int ldv, int n, double* w, void* workspace, size_t workspace_bytes,
                               void* stream) {
   WM_REQUIRE(indptr && indices && data && dinv && v && w && workspace && n > 0 && ldv > 0, WM_EINVAL);
   WM_REQUIRE(n <= SPEC_MAX_N && ldv <= SPEC_MAX_LDV, WM_EUNSUPPORTED);
-  WM_REQUIRE(spec_aligned(indptr, 3) && spec_aligned(indices, 3) && spec_aligned(data, 3) && spec_aligned(dinv, 7) &&
-                 spec_aligned(v, 7) && spec_aligned(w, 7),
+  WM_REQUIRE(wm_aligned(indptr, 3) && wm_aligned(indices, 3) && wm_aligned(data, 3) && wm_aligned(dinv, 7) &&
+                 wm_aligned(v, 7) && wm_aligned(w, 7),
              WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= SPEC_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   spec_matvec<<<wm_cdiv(n, SPEC_THREADS / 16), SPEC_THREADS, 0, static_cast<hipStream_t>(stream)>>>(indptr, indices, data, dinv, v,
                                                                                                    ldv, n, w);
   WM_LAUNCH_CHECK();
@@ -261,8 +256,8 @@ extern "C" int wm_spec_orthonormalise(double* w, double* V, int n, int ldv, int 
                                       void* stream) {
   WM_REQUIRE(w && V && comp && u && T && workspace && n > 0 && ldv > 0 && j >= 0 && ncomp > 0 && m > 0, WM_EINVAL);
   WM_REQUIRE(spec_ortho_ok(n, ldv, j, ncomp, m), WM_EUNSUPPORTED);
-  WM_REQUIRE(spec_aligned(w, 7) && spec_aligned(V, 7) && spec_aligned(comp, 3) && spec_aligned(u, 7) && spec_aligned(T, 7) &&
-                 spec_aligned(workspace, 15),
+  WM_REQUIRE(wm_aligned(w, 7) && wm_aligned(V, 7) && wm_aligned(comp, 3) && wm_aligned(u, 7) && wm_aligned(T, 7) &&
+                 wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_spec_orthonormalise_workspace_bytes(n, ldv, ncomp), WM_EWORKSPACE);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -294,7 +289,7 @@ extern "C" int wm_spec_orthonormalise(double* w, double* V, int n, int ldv, int 
 }
 
 extern "C" size_t wm_spec_rotate_workspace_bytes(int n, int m, int q) {
-  return n >= 1 && n <= SPEC_MAX_N && m >= 1 && m <= SPEC_MAX_LDV && q >= 1 && q <= SPEC_MAX_LDV ? SPEC_NO_WS : 0;
+  return n >= 1 && n <= SPEC_MAX_N && m >= 1 && m <= SPEC_MAX_LDV && q >= 1 && q <= SPEC_MAX_LDV ? WM_TOKEN_WS : 0;
 }
 
 extern "C" int wm_spec_rotate(const double* V, int ldv, const double* S, int lds, int n, int m, int q, double* out, int ldo,
@@ -302,8 +297,8 @@ extern "C" int wm_spec_rotate(const double* V, int ldv, const double* S, int lds
   WM_REQUIRE(V && S && out && workspace && n > 0 && m > 0 && q > 0, WM_EINVAL);
   WM_REQUIRE(ldv >= m && lds >= q && ldo >= q && V != out, WM_EINVAL);
   WM_REQUIRE(wm_spec_rotate_workspace_bytes(n, m, q) != 0, WM_EUNSUPPORTED);
-  WM_REQUIRE(spec_aligned(V, 7) && spec_aligned(S, 7) && spec_aligned(out, 7), WM_EALIGN);
-  WM_REQUIRE(workspace_bytes >= SPEC_NO_WS, WM_EWORKSPACE);
+  WM_REQUIRE(wm_aligned(V, 7) && wm_aligned(S, 7) && wm_aligned(out, 7), WM_EALIGN);
+  WM_REQUIRE(workspace_bytes >= WM_TOKEN_WS, WM_EWORKSPACE);
   spec_rotate<<<dim3(wm_cdiv(n, 64), wm_cdiv(q, 16)), SPEC_THREADS, 0, static_cast<hipStream_t>(stream)>>>(V, ldv, S, lds, n, m, q,
                                                                                                           out, ldo);
   WM_LAUNCH_CHECK();
