@@ -177,13 +177,13 @@ class _BatchNorm(torch.autograd.Function):
                                 float(momentum), int(bool(relu)), ptr(mean), ptr(invstd), ptr(out), ptr(ws), ws.numel(),
                                 stream_ptr()), "wm_f32_bn_fwd")
         ctx.save_for_backward(ys, out if relu else None, mean, invstd, _f32(gamma))
-        ctx.meta = (rows, c, g, bool(training), residual is not None, gamma is not None and gamma.requires_grad)
+        ctx.meta = (rows, c, g, bool(training), residual is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         ys, out, mean, invstd, gamma = ctx.saved_tensors
-        rows, c, g, training, has_res, affine = ctx.meta
+        rows, c, g, training, has_res = ctx.meta
         if not training:
             raise NotImplementedError("batch_norm (float32 preset): backward through eval-mode statistics is not implemented")
         dout = as_nhwc(dout) if dout.dim() == 4 else _f32(dout)
@@ -195,7 +195,9 @@ class _BatchNorm(torch.autograd.Function):
         ws = _workspace(lib.wm_f32_bn_workspace_bytes(rows, c, g), ys.device)
         check(lib.wm_f32_bn_bwd(ptr(ys), ptr(dout), ptr(out), ptr(gamma), ptr(mean), ptr(invstd), rows, c, g, ptr(dgamma),
                                 ptr(dbeta), ptr(dy), ptr(dz), ptr(ws), ws.numel(), stream_ptr()), "wm_f32_bn_bwd")
-        return dy, dz, (dgamma if affine else None), (dbeta if affine else None), None, None, None, None, None, None, None, None
+        # each parameter's gradient follows its own requires_grad (a frozen gamma keeps beta trainable)
+        return (dy, dz, (dgamma if ctx.needs_input_grad[2] else None), (dbeta if ctx.needs_input_grad[3] else None), None, None,
+                None, None, None, None, None, None)
 
 
 def batch_norm(y, gamma, beta, running_mean, running_var, training, residual=None, relu=False, eps=1e-5, momentum=0.1,

@@ -23,7 +23,8 @@ of csrc/conv.hip with their fused statistics and BatchNorm-backward epilogue, th
 the launch arithmetic their block sums follow, the pooling of csrc/pool.hip), each with
 switches that seed one wrong computation, and the input families.  tests/test_kernel_check_cpu.py proves on the CPU
 that every seeded error is rejected by `check` on these families; the GPU tests feed the kernels the same families.
-The loss kernels of csrc/embed.hip have theirs in the sibling tests/loss_cases.py.
+The loss kernels of csrc/embed.hip have theirs in the sibling tests/loss_cases.py, the float32 kernels of csrc/f32path.hip in
+tests/f32_cases.py (check(..., ulp=2^-23), inputs drawn inside float32_inputs()).
 """
 import contextlib
 import math
@@ -49,6 +50,8 @@ _JITTER = None
 
 def bf(x: torch.Tensor) -> torch.Tensor:
     """Round to bf16 (nearest even, through float32 as the kernels do), keep the dtype."""
+    if _FLOAT32_INPUTS:  # see float32_inputs()
+        return x.float().to(x.dtype)
     if _JITTER is not None:  # see jitter()
         x = x * (1.0 + 2.0 ** -20 * (2.0 * torch.rand(x.shape, generator=_JITTER, dtype=torch.float64) - 1.0)).to(x.dtype)
     return x.float().bfloat16().to(x.dtype)
@@ -66,12 +69,34 @@ def jitter(seed: int):
         _JITTER = None
 
 
+_FLOAT32_INPUTS = False
+
+
+@contextlib.contextmanager
+def float32_inputs():
+    """Inside the block bf() rounds to float32 instead: the input families (conv_inputs, attention_inputs, layer_norm_inputs,
+    bn_forward_inputs, act_grid, ...) then hold full float32 values, what the float32 kernels of csrc/f32path.hip are fed
+    (tests/f32_cases.py)."""
+    global _FLOAT32_INPUTS
+    _FLOAT32_INPUTS = True
+    try:
+        yield
+    finally:
+        _FLOAT32_INPUTS = False
+
+
+def f32_round(t: torch.Tensor) -> torch.Tensor:
+    """Round to float32 (nearest even), back in float64: one float32 operation of an emulation"""
+    return t.float().double()
+
+
 def _flat64(t) -> torch.Tensor:
     return t.detach().to("cpu", torch.float64).reshape(-1)
 
 
-def scores(x, ref64, a=None) -> dict:
-    """The four criteria of x against ref64.  `a`: absolute term of criterion 4."""
+def scores(x, ref64, a=None, ulp: float = BF16_ULP) -> dict:
+    """The four criteria of x against ref64.  `a`: absolute term of criterion 4, `ulp`: its relative term (one ulp of the
+    output's format: bf16 unless stated)."""
     x, r = _flat64(x), _flat64(ref64)
     assert x.shape == r.shape, (x.shape, r.shape)
     err = (x - r).abs()
@@ -79,8 +104,12 @@ def scores(x, ref64, a=None) -> dict:
     out["max |err| / max |ref|"] = float(err.max() / (r.abs().max() + 1e-300))
     out["relative RMS error"] = float(err.pow(2).mean().sqrt() / (r.pow(2).mean().sqrt() + 1e-300))
     out["1 - cosine"] = max(0.0, float(1.0 - (x @ r) / (x.norm() * r.norm() + 1e-300))) if float(r.norm()) > 0 else float(err.max() > 0)
+    if ulp < BF16_ULP and float(r.norm()) > 0 and float(x.norm()) > 0:
+        # a float32 output lies 1e-15 from its reference in 1 - cosine, below what the float64 dot product above resolves over
+        # 1e5 elements: half the squared distance of the two unit vectors is the same quantity without the cancellation
+        out["1 - cosine"] = float(0.5 * (x / x.norm() - r / r.norm()).pow(2).sum())
     if a is not None:
-        den = a + BF16_ULP * r.abs()
+        den = a + ulp * r.abs()
         frac = torch.where(den > 0, err / den.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf),
                                                                              torch.zeros_like(err)))
         out["max |err| / (a + ulp |ref|)"] = float(frac.max())
@@ -94,7 +123,7 @@ def _abs_term(emul, ref64) -> float:
 
 
 def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False,
-            floor_cosine: bool = False):
+            floor_cosine: bool = False, ulp: float = BF16_ULP):
     """[(criterion, measured, bound)] and whether `got` is finite; no assertion (the CPU proofs use this).
     abs_floor: a lower limit of criterion 4's absolute term (see f32_sum_floor).
     floor_all (the float32 statistics of BatchNorm): criteria 1 and 2 are not asked to go below `factor` roundings of
@@ -106,7 +135,7 @@ def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, fl
     g = _flat64(got)
     finite = bool(torch.isfinite(g).all())
     a = max(_abs_term(emul, ref64), float(abs_floor))
-    yard = scores(emul, ref64, a)
+    yard = scores(emul, ref64, a, ulp)
 
     def bound(k):
         if k == "1 - cosine":
@@ -130,7 +159,7 @@ def verdict(got, ref64, emul, factor: float = FACTOR, abs_floor: float = 0.0, fl
 
     if not finite:
         return [(k, math.inf, bound(k)) for k in yard], False
-    mine = scores(g, ref64, a)
+    mine = scores(g, ref64, a, ulp)
     return [(k, mine[k], bound(k)) for k in yard], True
 
 
@@ -159,9 +188,9 @@ def passes(got, ref64, emul, factor: float = FACTOR) -> bool:
 
 
 def check(got, ref64, emul, what: str, factor: float = FACTOR, abs_floor: float = 0.0, floor_all: bool = False,
-          floor_cosine: bool = False) -> float:
+          floor_cosine: bool = False, ulp: float = BF16_ULP) -> float:
     """Assert the four criteria (each logged through parity()); returns the worst measured / bound ratio."""
-    rows, finite = verdict(got, ref64, emul, factor, abs_floor, floor_all, floor_cosine)
+    rows, finite = verdict(got, ref64, emul, factor, abs_floor, floor_all, floor_cosine, ulp)
     assert finite, f"{what}: result holds inf / nan"
     worst = 0.0
     failed = []

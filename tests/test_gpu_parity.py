@@ -28,6 +28,8 @@ def _rel(a, b):
 @pytest.mark.parametrize("n,c,h,k,r,stride,pad", [(3, 3, 20, 64, 7, 2, 3), (2, 64, 14, 128, 3, 2, 1), (2, 128, 9, 128, 3, 1, 1),
                                                   (2, 64, 8, 128, 1, 2, 0), (5, 37, 6, 70, 3, 1, 1)])
 def test_f32_conv_matches_torch(n, c, h, k, r, stride, pad):
+    # (hand-set 2e-6 against float32 torch; the derived bounds, exact lattices and ragged tiles of the same kernel are in
+    # tests/test_gpu_f32_kernels.py::test_conv_lattice_is_exact / test_conv_forward_and_backward_through_every_epilogue)
     from ssl_wafermap_amd import f32path
 
     g = torch.Generator().manual_seed(n * 100 + c)
@@ -42,6 +44,8 @@ def test_f32_conv_matches_torch(n, c, h, k, r, stride, pad):
 
 
 def test_f32_batchnorm_layernorm_pool_attention_match_torch():
+    # (one shape per op against float32 torch with hand-set tolerances; per entry point, against float64 with derived bounds, ties
+    # in the pooling windows and the edge shapes: tests/test_gpu_f32_kernels.py)
     from ssl_wafermap_amd import f32path
 
     g = torch.Generator().manual_seed(0)
