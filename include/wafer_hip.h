@@ -1167,6 +1167,39 @@ size_t wm_lp_neighbor_mean_workspace_bytes(int m, int k, int classes);
 int wm_lp_neighbor_mean(const int32_t* idx, int m, int k, const double* dist, int n, int classes, double* out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Local outlier factor over neighbour lists (neighbors.py: LocalOutlierFactor, outlier_scores, hubness) in float64.
+ * The mapping and every summation order are stated in csrc/lof.hip.
+ *
+ * Common to the three: a list is a row of `ld` columns, 1 <= ld <= 63, of float32 distances and int32 indices as
+ * wm_knn_graph / wm_knn_query order them (by (distance, index)); for the fitted set the row itself has been removed.
+ * 1 <= rows, n_fit <= 2^24.  ks is a HOST array of `groups` neighbour counts, 1 <= groups <= WM_LOF_MAX_GROUPS, every
+ * 1 <= ks[r] <= ld (WM_EINVAL otherwise, before any launch; a caller with a longer list calls once per chunk): group r
+ * reads the first ks[r] columns of every row and no other, and all groups are served by one launch.  Outputs are
+ * row-major [groups][rows].  An index outside [0, n_fit) gathers nothing (its term counts as 0).  Pointers aligned to
+ * their element; the workspace is a token (the companions report a fixed size, 0 for unsupported sizes) and nothing is
+ * stored there.  Distances are widened to float64 once; every sum is the balanced tree over the columns t = 0 .. 63
+ * (zeros behind ks[r]), pairs (t, t ^ 1) first, then (t, t ^ 2), ... (t, t ^ 32).  No float atomics: two calls give the
+ * same bits, and a ks[r] gives the same bits alone as inside any list. */
+#define WM_LOF_MAX_GROUPS 64
+/* Local reachability density of the query rows against the fitted lists dist_fit [n_fit][ld_fit] (ks[r] <= ld_fit too):
+ *   lrd[r][i] = 1 / ((sum_{t < ks[r]} max(dist_q[i][t], dist_fit[idx_q[i][t]][ks[r] - 1])) / ks[r] + 1e-10).
+ * For the fit itself the query lists ARE the fitted lists (dist_q == dist_fit is allowed). */
+size_t wm_lof_lrd_workspace_bytes(int rows, int ld, int groups);
+int wm_lof_lrd(const float* dist_q, const int32_t* idx_q, int rows, int ld, const float* dist_fit, int n_fit, int ld_fit,
+               const int32_t* ks, int groups, double* lrd, void* workspace, size_t workspace_bytes, void* stream);
+/* lof[r][i] = ((sum_{t < ks[r]} lrd_fit[r][idx_q[i][t]]) / ks[r]) / lrd_q[r][i]; lrd_q [groups][rows] and lrd_fit
+ * [groups][n_fit] as wm_lof_lrd wrote them (the same array for the fit itself); lof is a third buffer. */
+size_t wm_lof_factor_workspace_bytes(int rows, int ld, int groups);
+int wm_lof_factor(const int32_t* idx_q, int rows, int ld, const double* lrd_q, const double* lrd_fit, int n_fit,
+                  const int32_t* ks, int groups, double* lof, void* workspace, size_t workspace_bytes, void* stream);
+/* indeg[r][j] = #{ (i, t) : t < ks[r], idx[i][t] == j } for j in [0, n), int32 [groups][n]: cleared by a kernel, then one
+ * integer atomic add per list entry into the group with the smallest ks[r] > t (max(ks) per row, order-independent), then
+ * the groups are added up in the order of their ks[r]. */
+size_t wm_lof_indegree_workspace_bytes(int rows, int ld, int groups);
+int wm_lof_indegree(const int32_t* idx, int rows, int ld, int n, const int32_t* ks, int groups, int32_t* indeg,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -369,6 +369,15 @@ SIGNATURES = {
                                c_void_p]),
     "wm_lp_neighbor_mean_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wm_lp_neighbor_mean": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- local outlier factor (ks is a host array)
+    "wm_lof_lrd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lof_lrd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                           c_void_p]),
+    "wm_lof_factor_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lof_factor": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
+    "wm_lof_indegree_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wm_lof_indegree": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,
