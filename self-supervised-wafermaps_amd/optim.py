@@ -160,7 +160,9 @@ class SGD(_ArenaStateMixin, torch.optim.Optimizer):
     def __init__(self, params, lr: float, momentum: float = 0.0, weight_decay: float = 0.0, grad_scale: float = 1.0):
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("invalid SGD hyper-parameter")
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        # dampening / nesterov: fixed, but torch.optim.SGD reads them from every group, and state_dict() is in its format
+        # (without them a checkpoint of this class loaded there and raised KeyError('dampening') at the first step)
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0.0, nesterov=False))
         self.grad_scale = float(grad_scale)
         self._arenas, self._hyper, self._hyper_host = [], [], []
         for group in self.param_groups:
