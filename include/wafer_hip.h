@@ -1090,6 +1090,47 @@ int wm_gmm_scatter_full(const float* x, int n, int d, int ld, const double* resp
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Logistic regression on an embedding matrix (linear_model.py: LogisticRegression, MultilabelLogisticRegression): one
+ * loss / gradient evaluation of `cols` independent columns in float64, as two passes over the rows.  The penalty, the
+ * division by the weight sum and the L-BFGS steps are host code.  Tile sizes and summation orders are stated in
+ * csrc/logreg.hip.
+ *
+ * Common to both: x as in the Gaussian-mixture section (float32 [n][ld], true feature count d, ld % 4 == 0, 16-byte
+ * aligned, columns d .. ld-1 never read), 1 <= n <= 2^24, d <= 1024, 1 <= cols <= 256.  Pointers aligned to their
+ * element, the workspace to 16 bytes and at least the companion's byte count (0: unsupported sizes; the companions
+ * launch nothing).  No atomics, no allocation, no synchronisation; every sum has an order that depends on (n, d) alone:
+ * two calls give the same bits, and a problem's loss, residual columns and gradient rows are the same bits whichever
+ * other problems share the call.
+ *
+ * wm_logreg_residual.  w float64 [cols][d + 1], column d the intercept.  z[i][q] = sum_f x[i][f] w[q][f] (f ascending,
+ * float64 MFMA tiles) + w[q][d], added last.  z_out (optional) float64 [n][cols] receives z.
+ *   mode 0 (softmax)  cols = groups * classes, group g owns columns g * classes .. g * classes + classes - 1.  y int32
+ *                     [n] in [-1, classes).  Per (row, group): m = max z, lse = m + log(sum exp(z - m)) in class order,
+ *                     p = exp(z - lse); with s_i = sw[i] (1 if sw == NULL): loss_i = s_i (lse - z_y),
+ *                     resid = s_i (p - onehot(y)).  A row with y == -1 has weight 0: its resid row is exact zeros and
+ *                     it adds an exact 0 to the loss.  loss float64 [groups].
+ *   mode 1 (sigmoid)  cols = groups * classes, column g * classes + l reads label l of y int8 [n][classes] (0 / 1).
+ *                     a = pos_weight[l] if y == 1 (1 if pos_weight == NULL or y == 0); with e = exp(-|z|):
+ *                     loss_i = s_i a (max(-z, 0) + log1p(e)) if y == 1, else s_i (max(z, 0) + log1p(e));
+ *                     resid = -s_i a sigma(-z) if y == 1, else s_i sigma(z), sigma from e alone (no exp of a positive
+ *                     argument).  loss float64 [cols].
+ *   y == NULL         prediction: resid receives p (mode 0) or sigma(z) (mode 1); loss, sw, pos_weight are not used.
+ * loss[p] = the sum of loss_i: over a tile of 64 rows the butterfly tree (partners 32, 16, .. 1 rows away), the four
+ * tiles of a slab of 256 rows as (t0 + t1) + (t2 + t3), the slabs in slab order (runs of ceil(slabs / 256) consecutive
+ * slabs, then the 256 run sums in order: wm_gmm_normalize's rule for lpn_sum).  z never goes through memory between
+ * the product and the softmax. */
+size_t wm_logreg_residual_workspace_bytes(int n, int d, int ld, int cols, int mode, int classes);
+int wm_logreg_residual(const float* x, int n, int d, int ld, const double* w, int cols, int mode, int classes,
+                       const void* y, const double* sw, const double* pos_weight, double* resid, double* loss,
+                       double* z_out, void* workspace, size_t workspace_bytes, void* stream);
+/* grad float64 [cols][d + 1] = resid^T [x | 1], resid float64 [n][cols]: wm_gmm_weighted_sums' launch path (the same
+ * tile kernel, the same cut of the rows, the planes added in slice order) with sx and nk stored at pitch d + 1, so
+ * grad[q][:d] and grad[q][d] are the bits wm_gmm_weighted_sums returns as sx[q] and nk[q]. */
+size_t wm_logreg_gradient_workspace_bytes(int n, int d, int ld, int cols);
+int wm_logreg_gradient(const float* x, int n, int d, int ld, const double* resid, int cols, double* grad, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Laplacian eigenmaps (manifold.py: laplacian_eigenpairs, spectral_layout, SpectralEmbedding): the device side of a
  * thick-restart Lanczos iteration with full reorthogonalisation on N = D^-1/2 G D^-1/2 in float64.  The small
  * eigenproblem of T and the component search are host code.  Every summation order is stated in csrc/spectral.hip.

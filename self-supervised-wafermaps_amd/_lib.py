@@ -346,6 +346,12 @@ SIGNATURES = {
     "wm_gmm_scatter_full_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "wm_gmm_scatter_full": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    # ---- logistic regression
+    "wm_logreg_residual_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "wm_logreg_residual": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wm_logreg_gradient_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_logreg_gradient": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ---- Laplacian eigenmaps
     "wm_spec_degree_workspace_bytes": (c_size_t, [c_int]),
     "wm_spec_degree": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

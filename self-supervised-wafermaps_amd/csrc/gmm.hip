@@ -71,6 +71,7 @@
 //                   not coalesce; the rows are short (k <= 1024) and walked three times out of L1 / L2.  Not measured
 //                   against a transposing LDS stage.
 #include "f64.h"
+#include "rows_sums.h"
 
 namespace {
 
@@ -412,17 +413,18 @@ __global__ __launch_bounds__(GM_THREADS) void gm_rows_tile(GmRowsArgs a) {
       }
 }
 
-// The planes [slices][k][d + 1] added in slice order: columns 0 .. d-1 -> sx, column d -> nk.
+// The planes [slices][k][d + 1] added in slice order: columns 0 .. d-1 -> sx (pitch sx_ld), column d -> nk (pitch
+// nk_ld; wm_logreg_gradient stores both into one array of pitch d + 1, which the two pointers may not be told apart by).
 __global__ __launch_bounds__(GM_THREADS) void gm_wsum_merge(const double* __restrict__ planes, int slices, int k, int d,
-                                                            double* __restrict__ nk, double* __restrict__ sx) {
+                                                            double* nk, int nk_ld, double* sx, int sx_ld) {
   const int W = d + 1;
   const long long e = (long long)blockIdx.x * GM_THREADS + threadIdx.x;
   if (e >= (long long)k * W) return;
   const int c = (int)(e / W), f = (int)(e - (long long)c * W);
   double sum = 0.0;
   for (int s = 0; s < slices; ++s) sum += planes[(size_t)s * k * W + e];
-  if (f < d) sx[(size_t)c * d + f] = sum;
-  else nk[c] = sum;
+  if (f < d) sx[(size_t)c * sx_ld + f] = sum;
+  else nk[(size_t)c * nk_ld] = sum;
 }
 
 // out[c][i][j] = the sum over the slices, in slice order, of the lower triangle's cell (max(i, j), min(i, j)).
@@ -546,9 +548,26 @@ extern "C" int wm_gmm_normalize(double* wlp_inout, int n, int k, double* lpn, in
   return WM_OK;
 }
 
-extern "C" size_t wm_gmm_weighted_sums_workspace_bytes(int n, int d, int ld, int k) {
+size_t wm_rows_sums_workspace_bytes(int n, int d, int ld, int k) {
   if (!gm_ok(n, d, ld, k, GM_MAX_D_DIAG)) return 0;
   return (size_t)gm_wsum_shape(n, d).slices * k * (d + 1) * sizeof(double);
+}
+
+int wm_rows_sums_launch(const float* x, int n, int d, int ld, const double* resp, int k, double* nk, int nk_ld, double* sx,
+                        int sx_ld, void* workspace, hipStream_t st) {
+  const F64Slices s = gm_wsum_shape(n, d);
+  GmRowsArgs a{x, resp, nullptr, static_cast<double*>(workspace), n, d, ld, k, s.slice_rows, 0};
+  gm_rows_tile<GM_WSUM><<<dim3((k + GM_TILE - 1) / GM_TILE, (d + 1 + GM_TILE - 1) / GM_TILE, s.slices), GM_THREADS, 0, st>>>(a);
+  WM_LAUNCH_CHECK();
+  const long long cells = (long long)k * (d + 1);
+  gm_wsum_merge<<<(int)((cells + GM_THREADS - 1) / GM_THREADS), GM_THREADS, 0, st>>>(a.planes, s.slices, k, d, nk, nk_ld, sx,
+                                                                                   sx_ld);
+  WM_LAUNCH_CHECK();
+  return WM_OK;
+}
+
+extern "C" size_t wm_gmm_weighted_sums_workspace_bytes(int n, int d, int ld, int k) {
+  return wm_rows_sums_workspace_bytes(n, d, ld, k);
 }
 
 extern "C" int wm_gmm_weighted_sums(const float* x, int n, int d, int ld, const double* resp, int k, double* nk, double* sx,
@@ -558,15 +577,7 @@ extern "C" int wm_gmm_weighted_sums(const float* x, int n, int d, int ld, const 
   WM_REQUIRE(wm_aligned(x, 15) && wm_aligned(resp, 7) && wm_aligned(nk, 7) && wm_aligned(sx, 7) && wm_aligned(workspace, 15),
              WM_EALIGN);
   WM_REQUIRE(workspace_bytes >= wm_gmm_weighted_sums_workspace_bytes(n, d, ld, k), WM_EWORKSPACE);
-  const F64Slices s = gm_wsum_shape(n, d);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  GmRowsArgs a{x, resp, nullptr, static_cast<double*>(workspace), n, d, ld, k, s.slice_rows, 0};
-  gm_rows_tile<GM_WSUM><<<dim3((k + GM_TILE - 1) / GM_TILE, (d + 1 + GM_TILE - 1) / GM_TILE, s.slices), GM_THREADS, 0, st>>>(a);
-  WM_LAUNCH_CHECK();
-  const long long cells = (long long)k * (d + 1);
-  gm_wsum_merge<<<(int)((cells + GM_THREADS - 1) / GM_THREADS), GM_THREADS, 0, st>>>(a.planes, s.slices, k, d, nk, sx);
-  WM_LAUNCH_CHECK();
-  return WM_OK;
+  return wm_rows_sums_launch(x, n, d, ld, resp, k, nk, 1, sx, d, workspace, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t wm_gmm_scatter_diag_workspace_bytes(int n, int d, int ld, int k) {
