@@ -1241,6 +1241,27 @@ size_t wm_lof_indegree_workspace_bytes(int rows, int ld, int groups);
 int wm_lof_indegree(const int32_t* idx, int rows, int ld, int n, const int32_t* ks, int groups, int32_t* indeg,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian log-sums over all pairs (density.py: KernelDensity, KDEClassifier, uniformity) in float64.  The mapping and
+ * every summation order are stated in csrc/kde.hip.
+ *   out[q][i] = log sum_j exp(-inv_two_h2[q] * s_ij),   out row-major [b][m],
+ * over the columns j of x [n][d] that are not excluded, for the rows i of xr [m][d].  s_ij is the SQUARED Euclidean
+ * distance as the all-pairs kernels build it before the root: float32 fused multiply-adds over the features in index
+ * order in one accumulator, widened exactly to double (s_ij and s_ji are the same bits; equal rows give exactly 0;
+ * relative error at most (d + 2) 2^-24, first order).  Column j is excluded for row i when self_offset >= 0 and
+ * j + self_offset == i: 0 with xr == x is the leave-one-out sum, `lo` with x = xr + lo * d the leave-one-out sum against
+ * the rows lo .. lo + n - 1 of xr, -1 excludes nothing.  A duplicate of a row is another column and counts.  A row
+ * without an included column gives -inf; a pair whose s is not finite contributes nothing.  inv_two_h2 is a HOST array
+ * of b values, 1 <= b <= WM_KDE_MAX_BANDWIDTHS, every one finite and > 0 (WM_EINVAL otherwise, and for self_offset < -1,
+ * before any launch; a caller with a longer list calls once per chunk).  d % 4 == 0, d <= 1024, 1 <= m, n <= 2^24; xr, x
+ * and the workspace aligned to 16 bytes, out to 8.  Exponent arithmetic and sums in float64; one running minimum of s per
+ * row is the shift of every bandwidth, so a bandwidth gives the same bits alone as inside any list; no atomics: two calls
+ * give the same bits.  The size function answers 0 for sizes outside these limits. */
+#define WM_KDE_MAX_BANDWIDTHS 4
+size_t wm_kde_logsum_workspace_bytes(int m, int n, int d, int b);
+int wm_kde_logsum(const float* xr, int m, const float* x, int n, int d, const double* inv_two_h2, int b, int self_offset,
+                  double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debugging probe (no reference counterpart): *slot = max(*slot, max_i |x[i]|), NaN if any x[i] is NaN
  * (+inf stays +inf).  x: n elements of WM_F32 / WM_BF16; *slot must hold a non-negative float (zero it
  * first).  Allocates nothing, so it can sit between the launches of a captured hipGraph

@@ -384,6 +384,10 @@ SIGNATURES = {
                               c_void_p]),
     "wm_lof_indegree_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wm_lof_indegree": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- Gaussian log-sums over all pairs (inv_two_h2 is a host array)
+    "wm_kde_logsum_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wm_kde_logsum": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
     # ---- UMAP
     "wm_umap_smooth_knn":(c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wm_umap_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double,

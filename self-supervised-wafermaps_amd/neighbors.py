@@ -33,6 +33,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream_ptr
 from .cluster import metric_code
+from .density import KernelDensity  # noqa: F401  (sklearn's class lives in neighbors: neighbors.KernelDensity is density's)
 from .manifold import _token_ws, knn_graph, knn_query
 
 MAX_K = 63  # columns of a list: one wave64 lane each, the last lane idle (csrc/lof.hip)
