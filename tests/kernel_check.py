@@ -24,7 +24,9 @@ the launch arithmetic their block sums follow, the pooling of csrc/pool.hip), ea
 switches that seed one wrong computation, and the input families.  tests/test_kernel_check_cpu.py proves on the CPU
 that every seeded error is rejected by `check` on these families; the GPU tests feed the kernels the same families.
 The loss kernels of csrc/embed.hip have theirs in the sibling tests/loss_cases.py, the float32 kernels of csrc/f32path.hip in
-tests/f32_cases.py (check(..., ulp=2^-23), inputs drawn inside float32_inputs()).
+tests/f32_cases.py (check(..., ulp=2^-23), inputs drawn inside float32_inputs()), the ViT losses and the token plumbing of
+the second half of csrc/transformer.hip (MSE / L1, DINO, soft cross-entropy, the mean-entropy regulariser, tokens_assemble,
+patchify, row gather / scatter, argsort, the plain column sums, the small float32 matmul) in tests/vit_cases.py.
 """
 import contextlib
 import math
