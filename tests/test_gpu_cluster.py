@@ -14,6 +14,7 @@ import torch
 from parity_log import parity
 from pathlib import Path
 
+from cluster_cases import components, eps, max_rel, rows  # noqa: F401  (shared with the slice-level tests; sibling files import them from here)
 from test_cluster_cpu import BLOB_PARAMS, lattice_points, pairwise64, prim_mst, same_clustering
 
 pytestmark = pytest.mark.gpu
@@ -22,19 +23,6 @@ DEV = "cuda:0"
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden"
 METRICS = ["euclidean", "manhattan"]
-
-
-def eps(d):
-    return (d + 3) * 2.0 ** -24
-
-
-def rows(n, d, seed):
-    """float32 rows with exact duplicates among them (rows 3, 5, 7 and the last equal row 0 when they exist)."""
-    x = np.random.default_rng(seed).standard_normal((n, d)).astype(np.float32)
-    for i in (3, 5, 7, n - 1):
-        if 0 < i < n:
-            x[i] = x[0]
-    return x
 
 
 _CACHE = {}
@@ -60,14 +48,6 @@ def lattice32(metric):
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def max_rel(got, want):
-    """Largest relative error where the reference is positive; where it is exactly 0 so must the result be."""
-    got, want = np.asarray(got, dtype=np.float64).ravel(), np.asarray(want, dtype=np.float64).ravel()
-    zero = want == 0
-    assert (got[zero] == 0).all(), "an exactly zero reference needs an exactly zero result"
-    return float(np.max(np.abs(got - want)[~zero] / want[~zero])) if (~zero).any() else 0.0
 
 
 # ------------------------------------------------------------------------------------------------ core distances
@@ -102,14 +82,6 @@ def test_core_distance_against_float64(n, d):
 
 
 # ------------------------------------------------------------------------------------------------ one Boruvka round
-
-
-def components(n, kind):
-    if kind == "singletons":
-        return np.arange(n, dtype=np.int32)[::-1].copy()  # ids are labels, not positions
-    if kind == "halves":
-        return (np.arange(n) % 2).astype(np.int32) * 7 + 2
-    return np.full(n, 5, dtype=np.int32)
 
 
 def brute_min_edge(dist, core, comp):
